@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Benchmark of the per-frame memory-readout path (BASELINE.json: frames/sec at 480p, 1 object, 32 memory frames).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload b32|b32dyn|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload b32|b32dyn|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is given, and prints
+the JSON line (`value`, `ms_per_step`, ...).  Everything else it can measure - the long window, the instrumented passes, the
+kernel trace, the un-hinted pass, the opt-in precision modes, the CPU baseline and its parity check - runs with --full only.
 
 Workloads (`--workload`, default b32 = BASELINE configs[1], the one the metric is quoted on):
   b32     480x854, 1 object, 32 annotated frames preloaded with put_to_permanent_memory, mem_every=1e9: N stays 32*1620
@@ -62,6 +66,7 @@ CLEAR_MARGIN = 2e-2                    # the tests' gate (tests/test_gpu_e2e.py)
 TIGHT_MARGIN = 2e-3                    # SURVEY 8(c)'s acceptance margin, reported beside it
 SCHEMA = 6                             # meaning of the keys of the JSON line; see `schema_note` in the line
 LONG_WINDOW = 200                      # frames of `value_long_window` (reported when --steps is shorter)
+DUMP_BYTES = 64 * 2 ** 20              # --dump-outputs: all arrays together at most this large (float32)
 BASELINE_METRIC = 'frames/sec at 480p, 1 obj, 32 memory frames; mask IoU vs reference'
 
 PRECISION_LABEL = {'fp32': '',
@@ -230,17 +235,19 @@ def run_gpu(args, device, rank, world):
 
     host_t = {'step': 0.0, 'hint': 0.0, 'fetch': 0.0, 'n': 0} if os.environ.get('XMEM_BENCH_HOST_TIMES') else None
 
+    last = {}                                        # the probabilities of the latest step (a view, valid until the next step)
+
     def one_step(i, stop=None, origin=0):
         # `stop`: one past the last frame of the stream being driven; `origin`: its first frame (the phase of the key batches).  A finite
         # stream does not hint a batch that starts at or past its end (run_on_video does not either); a batch that straddles the end is
         # hinted whole (no new graph variant inside a timed region - the frames past the end are extra work INSIDE it).
         if host_t is None:
-            prob = core.step(frame(i), None, None)
+            prob = last['prob'] = core.step(frame(i), None, None)
             if (i - origin) % KB == 0 and (stop is None or i + KB < stop):   # first frame of its batch consumed: hint the next batch under it
                 hint(i + KB)
             return [m for _, m in fetcher.submit(i, ops.argmax_u8(prob))]
         t0 = time.perf_counter()
-        prob = core.step(frame(i), None, None)
+        prob = last['prob'] = core.step(frame(i), None, None)
         t1 = time.perf_counter()
         if (i - origin) % KB == 0 and (stop is None or i + KB < stop):
             hint(i + KB)
@@ -286,6 +293,11 @@ def run_gpu(args, device, rank, world):
         ops.trace_marker(2)
     torch.cuda.synchronize(device); barrier(device)
     elapsed = time.perf_counter() - t0
+    # what a caller of the timed path received for its last frame: the probabilities step() returned and the uint8 mask on the host
+    # (copied before anything else runs on the device - the probabilities may live in a captured graph's output buffer)
+    outputs = None
+    if rank == 0 and getattr(args, 'dump_outputs', None):
+        outputs = dict(last_step_prob=last['prob'].float().cpu().numpy(), last_step_mask=out_masks[-1].astype(np.float32))
     if host_t is not None:
         n = max(host_t['n'], 1)
         print(f"[host ms per frame over {n} calls incl. setup] step {1e3 * host_t['step'] / n:.3f}  hint {1e3 * host_t['hint'] / n:.3f} "
@@ -467,7 +479,22 @@ def run_gpu(args, device, rank, world):
     return dict(elapsed=elapsed, preload_s=preload_s, taps=taps, inst_frames=inst_frames, inst_elapsed=inst_elapsed,
                 masks=out_masks, core=core, frames=frames, masks_in=masks, sd=sd, n_query=n_query, base=base,
                 n_elems=n_elems, wl=wl, cfg=cfg, filter_events=filt, candidates=cand, plain=plain, frame_fn=frame,
-                conv_survey=conv_survey, select_alone=select_alone, long_window=long_window)
+                conv_survey=conv_survey, select_alone=select_alone, long_window=long_window, outputs=outputs)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """arrays (name -> ndarray) as float32 `out_dir/<name>.npy`.  If together they exceed `budget` bytes, every array is replaced by
+    the same fixed, seeded sample of its flattened elements (a fraction of each that fits), so that two runs stay comparable."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > budget:
+            n = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            print(f'[bench] {name}: {n} of {arrays[name].size} elements (seeded sample, the outputs exceed {budget} bytes)', file=sys.stderr)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 # ---- rocprofv3 kernel trace of the timed region (child process) ------------------------------------------------
@@ -557,7 +584,7 @@ def run_mode_child(args, mode):
     steps = min(args.steps, 120)
     cmd = [sys.executable, os.path.abspath(__file__), '--precision', mode, '--steps', str(steps), '--warmup', str(args.warmup),
            '--workload', args.workload, '--key-batch', str(args.key_batch), '--no-cpu-baseline', '--no-kernel-trace', '--plain-steps', '0',
-           '--no-extra-modes']
+           '--no-extra-modes', '--full']
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
@@ -857,7 +884,12 @@ def parse_args(argv=None):
                     'collective).  gloo (default): every rank sees only its own GPU (device isolation as xmem2_amd.launch), reductions on the '
                     'host.  nccl: RCCL control plane, every device stays visible to every rank')
     ap.add_argument('--scale-only', action='store_true', help='only the timed region and the JSON line: no traced child, no opt-in mode children, '
-                    'no un-hinted pass, no instrumented passes, no CPU baseline (what a multi-GPU scaling run needs; implied on ranks != 0)')
+                    'no un-hinted pass, no instrumented passes, no CPU baseline (what a multi-GPU scaling run needs; implied without --full and '
+                    'for N > 1)')
+    ap.add_argument('--full', action='store_true', help='measure everything besides the headline as well: long window, instrumented passes, '
+                    'kernel trace, un-hinted pass, opt-in precision modes, CPU baseline and parity (N = 1; without it a run is --scale-only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step returned (probabilities, uint8 mask) '
+                    'as float32 DIR/<name>.npy (at most 64 MB in all)')
     return ap.parse_args(argv)
 
 
@@ -870,6 +902,8 @@ def main():
         torch.utils.deterministic.fill_uninitialized_memory = True
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 or args.gpus > 1:
         args.scale_only = True                     # a scaling run measures the timed region only, on every rank alike
+    if not args.full:
+        args.scale_only = True                     # a plain run: set-up, warm-up, the timed steps, [--dump-outputs], the line
     if args.scale_only:
         args.no_cpu_baseline = args.no_kernel_trace = args.no_extra_modes = True
         args.plain_steps = 0
@@ -934,6 +968,8 @@ def main():
         first, count = (int(v) for v in os.environ['XMEM_MAIN_CUS'].split(':'))
         torch.cuda.set_stream(_ops.masked_stream(device, count, first))
     res = run_gpu(args, device, rank, world)
+    if res.get('outputs') is not None:
+        dump_outputs(args.dump_outputs, res['outputs'])
     elapsed = max_over_ranks(res['elapsed'], device)
     total_frames = sum_over_ranks(args.steps, device)
     per_rank = [args.steps / e for e in gather_over_ranks(res['elapsed'], device)]

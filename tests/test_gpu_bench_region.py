@@ -6,6 +6,7 @@ spies on the core's entry points and on bench.barrier (called right before the c
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -48,10 +49,16 @@ def test_timed_region_holds_all_the_work_of_its_frames(monkeypatch):
     monkeypatch.setattr(InferenceCore, 'step', step)
     monkeypatch.setattr(bench, 'barrier', barrier)
 
-    args = bench.parse_args(['--scale-only', '--steps', str(steps), '--warmup', str(warmup)])
+    args = bench.parse_args(['--scale-only', '--steps', str(steps), '--warmup', str(warmup), '--dump-outputs', 'unused'])
     KB = max(1, args.key_batch)
     res = bench.run_gpu(args, torch.device('cuda', 0), 0, 1)
     assert len(res['masks']) == steps
+    # --dump-outputs: what the last timed step handed its caller, taken before anything else ran on the device
+    out = res['outputs']
+    wl = bench.WORKLOADS[args.workload]
+    assert out['last_step_prob'].shape == (wl['K'] + 1, wl['H'], wl['W']) and out['last_step_mask'].shape == (wl['H'], wl['W'])
+    assert np.array_equal(out['last_step_mask'], res['masks'][-1]) and np.isfinite(out['last_step_prob']).all()
+    assert np.abs(out['last_step_prob'].sum(0) - 1).max() < 1e-3
 
     marks = [i for i, e in enumerate(log) if e[0] == 'barrier']
     assert len(marks) == 2, log

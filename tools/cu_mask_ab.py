@@ -18,7 +18,7 @@ VARIANTS = [('baseline', {}),
 
 
 def run(env_extra, trace):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--no-extra-modes', '--plain-steps', '0', '--steps', '200']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--no-extra-modes', '--plain-steps', '0', '--steps', '200']
     if not trace:
         cmd.append('--no-kernel-trace')
     p = subprocess.run(cmd, env=dict(os.environ, **env_extra), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=400)
