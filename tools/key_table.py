@@ -12,9 +12,9 @@ dev = torch.device('cuda:0')
 cfg = bench.b32_config()
 net = XMem(dict(cfg), None).to(dev).eval(); net.load_weights(synthetic_state_dict(0))
 img = torch.randn(B, 480, 864, 4, device=dev); img[..., 3] = 0
-net._encode_key_eager(img, True, True, False, True)
+net._encode_key_eager(img, True, True, inline_skips=True)
 ops.RECORD = []
-net._encode_key_eager(img, True, True, False, True)
+net._encode_key_eager(img, True, True, inline_skips=True)
 records, ops.RECORD = ops.RECORD, None
 rows = {}
 for kind, key, flop, fn, keep in records:

@@ -1,5 +1,5 @@
 """Pass-1 filter kernel and whole hinted call at the three served memory sizes (synthetic keys, perfect hint):
-   python tools/probes/filter_sizes.py [b32 c4 c5]      (XMEM_F16_SPLITS=n overrides the split count for an A/B)"""
+   python tools/probes/filter_sizes.py [b32 c4 c5]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'tests'))

@@ -31,7 +31,7 @@ for (H, W, K) in GEOMS:
         for B in (2, 4, 8):
             img = torch.zeros(B, (H + 15) // 16 * 16, (W + 15) // 16 * 16, 4, device='cuda')
             with ops.precision(PREC):
-                net._encode_key_eager(img, True, True, False, True)
+                net._encode_key_eager(img, True, True, inline_skips=True)
     # the decoder fuser with its frame-only half pre-convolved in the key pass (prefetched frames): the per-object half's shapes
     h16, w16 = (H + 15) // 16, (W + 15) // 16
     with ops.precision(PREC):

@@ -600,8 +600,7 @@ __global__ __launch_bounds__(64 * RF_WAVES, RF_MINWG) void affinity_refine_kerne
 
 // per-query candidate list length: ~N/64 (redundant memories keep thousands of near-ties for a few queries), 2048 .. 16384
 int aff_filter16_list_cap(int n_total) {
-    static const int cmin = getenv("XMEM_AFF_LCAP_MIN") ? atoi(getenv("XMEM_AFF_LCAP_MIN")) : 2048;     // tools: A/B of the floor
-    int c = cmin >= 256 && cmin <= 16384 ? cmin : 2048;
+    int c = 2048;
     while (c < n_total / 64 && c < 16384) c *= 2;
     return c;
 }
@@ -636,14 +635,12 @@ int aff_filter16_launch(Filter16Args a, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // 8-wave workgroups (512 queries, one per CU) when the query count fills them and the memory is long enough: the rows
     // cross the fabric once per 512 instead of once per 256 queries
-    int nw = (a.HW >= 2048 && a.total_tiles >= 8192) ? 8 : 4;
-    if (const char* e = getenv("XMEM_F16_WAVES")) nw = atoi(e) == 8 ? 8 : 4;   // tools: A/B
+    const int nw = (a.HW >= 2048 && a.total_tiles >= 8192) ? 8 : 4;
     const int wgq = 64 * nw, stage = nw, per_xcd = nw == 4 ? 32 * F16_WG_PER_CU : 32;
     const int qt = cdiv(a.HW, wgq);
     // all workgroups of a split resident on one XCD at once when the query tiles allow: 8 x floor(per_xcd / query tiles) splits,
     // whole LDS stages, >= 2 stages per split
     int sp = 8 * (per_xcd / qt); if (sp < 8) sp = 8;
-    if (const char* e = getenv("XMEM_F16_SPLITS")) { sp = atoi(e); if (sp < 1) sp = 1; }   // tools: A/B of the split count
     { int maxs = a.total_tiles / (2 * stage); if (maxs < 1) maxs = 1; if (sp > maxs) sp = maxs; }
     a.tiles_per_split = cdiv(cdiv(a.total_tiles, sp), stage) * stage;
     a.splits = cdiv(a.total_tiles, a.tiles_per_split);

@@ -541,7 +541,6 @@ __global__ __launch_bounds__(256) void conv_cout1_kernel(ConvArgs p) {
 // wave per pixel every wave fetched its own 3 x 3 input vectors and the nine weight vectors: 18 KB through the vector cache for 1 KB of
 // new input - 466 MB per launch, 20 us for 60 MFLOP.  Four pixels share a 3 x 6 patch and one set of weights: 27 KB per four pixels
 // (3.4x fewer bytes through the cache).  Per pixel the products and the order of the additions are those of conv_cout1_kernel: same bits.
-static bool cout1_row4() { static const bool on = !(getenv("XMEM_COUT1_ROW4") && getenv("XMEM_COUT1_ROW4")[0] == '0'); return on; }   // tools: A/B
 __global__ __launch_bounds__(256) void conv_cout1_row4_kernel(ConvArgs p) {
     const int lane = threadIdx.x & 63;
     const int gpr = (p.Wo + 3) >> 2;                              // groups of four pixels per output row
@@ -1355,8 +1354,6 @@ static inline void transform_grid(size_t items, int& blocks, int& threads) {
 }
 
 static bool conv_is_one(const ConvArgs& a) {
-    static const int off = getenv("XMEM_CONV_ONE") && getenv("XMEM_CONV_ONE")[0] == '0';
-    if (off) return false;
     return a.KH == 1 && a.KW == 1 && a.pad == 0 &&
            (double)a.B * a.H * a.W * a.ldin * 4.0 < 4.0e9 && (double)a.Cout * a.K * 4.0 < 4.0e9;
 }
@@ -1603,7 +1600,7 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
         // requested together: four pixels per wave 26.8 us against 31.2 (host-side events, same bits), +0.6 % on the B32 line; small maps
         // (2 x 37 x 51: 21 against 16 us) keep one pixel per wave - too few waves otherwise)
         if (half) hipLaunchKernelGGL(conv_cout1_kernel<true>, dim3(cdiv(a.M, 4)), dim3(256), 0, s, a);
-        else if (cout1_row4() && a.M >= 8192 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Cin <= 256 && a.Ho == a.H + 2 * a.pad - 2 && a.Wo == a.W + 2 * a.pad - 2)
+        else if (a.M >= 8192 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.Cin <= 256 && a.Ho == a.H + 2 * a.pad - 2 && a.Wo == a.W + 2 * a.pad - 2)
             hipLaunchKernelGGL(conv_cout1_row4_kernel, dim3(cdiv(a.B * a.Ho * ((a.Wo + 3) / 4), 4)), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(conv_cout1_kernel<false>, dim3(cdiv(a.M, 4)), dim3(256), 0, s, a);
         return xmem_check_launch();

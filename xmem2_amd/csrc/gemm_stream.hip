@@ -313,8 +313,10 @@ int gemm_stream_launch(GemmStreamArgs& a, int variant, int ring, hipStream_t s) 
     if (a.K % 32 != 0 || a.K <= 0 || a.M <= 0 || a.N <= 0 || a.G <= 0) return XMEM_ERR_UNSUPPORTED;
     if (variant < 0 || variant > 2 || (ring != 3 && ring != 4)) return XMEM_ERR_BAD_ARG;
     const int bm = variant == 0 ? 64 : 128, bn = variant == 2 ? 128 : 64;
-    static const int dbg = getenv("XMEM_STREAM_DBG") ? atoi(getenv("XMEM_STREAM_DBG")) : 0;
-    a.dbg = dbg;
+    a.dbg = 0;
+#ifdef XMEM_TOOLS
+    { static const int dbg = getenv("XMEM_STREAM_DBG") ? atoi(getenv("XMEM_STREAM_DBG")) : 0; a.dbg = dbg; }
+#endif
     a.nk = a.K / 32;
     a.tiles_m = cdiv(a.M, bm); a.tiles_n = cdiv(a.N, bn);
     const long units = (long)a.G * a.tiles_m * a.tiles_n;

@@ -12,13 +12,9 @@ to the LAST ``get_v_size(g)`` keys of the store.
 Row-major views are exposed for the kernels (``key_rows`` ...); the reference-shaped properties
 (``key`` ``1 x C x N`` ...) are zero-copy transposed views for callers such as the GUI gauges.
 """
-import os
-
 import torch
 
 from . import ops
-
-KEEP_ROWS16 = os.environ.get('XMEM_KEEP_ROWS16', '1') != '0'     # 0: the readout derives its fp16 operand rows per call (A/B runs)
 
 
 class _Arena:
@@ -185,7 +181,7 @@ class KeyValueMemoryStore:
         self._k = _Arena([], ck, device)
         self._s = _Arena([], 0, device)
         self._e = _Arena([], ck, device)
-        self._r16 = _Arena([], ops.ROWS16_FLOATS, device) if (ck == 64 and KEEP_ROWS16) else None
+        self._r16 = _Arena([], ops.ROWS16_FLOATS, device) if ck == 64 else None
         self._has_s, self._has_e = has_s, has_e
         if self.count_usage:
             self._use = _Arena([], 0, device)

@@ -26,6 +26,10 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
+# captured HIP-graph stages kept before the least recently replayed one is dropped
+MAX_STAGES = 160
+
+
 def _padc(n):
     """channel padding of a buffer the network allocates: 4 floats or (fp16 loop) 8 halfs = one 16-byte operand chunk"""
     return (n + 7) // 8 * 8 if ops.act_dtype() == torch.float16 else _pad4(n)
@@ -52,23 +56,6 @@ class XMem:
         self._zeros = {}
         self._owner_free, self._owner_next = [], 0   # owner tokens of the cores driving this network (see acquire_owner)
         self._call_precision = None      # per-call override (InferenceCore preloads permanent memory in fp32)
-        self.max_stages = int(os.environ.get('XMEM_MAX_STAGES', '160'))   # captured HIP-graph stages kept before the cache is dropped
-        # the decoder's skip convolutions depend only on f8 / f4: inside the captured key-encoder graph they run on a
-        # forked stream next to the small-grid layer2 / layer3 kernels.  Measured neutral on MI355X (A/B on one box:
-        # 272 vs 273 fps), so it is off by default (XMEM_OVERLAP=1 enables it).
-        self.overlap_skips = os.environ.get('XMEM_OVERLAP', '0') != '0'
-        self.share_x = os.environ.get('XMEM_SHARE_X', '1') != '0'     # several objects: convolve the shared f16 half of the fusers once
-        self.prefuse_x = os.environ.get('XMEM_PREFUSE_X', '1') != '0'  # prefetched frames: the decoder fuser's f16 half in the batched key pass
-        self._side = None
-        # GroupResBlocks with a downsample branch (fuser block1, up_16_8.out_conv): conv1 and the downsample convolution read the same
-        # tensor and are independent - inside a captured stage the downsample CAN run on a forked stream beside conv1 (same kernels,
-        # bit-identical results, tests/test_gpu_network.py).  Measured on MI355X (round 5, profiles/r05_branch_overlap_ab.txt): it LOSES -
-        # B32 614 -> 561 frames/s, C3 283 -> 276, C4 209 -> 199: with the key pass and the early readout on their own streams the chip
-        # has no idle share for a fourth queue, and the fork / join edges serialise the captured graph.  Off (XMEM_BRANCH_OVERLAP=1 enables).
-        self.branch_overlap = os.environ.get('XMEM_BRANCH_OVERLAP', '0') != '0'
-        self.fuse_hidden_update = os.environ.get('XMEM_FUSE_HIDDEN_UPDATE', '1') != '0'   # the three pointwise convolutions of HiddenUpdater as one (A/B knob)
-        self.gather_hidden_input = os.environ.get('XMEM_GATHER_HIDDEN_INPUT', '1') != '0'  # ... and their concatenated input built by one launch (A/B knob)
-        self._branch = None
         # scratch of the side-stream key-encoder stages is scoped to this instance and released with it
         self._scope = ops.new_scope()
         weakref.finalize(self, ops.release_scope, self._scope)
@@ -275,14 +262,6 @@ class XMem:
         input / output buffers and replay it.  Kernels are launched through ctypes on torch's current stream, which
         is the capturing stream inside torch.cuda.graph, so they are captured like any other launch."""
         prec = self._call_precision or self.precision
-        only = os.environ.get('XMEM_PRECISION_ONLY')          # tools: restrict a non-default precision to one stage kind
-        if only and prec == 'fp16':
-            # the fp16 loop keeps HALF activations across stage boundaries (key -> segment -> value): one stage alone cannot run in
-            # another storage type.  The knob is for the operand-only modes (fp16w / fp32x), whose tensors stay fp32.
-            raise RuntimeError("XMEM_PRECISION_ONLY does not compose with precision='fp16' (half activations cross the stage boundaries); "
-                               "use it with 'fp16w' or 'fp32x'")
-        if only and prec != 'fp32' and name != only:
-            prec = 'fp32'
         if not self.use_graphs or ops.eager_only() or name in os.environ.get('XMEM_EAGER_STAGES', '').split(','):
             with ops.precision(prec):
                 return fn(*inputs)
@@ -294,17 +273,13 @@ class XMem:
             # warm-up: sizes every workspace before the capture.  Inputs the stage updates in place (`mutates`: the hidden
             # state) are cloned for it, otherwise warm-up + first replay would advance the state twice.
             with ops.precision(prec):
-                self._in_stage = True            # warm-up and capture take the same (forked) launch sequence: same workspaces
-                try:
-                    fn(*[(t.clone() if (i in mutates and t is not None) else t) for i, t in enumerate(static_in)])
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        static_out = fn(*static_in)
-                finally:
-                    self._in_stage = False
+                fn(*[(t.clone() if (i in mutates and t is not None) else t) for i, t in enumerate(static_in)])
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static_out = fn(*static_in)
             st = (graph, static_in, static_out)
-            while len(self._stages) >= self.max_stages:
+            while len(self._stages) >= MAX_STAGES:
                 self._evict_lru()
             self._stages[full_key] = st
         else:
@@ -379,38 +354,14 @@ class XMem:
     def _group_res(self, g, p, out=None, out_ld=None):
         """GroupResBlock, model/group_modules.py:44-52: conv2(relu(conv1(relu(g)))) + (downsample(g) | g)."""
         W = self._w
-        if (p + '.downsample') in W and self._fork_ok():
-            res = self._forked(lambda: ops.conv2d(g, W[p + '.downsample']))
-            o = ops.conv2d(g, W[p + '.conv1'], relu_in=True, relu_out=True)
-            self._join()
-            return ops.conv2d(o, W[p + '.conv2'], res=res, out=out, out_ld=out_ld)
         o = ops.conv2d(g, W[p + '.conv1'], relu_in=True, relu_out=True)
         res = ops.conv2d(g, W[p + '.downsample']) if (p + '.downsample') in W else g
         return ops.conv2d(o, W[p + '.conv2'], res=res, out=out, out_ld=out_ld)
 
-    # ---- forked branch inside a stage ------------------------------------------------------------
-    def _fork_ok(self):
-        """Fork only where the launches end up in a HIP graph (a stage being warmed up or captured): eager launches would pay two
-        cross-stream waits per block for nothing."""
-        return self.branch_overlap and self.use_graphs and not ops.eager_only() and getattr(self, '_in_stage', False)
-
-    def _forked(self, fn):
-        """Run fn() on the branch stream (own scratch scope: the convolution workspaces are per stream), forked from the current one."""
-        main = torch.cuda.current_stream()
-        if self._branch is None:
-            self._branch = torch.cuda.Stream(device=self.device)
-        self._branch.wait_stream(main)
-        with torch.cuda.stream(self._branch), ops.ws_scope(getattr(ops._tls, 'suffix', '') + f'@branch#{self._scope}#'):
-            out = fn()
-        return out
-
-    def _join(self):
-        torch.cuda.current_stream().wait_stream(self._branch)
-
     def _shares_x(self, p, n_obj):
         """True when `_fusion(cat, p, x)` convolves the shared x half once (several objects, split weights uploaded)."""
         W = self._w
-        return n_obj > 1 and self.share_x and (p + '.block1.conv1@x') in W and (p + '.block1.downsample@x') in W
+        return n_obj > 1 and (p + '.block1.conv1@x') in W and (p + '.block1.downsample@x') in W
 
     def _fusion(self, cat, p, x=None, pre=None):
         """FeatureFusionBlock, model/modules.py:31-41, on the already concatenated [x | g] tensor.  With several objects
@@ -425,13 +376,8 @@ class XMem:
             # pre = (conv1@x(relu(x)), downsample@x(x)) already made in the batched key pass (prefetched frames)
             sx = pre[0] if pre is not None else ops.conv2d(x, W[b1 + '.conv1@x'], relu_in=True)
             dx = pre[1] if pre is not None else ops.conv2d(x, W[b1 + '.downsample@x'])
-            if self._fork_ok():
-                res = self._forked(lambda: ops.conv2d(gpart, W[b1 + '.downsample@g'], res=dx, res_broadcast=True, in_ld=ld, cin=cg))
-                o = ops.conv2d(gpart, W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True, in_ld=ld, cin=cg)
-                self._join()
-            else:
-                o = ops.conv2d(gpart, W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True, in_ld=ld, cin=cg)
-                res = ops.conv2d(gpart, W[b1 + '.downsample@g'], res=dx, res_broadcast=True, in_ld=ld, cin=cg)
+            o = ops.conv2d(gpart, W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True, in_ld=ld, cin=cg)
+            res = ops.conv2d(gpart, W[b1 + '.downsample@g'], res=dx, res_broadcast=True, in_ld=ld, cin=cg)
             g = ops.conv2d(o, W[b1 + '.conv2'], res=res)
         else:
             g = self._group_res(cat, b1)
@@ -452,40 +398,26 @@ class XMem:
     # ---- hot path (NHWC) ------------------------------------------------------------------------
     def encode_key_nhwc(self, image4, need_sk=True, need_ek=True, with_skips=False, slot=0, inline_skips=False):
         """image4 [B,Hp,Wp,4] -> key [B*h*w,Ck], shrinkage [B*h*w]|None, selection|None, f16, f8, f4 (NHWC)
-        [+ (skip8, skip4), the decoder's skip convolutions of f8 / f4, when with_skips and the graph path is active].
+        [+ the decoder's skip convolutions of f8 / f4 (and the decoder fuser's f16 half) when inline_skips, else None, when with_skips].
         With graphs on, the returned tensors are the stage's static buffers: valid until the next call
         with the same `slot` (two slots let the key encoder of frame t+1 run while frame t is still being decoded)."""
         self._need_weights()
-        overlap = bool(with_skips and not inline_skips and self.overlap_skips and self.use_graphs and not ops.eager_only()
-                       and image4.shape[0] == 1)
         inline = bool(with_skips and inline_skips)      # a prefetched pass also runs the decoder's skip convolutions
         # key-encoder graphs may run on a side stream: never share scratch with the decoder, nor with another network instance
         self._key_ws = f'@key{slot}#{self._scope}#'
         with ops.ws_scope(self._key_ws):
-            out = self._run_stage('key', (need_sk, need_ek, overlap, inline, slot), [image4],
-                                  lambda im: self._encode_key_eager(im, need_sk, need_ek, overlap, inline))
+            out = self._run_stage('key', (need_sk, need_ek, inline, slot), [image4],
+                                  lambda im: self._encode_key_eager(im, need_sk, need_ek, inline))
         if with_skips:
-            return out if (overlap or inline) else tuple(out) + (None,)
+            return out if inline else tuple(out) + (None,)
         return out[:6]
 
-    def _encode_key_eager(self, image4, need_sk, need_ek, overlap=False, inline_skips=False):
+    def _encode_key_eager(self, image4, need_sk, need_ek, inline_skips=False):
         W = self._w
         x = ops.conv2d(image4, W['key_encoder.conv1'], relu_out=True)       # the stem reads the fp32 image in every mode
         x = ops.maxpool3x3s2(x, out_dtype=ops.act_dtype())                # fp16 loop: activations become halfs here
         f4 = self._stage(x, 'key_encoder.res2', 3, self._bottleneck)
-        skip4 = skip8 = None
-        main = torch.cuda.current_stream()
-        if overlap:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=image4.device)
-            self._side.wait_stream(main)                       # fork: f4 is ready
-            with torch.cuda.stream(self._side), ops.ws_scope(f'@side4#{self._scope}#'):
-                skip4 = ops.conv2d(f4, W['decoder.up_8_4.skip_conv'])
         f8 = self._stage(f4, 'key_encoder.layer2', 4, self._bottleneck)
-        if overlap:
-            self._side.wait_stream(main)                       # f8 is ready
-            with torch.cuda.stream(self._side), ops.ws_scope(f'@side8#{self._scope}#'):
-                skip8 = ops.conv2d(f8, W['decoder.up_16_8.skip_conv'])
         f16 = self._stage(f8, 'key_encoder.layer3', 6, self._bottleneck)
         B, h, w, _ = f16.shape
         ld = _pad4(2 * self.key_dim + 1)
@@ -494,16 +426,13 @@ class XMem:
         key, shr, sel = ops.key_post(proj, self.key_dim, need_sk, need_ek)
         if inline_skips:                      # same stream: f8 / f4 only depend on the image (model/modules.py:186,231-232)
             extras = (ops.conv2d(f8, W['decoder.up_16_8.skip_conv']), ops.conv2d(f4, W['decoder.up_8_4.skip_conv']))
-            if self.prefuse_x and ('decoder.fuser.block1.conv1@x') in W and ('decoder.fuser.block1.downsample@x') in W:
+            if ('decoder.fuser.block1.conv1@x') in W and ('decoder.fuser.block1.downsample@x') in W:
                 # FeatureFusionBlock convolves cat([f16, readout, hidden]) (model/modules.py:31-41): W * cat = W_x * f16 + W_g * [readout |
                 # hidden], and the f16 half (1024 of 1600 input channels of block1's two 3x3 convolutions) depends on the frame only -
                 # so it is convolved HERE, in the batched pass on the side stream, and enters the decoder as a residual
                 b1 = 'decoder.fuser.block1'
                 extras += (ops.conv2d(f16, W[b1 + '.conv1@x'], relu_in=True), ops.conv2d(f16, W[b1 + '.downsample@x']))
             return key, shr, sel, f16, f8, f4, extras
-        if overlap:
-            main.wait_stream(self._side)                       # join before the stage (and its graph capture) ends
-            return key, shr, sel, f16, f8, f4, (skip8, skip4)
         return key, shr, sel, f16, f8, f4
 
     def encode_value_nhwc(self, image4, f16, hidden, masks, is_deep_update=True, slot=0):
@@ -607,7 +536,7 @@ class XMem:
             c4 = self._w['decoder.pred'].cin
             half = (self._call_precision or self.precision) == 'fp16'
             gf = self._w.get('decoder.hidden_update.g_fused')
-            if gf is not None and not half and self.fuse_hidden_update:
+            if gf is not None and not half:
                 # the concatenated input of the fused hidden-update convolution [g16 | area(g8) | area(g4), area(logits), zero padding]
                 g4d = self._zero_scratch((K, h, w, gf.cin), cat16.device, torch.float32)
             else:
@@ -658,7 +587,7 @@ class XMem:
             if gf is not None and g4d.shape[3] == gf.cin and g4d.dtype == torch.float32:
                 # one pointwise convolution over [g16 | area(g8) | area(g4), area(logits)] (see _upload)
                 c16, c8, ld = g16.shape[3], g8.shape[3], g4d.shape[3]
-                if self.gather_hidden_input and all(t.is_contiguous() for t in (g16, g8, g4, logits)):
+                if all(t.is_contiguous() for t in (g16, g8, g4, logits)):
                     ops.hidden_update_gather(g16, g8, g4, logits, g4d)        # one launch (round 6; the same bits as the four below)
                 else:
                     ops.copy_channels(g16, g4d, 0)

@@ -271,13 +271,15 @@ def winograd4_weights(w):
     return u.reshape(36, w.shape[0], w.shape[3]).to(torch.float32).contiguous()
 
 
-# F(4x4,3x3) replaces F(2x2,3x3) for outputs of at least this many pixels per image (1/8 resolution of 480p and up): below
-# that the 36 tile-position GEMMs are too small to fill the chip.  XMEM_WINO4=0 turns it off (F(2x2) everywhere).
-WINO4_MIN_PIXELS = int(os.environ.get('XMEM_WINO4_MIN_PIXELS', '4096'))   # applies to F(2x2) entries of the plan table only
-WINO4 = os.environ.get('XMEM_WINO4', '1') != '0'
-# Tools knob (parity attribution, tools/parity_by_plan.py): 'direct' runs every convolution in the direct implicit-GEMM form,
+# The heuristic plan (shapes the table does not list) takes F(4x4,3x3) from this many output pixels (1/8 resolution of 480p and
+# up), F(2x2,3x3) below: there the 36 tile-position GEMMs are too small to fill the chip.
+F4_MIN_PIXELS = 4096
+# Tools knob (parity attribution, tests/parity_by_plan.py): 'direct' runs every convolution in the direct implicit-GEMM form,
 # 'f2' replaces F(4x4) by F(2x2), 'direct_sk2' / 'direct_sk3' = the direct form summed in 2 / 3 slabs; None / '' = the shipped plan table.  Read at call time so that a tool can switch it.
 CONV_FORM = os.environ.get('XMEM_CONV_FORM') or None
+# the CONV_FORM forms that fix the plan outright: the library's deterministic direct-form heuristic; the direct form with every
+# contraction cut into 2 / 3 slabs summed afterwards (the SAME products in another fp32 summation order)
+_DIRECT_FORMS = {'direct': (0, 0), 'direct_sk2': (3, 2), 'direct_sk3': (3, 3)}
 
 
 def winograd_weights(w):
@@ -295,10 +297,13 @@ def winograd_weights(w):
 AUTOTUNE = os.environ.get('XMEM_CONV_AUTOTUNE', '0') == '1'
 _PLAN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans.json')
 _PLAN_FILE_X = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans_fp32x.json')   # measured with the split kernels
+_PLAN_FILE_H = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans_fp16.json')    # measured with the half kernels
 _plans = None
 _plans_x = None
+_plans_h = None
 _tuned_now = {}
 _tuned_now_x = {}
+_tuned_now_h = {}
 
 
 def _read_plan_file(path):
@@ -332,6 +337,13 @@ def _lookup_plan(key, split):
     return _load_plans().get(key) or _tuned_now.get(key)
 
 
+def _half_plans():
+    global _plans_h
+    if _plans_h is None:
+        _plans_h = _read_plan_file(_PLAN_FILE_H)
+    return _plans_h
+
+
 def dump_tuned_plans(path, split=False):
     """Write every plan known to this process (shipped + tuned now) - used to refresh conv_plans.json."""
     if _PRECISION == 'fp32x' or split:
@@ -342,7 +354,7 @@ def dump_tuned_plans(path, split=False):
         return len(allp)
     allp = dict(_load_plans())
     allp.update(_tuned_now)
-    if WINO4 and (os.environ.get('XMEM_RETUNE_ALL') or '__tuned_with_f4__' in allp):
+    if os.environ.get('XMEM_RETUNE_ALL') or '__tuned_with_f4__' in allp:
         allp['__tuned_with_f4__'] = (1, 0)           # EVERY entry was measured against the F(4x4) candidates (full retune only)
     with open(path, 'w') as f:
         json.dump({k: list(v) for k, v in sorted(allp.items())}, f, indent=0)
@@ -367,13 +379,8 @@ def _tune_conv(lib, d, x_device, cw=None, incumbent=None):
     if d.w_winograd and d.ldout % 4 == 0 and (not d.res or d.ldres % 4 == 0):
         cands += [(t + 6, cfg) for t, cfg in tiles.items()]
         cands += [(13, (128, 64, 32)), (14, (64, 64, 32)), (15, (64, 128, 32))]
-        if cw is not None and WINO4 and Ho * Wo >= 256:          # F(4x4,3x3): the same GEMM tiles over 36 positions
-            if cw.wu4 is None:
-                cw.wu4 = winograd4_weights(cw.w)
-            d.w_winograd4 = cw.wu4.data_ptr()
-            if d.arith == 1:
-                cw.ensure_split()
-                d.w_winograd4_split = cw.wu4_sp.data_ptr()
+        if cw is not None and Ho * Wo >= 256:          # F(4x4,3x3): the same GEMM tiles over 36 positions
+            _f4_operand(cw, d)
             cands += [(t + 16, cfg) for t, cfg in tiles.items()]
     for tile, (bm, bn, bk) in cands:
         if bn == 128 and d.Cout <= 64 and tile != 15:
@@ -447,6 +454,17 @@ def _time_plan(lib, d, dev, plan, reps=12):
     return best
 
 
+def _tune_conv_half(lib, d, dev):
+    """The same for the half kernels: tiles 1..3 and 4 = 256x128 (8 waves, half kernels only), split-K 1..8."""
+    best, best_t = (0, 0), None
+    for tile in (1, 2, 3, 4):
+        for sk in (1, 2, 4, 8):
+            t = _time_plan(lib, d, dev, (tile, sk), reps=8)
+            if t is not None and (best_t is None or t < best_t):
+                best, best_t = (tile, sk), t
+    return best
+
+
 def _tune_stream(lib, d, dev, plan):
     base = _time_plan(lib, d, dev, plan)
     best, best_t = plan, base
@@ -496,21 +514,132 @@ def conv_executed_mfma_flops(B, Ho, Wo, cin, cout, kh, kw, stride, pad, plan_til
     return npos * 2.0 * up(tiles, tile[0]) * up(cout, tile[1]) * up(cin, 32)
 
 
-_PLAN_FILE_H = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans_fp16.json')   # measured with the half kernels
-_plans_h = None
-_tuned_now_h = {}
+def _f4_operand(cw, d):
+    """Point `d` at the F(4x4,3x3) operand of `cw` (and at its split form in 'fp32x'), built on first use."""
+    if cw.wu4 is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('conv2d: the F(4x4) operand must be built before graph capture (run the stage eagerly once)')
+        cw.wu4 = winograd4_weights(cw.w)
+    d.w_winograd4 = cw.wu4.data_ptr()
+    if d.arith == 1:
+        cw.ensure_split()
+        d.w_winograd4_split = cw.wu4_sp.data_ptr()
 
 
-def _conv2d_half(lib, x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype):
+def _conv_plan(lib, d, cw, key, plan, dev, pixels, wino_ok):
+    """(tile, split-K) of one conv2d call, with `d` pointed at the F(4x4) operand when the plan reads it.  The plan is, in this order:
+    1. the caller's plan, taken literally (tests, tools, the fp16w mode);
+    2. a CONV_FORM attribution form (fp32 mode);
+    3. the plan table of the mode (the shipped conv_plans*.json, then the plans this process chose before);
+    4. the tuner: AUTOTUNE times the candidates of a shape the table lacks (with RETUNE_MARGIN also those of a tabled shape),
+       TUNE_STREAM tries the streaming-GEMM variants of a Winograd plan;
+    5. the deterministic heuristic: same shape -> same plan -> same summation order on every machine.
+    CONV_FORM 'f2' then runs the GEMM tile of an F(4x4) plan under F(2x2)."""
+    half, split = bool(d.in_half), d.arith == 1
+    fp32 = not half and _PRECISION == 'fp32'
+    explicit = plan is not None or (fp32 and CONV_FORM in _DIRECT_FORMS)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if explicit:
+        plan = tuple(plan) if plan is not None else _DIRECT_FORMS[CONV_FORM]
+    else:
+        tune = AUTOTUNE and cw.cout > 1 and not capturing
+        tuned = _tuned_now_h if half else _tuned_now_x if split else _tuned_now
+        plan = (_half_plans().get(key) or _tuned_now_h.get(key)) if half else _lookup_plan(key, split)
+        if plan is not None and tune and fp32 and RETUNE_MARGIN > 0 and key not in _retuned:
+            _retuned.add(key)                     # tools: the tabled plan against its candidates, replaced only when clearly beaten
+            if 17 <= plan[0] <= 28 and cw.wu is not None:
+                _f4_operand(cw, d)
+            new_plan = _tune_conv(lib, d, dev, cw, incumbent=plan)
+            if new_plan != plan:
+                plan = tuned[key] = new_plan
+        if plan is None:
+            if tune:
+                plan = _tune_conv_half(lib, d, dev) if half else _tune_conv(lib, d, dev, cw)
+            elif not half and cw.wu is not None and wino_ok:
+                # a shape the table does not know (another resolution / object count): the 3x3 stride-1 layers still take Winograd
+                # with the 64x64 GEMM tile instead of the direct form
+                plan = (19, 1) if pixels >= F4_MIN_PIXELS else (9, 1)
+            else:
+                plan = (0, 0)
+            tuned[key] = plan
+        if CONV_FORM == 'f2' and 17 <= plan[0] <= 28:     # F(4x4): classic tiles 17..22, streaming GEMM 23..28
+            plan = (plan[0] - 10 if plan[0] <= 22 else plan[0] + 6, plan[1])
+    d.w_winograd4 = None
+    if not half and 17 <= plan[0] <= 28 and cw.wu is not None:
+        _f4_operand(cw, d)
+    if TUNE_STREAM and not (explicit or half or split) and plan[0] in _STREAM_VARIANTS and key not in _stream_checked and not capturing:
+        _stream_checked.add(key)
+        plan = _tuned_now[key] = _tune_stream(lib, d, dev, plan)
+    return plan
+
+
+def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half):
+    """One convolution of either path: descriptor, the operands of the precision mode, plan (_conv_plan), workspace, launch on the
+    current stream, and the RECORD entry."""
+    lib = load()
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
+    Wo = (W + 2 * cw.pad - cw.kw) // cw.stride + 1
+    if out is None:
+        out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=out_dtype, device=x.device), cw.cout
+    elif out_ld is None:
+        out_ld = out.shape[-1]
+    d = ConvDesc()
+    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
+    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
+    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
+    d.res = res.data_ptr() if res is not None else None
+    d.ldres = res.shape[-1] if res is not None else 0
+    d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
+    d.out = out.data_ptr(); d.ldout = out_ld
+    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
+    wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
+    key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
+    if half:
+        d.in_half, d.out_half, d.w_half = 1, int(out.dtype == torch.float16), cw.half().data_ptr()
+        key = f'h{key}o{d.out_half}'
+    else:
+        d.w_winograd = cw.wu.data_ptr() if cw.wu is not None else None
+        if _PRECISION == 'fp16w' and cw.wu_f16 is not None and plan is None and wino_ok:
+            d.w_winograd_f16 = cw.wu_f16.data_ptr()
+            plan = (16, 1)                       # the library falls back to the fp32 Winograd tile if its own conditions fail
+        if _PRECISION == 'fp32x' and cw.cout > 1:
+            # split-operand arithmetic for every GEMM-shaped path (the Cout = 1 mask head is a GEMV on the fp32 VALU)
+            if cw.sp_shift is None or (cw.wu4 is not None and cw.wu4_sp is None):
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('conv2d: split operands must be built before graph capture (run the stage eagerly once)')
+                if cw.sp_shift is None and cw.wu is not None and cw.wu4 is None:
+                    cw.wu4 = winograd4_weights(cw.w)          # so that ONE power of two covers every form of this layer
+                cw.ensure_split()
+            d.arith = 1
+            d.w_split = cw.w_sp.data_ptr()
+            d.w_winograd_split = cw.wu_sp.data_ptr() if cw.wu_sp is not None else None
+            d.w_winograd4_split = cw.wu4_sp.data_ptr() if cw.wu4_sp is not None else None    # taken only by an F(4x4) plan
+            d.scale = cw.scale_sp.data_ptr()
+    plan = _conv_plan(lib, d, cw, key, plan, x.device, B * Ho * Wo, wino_ok)
+    d.plan_tile, d.plan_splitk = plan
+    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
+    ws = workspace(need, x.device, 'conv') if need else None
+    launch = lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr())
+    check(launch())
+    if RECORD is not None:
+        tile = ({4: 1}.get(plan[0], plan[0]) if plan[0] <= 6 else 0) if half else plan[0]    # the half 256x128 tile counts as 128x128
+        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch,
+                       (x, out, res, cw, ws, dict(relu_in=bool(relu_in), relu_out=bool(relu_out), in_ld=ldin, cin=cin, out_ld=out_ld,
+                                                  res_broadcast=bool(res_broadcast), plan=tuple(plan),
+                                                  executed_mfma_flops=conv_executed_mfma_flops(
+                                                      B, Ho, Wo, cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, tile,
+                                                      bool(d.w_winograd) and wino_ok)))))
+    return out
+
+
+def _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype):
     """The fp16 loop's convolution: x [B,H,W,C] halfs (pixel stride in_ld halfs), half weights, direct implicit GEMM on the fp16
     MFMA, fp32 accumulation + epilogue; output (and residual) halfs, or float32 with out_dtype=torch.float32 (key projection,
     mask head).  Input channels beyond the layer's own (a buffer padded to a multiple of 8) must be zero: the half weights are
     zero there."""
-    global _plans_h
-    B, H, W = x.shape[0], x.shape[1], x.shape[2]
     ldin = in_ld if in_ld is not None else x.shape[3]
-    wh = cw.half()
-    cin_h = wh.shape[3]                                   # the layer's Cin padded to 8
+    cin_h = cw.half().shape[3]                            # the layer's Cin padded to 8
     cin = cin if cin is not None else cin_h
     if cin != cin_h and cin != cw.cin:
         raise RuntimeError(f'conv2d (half): weight expects Cin={cw.cin} (padded {cin_h}), got {cin}')
@@ -530,60 +659,16 @@ def _conv2d_half(lib, x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, pl
             inpix = (x.storage_offset() - base.storage_offset()) % ldin
             if inpix + cin_h > ldin:
                 raise RuntimeError(f'conv2d (half): the slice [{inpix}, +{cin_h}) crosses the pixel stride {ldin}')
-    Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
-    Wo = (W + 2 * cw.pad - cw.kw) // cw.stride + 1
     odt = out_dtype if out_dtype is not None else (out.dtype if out is not None else torch.float16)
-    if out is None:
-        out = torch.empty((B, Ho, Wo, cw.cout), dtype=odt, device=x.device)
-        out_ld = cw.cout
-    elif out_ld is None:
-        out_ld = out.shape[-1]
-    if out.dtype != odt:
+    if out is not None and out.dtype != odt:
         raise RuntimeError('conv2d (half): out buffer dtype does not match out_dtype')
-    if res is not None and res.dtype != out.dtype:
+    if res is not None and res.dtype != odt:
         raise RuntimeError('conv2d (half): the residual must have the output storage type')
-    d = ConvDesc()
-    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin_h, ldin
-    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
-    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.ldres = res.shape[-1] if res is not None else 0
-    d.res_broadcast = int(bool(res_broadcast and res is not None))
-    d.out = out.data_ptr(); d.ldout = out_ld
-    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
-    d.in_half, d.out_half, d.w_half = 1, int(out.dtype == torch.float16), wh.data_ptr()
-    key = f'h{B}x{H}x{W}x{cin_h}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None)}{int(relu_in)}{int(relu_out)}o{d.out_half}'
-    if plan is None:
-        if _plans_h is None:
-            _plans_h = _read_plan_file(_PLAN_FILE_H)
-        plan = _plans_h.get(key) or _tuned_now_h.get(key)
-        if plan is None:
-            plan = (0, 0)
-            if AUTOTUNE and cw.cout > 1 and not torch.cuda.is_current_stream_capturing():
-                best, best_t = (0, 0), None
-                for tile in (1, 2, 3, 4):                 # 4 = 256x128, 8 waves (half kernels only)
-                    for sk in (1, 2, 4, 8):
-                        t = _time_plan(lib, d, x.device, (tile, sk), reps=8)
-                        if t is not None and (best_t is None or t < best_t):
-                            best, best_t = (tile, sk), t
-                plan = best
-            _tuned_now_h[key] = plan
-    d.plan_tile, d.plan_splitk = plan
-    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-    ws = workspace(need, x.device, 'conv') if need else None
-    check(lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr()))
-    if RECORD is not None:
-        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true,
-                       lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr()),
-                       (x, out, res, cw, ws, dict(relu_in=bool(relu_in), relu_out=bool(relu_out), in_ld=ldin, cin=cin_h, out_ld=out_ld,
-                                                  res_broadcast=bool(res_broadcast), plan=tuple(plan),
-                                                  executed_mfma_flops=conv_executed_mfma_flops(B, Ho, Wo, cin_h, cw.cout, cw.kh, cw.kw, cw.stride,
-                                                                                               cw.pad, {4: 1}.get(plan[0], plan[0]) if plan[0] <= 6 else 0, False)))))
-    return out
+    return _conv_run(x, cw, cin_h, ldin, out, out_ld, odt, res, relu_in, relu_out, res_broadcast, plan, half=True)
 
 
 def dump_tuned_plans_half(path):
-    allp = dict(_plans_h or _read_plan_file(_PLAN_FILE_H))
+    allp = dict(_half_plans())
     allp.update(_tuned_now_h)
     with open(path, 'w') as f:
         json.dump({k: list(v) for k, v in sorted(allp.items())}, f, indent=0)
@@ -593,152 +678,16 @@ def dump_tuned_plans_half(path):
 def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
            res_broadcast=False, out_dtype=None):
     """x [B,H,W,C] NHWC (or any buffer whose pixel stride is `in_ld`) -> out [B,Ho,Wo,Cout]."""
-    lib = load()
     _req(x, 'conv2d input', half_ok=True)
     if x.dtype == torch.float16:
-        return _conv2d_half(lib, x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype)
+        return _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype)
     if out_dtype is not None and out_dtype != torch.float32:
         raise RuntimeError('conv2d: a float32 input gives a float32 output (the fp16 loop converts at the max-pool after the stems)')
-    B, H, W = x.shape[0], x.shape[1], x.shape[2]
-    ldin = in_ld if in_ld is not None else x.shape[3]
     cin = cin if cin is not None else cw.cin
     if cin != cw.cin:
         raise RuntimeError(f'conv2d: weight expects Cin={cw.cin}, got {cin}')
-    Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
-    Wo = (W + 2 * cw.pad - cw.kw) // cw.stride + 1
-    guard = None
-    if out is None:
-        if _GUARD and not torch.cuda.is_current_stream_capturing():      # tools: sentinel zones around the output (XMEM_GUARD=1)
-            n, G = B * Ho * Wo * cw.cout, 65536
-            flat = torch.full((n + 2 * G,), 12345.0, dtype=torch.float32, device=x.device)
-            out = flat[G:G + n].view(B, Ho, Wo, cw.cout)
-            guard = (flat, G, n)
-        else:
-            out = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float32, device=x.device)
-        out_ld = cw.cout
-    elif out_ld is None:
-        out_ld = out.shape[-1]
-    d = ConvDesc()
-    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
-    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
-    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.ldres = res.shape[-1] if res is not None else 0
-    d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
-    d.out = out.data_ptr(); d.ldout = out_ld
-    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
-    explicit = plan is not None                  # a caller-given plan is taken literally (tests, the tuner)
-    d.w_winograd = cw.wu.data_ptr() if cw.wu is not None else None
-    d.w_winograd_f16 = None
-    if _PRECISION == 'fp16w' and cw.wu_f16 is not None and plan is None and out_ld % 4 == 0 and (res is None or res.shape[-1] % 4 == 0):
-        d.w_winograd_f16 = cw.wu_f16.data_ptr()
-        plan = (16, 1)                       # the library falls back to the fp32 Winograd tile if its own conditions fail
-    key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
-    d.arith = 0
-    d.w_split = d.w_winograd_split = d.w_winograd4_split = None
-    split = _PRECISION == 'fp32x' and cw.cout > 1
-    if split:
-        # split-operand arithmetic for every GEMM-shaped path (the Cout = 1 mask head is a GEMV on the fp32 VALU)
-        if cw.sp_shift is None or (cw.wu4 is not None and cw.wu4_sp is None):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('conv2d: split operands must be built before graph capture (run the stage eagerly once)')
-            if cw.sp_shift is None and cw.wu is not None and cw.wu4 is None and WINO4:
-                cw.wu4 = winograd4_weights(cw.w)          # so that ONE power of two covers every form of this layer
-            cw.ensure_split()
-        d.arith = 1
-        d.w_split = cw.w_sp.data_ptr()
-        d.w_winograd_split = cw.wu_sp.data_ptr() if cw.wu_sp is not None else None
-        d.w_winograd4_split = cw.wu4_sp.data_ptr() if cw.wu4_sp is not None else None    # taken only by an F(4x4) plan
-        d.scale = cw.scale_sp.data_ptr()
-    if plan is None and CONV_FORM == 'direct' and _PRECISION == 'fp32':
-        plan, explicit = (0, 0), True            # the library's deterministic direct-form heuristic
-    elif plan is None and CONV_FORM in ('direct_sk2', 'direct_sk3') and _PRECISION == 'fp32':
-        # the direct form with every contraction cut into 2 / 3 slabs that are summed afterwards: the SAME products in another fp32
-        # summation order (tests/parity_by_plan.py: how much of a parity margin is the order of additions alone)
-        plan, explicit = (3, int(CONV_FORM[-1])), True
-    if plan is None:
-        plan = _lookup_plan(key, split)
-        if plan is not None and RETUNE_MARGIN > 0 and AUTOTUNE and not split and _PRECISION == 'fp32' and cw.cout > 1 and key not in _retuned \
-                and not torch.cuda.is_current_stream_capturing():
-            _retuned.add(key)                     # tools: the tabled plan against its candidates, replaced only when clearly beaten
-            if 17 <= plan[0] <= 28 and cw.wu4 is None and cw.wu is not None:
-                cw.wu4 = winograd4_weights(cw.w)
-            if cw.wu4 is not None:
-                d.w_winograd4 = cw.wu4.data_ptr()
-            new_plan = _tune_conv(lib, d, x.device, cw, incumbent=tuple(plan))
-            if tuple(new_plan) != tuple(plan):
-                plan = tuple(new_plan)
-                _tuned_now[key] = plan
-    if plan is None:
-        plan = (0, 0)
-        if AUTOTUNE and cw.cout > 1 and not torch.cuda.is_current_stream_capturing():
-            plan = _tune_conv(lib, d, x.device, cw)
-        elif cw.wu is not None and out_ld % 4 == 0 and (res is None or res.shape[-1] % 4 == 0):
-            # a shape the shipped table does not know (another resolution / object count): the 3x3 stride-1 layers still take
-            # Winograd with the 64x64 GEMM tile - F(4x4) from 1/8 resolution of 480p up, F(2x2) below - instead of the direct
-            # form (deterministic: same shape -> same plan on every machine)
-            plan = (19, 1) if (WINO4 and CONV_FORM != 'f2' and B * Ho * Wo >= WINO4_MIN_PIXELS) else (9, 1)
-        (_tuned_now_x if split else _tuned_now)[key] = plan
-    d.w_winograd4 = None
-    if not explicit and 7 <= plan[0] <= 12 and WINO4 and CONV_FORM != 'f2' and cw.wu is not None and Ho * Wo >= WINO4_MIN_PIXELS and _PRECISION == 'fp32' \
-            and '__tuned_with_f4__' not in _load_plans():      # a table tuned against F(4x4) already says which layers take it
-        if cw.wu4 is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('conv2d: the F(4x4) operand must be built before graph capture (run the stage eagerly once)')
-            cw.wu4 = winograd4_weights(cw.w)
-        d.w_winograd4 = cw.wu4.data_ptr()
-        plan = (plan[0] + 10, plan[1])
-    elif (17 <= plan[0] <= 22 or 23 <= plan[0] <= 28) and (not WINO4 or CONV_FORM == 'f2') and not explicit:
-        plan = (plan[0] - 10 if plan[0] <= 22 else plan[0] + 6, plan[1])     # XMEM_WINO4=0: the same GEMM tile under F(2x2)
-    elif 17 <= plan[0] <= 28:                        # F(4x4): classic tiles 17..22, streaming GEMM 23..28
-        if cw.wu4 is None and cw.wu is not None:
-            cw.wu4 = winograd4_weights(cw.w)
-        d.w_winograd4 = cw.wu4.data_ptr() if cw.wu4 is not None else None
-    if split and cw.wu4 is not None and cw.wu4_sp is None:          # the F(4x4) operand was built just above
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('conv2d: split operands must be built before graph capture (run the stage eagerly once)')
-        cw.ensure_split()
-        d.w_winograd4_split = cw.wu4_sp.data_ptr()
-    if TUNE_STREAM and not explicit and plan[0] in _STREAM_VARIANTS and d.arith == 0 and key not in _stream_checked \
-            and not torch.cuda.is_current_stream_capturing():
-        _stream_checked.add(key)
-        plan = _tune_stream(lib, d, x.device, tuple(plan))
-        _tuned_now[key] = plan
-    d.plan_tile, d.plan_splitk = plan
-    if _SPLIT_CHECK and d.arith == 1 and not torch.cuda.is_current_stream_capturing():
-        # tools: the same call in fp32 first, then compare (XMEM_SPLIT_CHECK=1; synchronises)
-        d.arith, sc = 0, d.scale
-        d.scale = cw.scale.data_ptr()
-        need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-        ws = workspace(need, x.device, 'conv') if need else None
-        check(lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr()))
-        want = out.clone()
-        d.arith, d.scale = 1, sc
-    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-    ws = workspace(need + (1 << 20 if guard else 0), x.device, 'conv') if need else None
-    if guard and ws is not None:
-        ws[need:need + (1 << 20)].fill_(0x5a)
-    check(lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr()))
-    if guard:
-        flat, G, n = guard
-        bad_lo, bad_hi = int((flat[:G] != 12345.0).sum()), int((flat[G + n:] != 12345.0).sum())
-        bad_ws = int((ws[need:need + (1 << 20)] != 0x5a).sum()) if ws is not None else 0
-        if bad_lo or bad_hi or bad_ws:
-            print(f'[guard] {key} plan={tuple(plan)} arith={d.arith}: {bad_lo} floats written BEFORE the output, {bad_hi} AFTER it, '
-                  f'{bad_ws} bytes past the workspace', file=sys.stderr)
-    if _SPLIT_CHECK and d.arith == 1 and not torch.cuda.is_current_stream_capturing():
-        err = float((out - want).abs().max()) / max(float(want.abs().max()), 1e-30)
-        print(f'[split check] {key} plan={tuple(plan)} in_ld={ldin} max |fp32x - fp32| / max|fp32| = {err:.2e}' +
-              ('   <-- MISMATCH' if not err < 1e-3 else ''), file=sys.stderr)
-    if RECORD is not None:
-        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true,
-                       lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr()),
-                       (x, out, res, cw, ws, dict(relu_in=bool(relu_in), relu_out=bool(relu_out), in_ld=ldin, cin=cin, out_ld=out_ld,
-                                                  res_broadcast=bool(res_broadcast), plan=tuple(plan),
-                                                  executed_mfma_flops=conv_executed_mfma_flops(
-                                                      B, Ho, Wo, cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, plan[0],
-                                                      bool(d.w_winograd) and out_ld % 4 == 0 and (res is None or res.shape[-1] % 4 == 0))))))
-    return out
+    ldin = in_ld if in_ld is not None else x.shape[3]
+    return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False)
 
 
 _HIPRT = None
@@ -770,11 +719,9 @@ def side_stream(device):
 
 
 def readout_stream(device):
-    """The stream the early readout (the NEXT hinted frame's select + readout) runs on, under the current frame's decoder.
-    XMEM_READOUT_PRIORITY (tools: A/B) = the stream's priority: -1 high (its short chain of kernels is dispatched ahead of the decoder's
-    as CUs free up), 0 normal."""
-    pr = int(os.environ.get('XMEM_READOUT_PRIORITY', '0') or 0)
-    return torch.cuda.Stream(device=device, priority=pr)
+    """The stream the early readout (the NEXT hinted frame's select + readout) runs on, under the current frame's decoder, at normal
+    priority (high priority measured no faster: profiles/HISTORY.md step 26)."""
+    return torch.cuda.Stream(device=device)
 
 
 def trace_marker(tag=0):
@@ -969,11 +916,6 @@ def nchw_to_nhwc(x):
 # memory readout
 # ---------------------------------------------------------------------------------------------
 
-_AFF_STATS = bool(os.environ.get('XMEM_AFFINITY_STATS'))
-_SPLIT_CHECK = bool(os.environ.get('XMEM_SPLIT_CHECK'))
-_GUARD = bool(os.environ.get('XMEM_GUARD'))
-
-
 ROWS16_FLOATS = 72            # one fp16 filter operand row (144 halfs = 288 bytes) counted in floats
 
 
@@ -1027,14 +969,6 @@ def affinity_topk(segments, qk, qe, top_k, want_sim=False, hint=None):
     check(lib.xmem_affinity_topk_hinted(arr, len(segs), ptr(qk), ptr(qe), ck, HW, top_k, hp, ptr(w), ptr(idx), ptr(sim),
                                         ptr(ws), need, stream_ptr()))
     _tap_end('affinity', e0, 4.0 * ck * n_total * HW)
-    if _AFF_STATS and hp is not None:                      # tools: candidate statistics of the fp16-filter path (synchronises)
-        o = [C.c_size_t(), C.c_size_t(), C.c_size_t()]
-        check(lib.xmem_affinity_debug_offsets(n_total, HW, *[C.byref(x) for x in o]))
-        torch.cuda.synchronize()
-        cnt = ws[o[0].value:o[0].value + 4 * HW].view(torch.int32).float()
-        flg = ws[o[1].value:o[1].value + 4 * ((HW + 127) // 128)].view(torch.int32)
-        print(f'[affinity] N={n_total} HW={HW}: candidates/query mean {float(cnt.mean()):.0f} median {float(cnt.median()):.0f} '
-              f'max {int(cnt.max())}; fallback tiles {int((flg != 0).sum())}/{flg.numel()}', file=sys.stderr)
     if RECORD is not None:
         RECORD.append(('affinity', f'{n_total}x{HW}k{top_k}', 4.0 * ck * n_total * HW,
                        lambda: lib.xmem_affinity_topk_hinted(arr, len(segs), ptr(qk), ptr(qe), ck, HW, top_k, hp, ptr(w), ptr(idx),
