@@ -233,6 +233,15 @@ int xmem_resize_bilinear(const float* in, float* out, int C, int Hi, int Wi, int
 /* torch.argmax(prob, dim=0) -> uint8, inference/run_on_video.py:170-172; prob [C][H][W] */
 int xmem_argmax_u8(const float* prob, uint8_t* out, int C, int H, int W, void* stream);
 
+/* One pass of a test-time ensemble (eval.py --size S [--flip] --save_scores + merge_multi_scale.py), at the ORIGINAL resolution H x W:
+ *   v   = bilinear(prob)[c, y, mirror ? W-1-x : x]   (identity when Hi, Wi == H, W; same arithmetic as xmem_resize_bilinear)
+ *   q   = (uint16)(v * 255.f), truncated
+ *   acc = first ? q : acc + q                        acc: uint16 [C][H][W]; at most 257 passes cannot overflow
+ *   out (if non-NULL) = first index of max_c acc[c]   uint8 [H][W], the merged mask of the pass that closes the frame
+ * prob [C][Hi][Wi], C in [1, 255]. */
+int xmem_ensemble_accumulate(const float* prob, int C, int Hi, int Wi, int mirror,
+                             uint16_t* acc, int H, int W, int first, uint8_t* out, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

@@ -783,6 +783,59 @@ extern "C" int xmem_argmax_u8(const float* prob, uint8_t* out, int C, int H, int
     return xmem_check_launch();
 }
 
+// One pass of the test-time ensemble (eval.py:208-225 + merge_multi_scale.py:44-57) at the original resolution: bilinear resize,
+// horizontal flip of the resized scores, (uint8)(p * 255) truncation, exact integer sum over passes; the pass that closes the frame
+// also takes the first-index argmax of the sum.  One thread per output pixel, looping over channels.
+// The interpolated value must be bit-identical to resize_bilinear_kernel's.  Written in the same plain form, the compiler contracted
+// it differently here (a few values per frame one ulp apart, which the truncation turns into a different uint8), so the contraction
+// that resize_bilinear_kernel compiles to (gfx950 ISA: two v_mul + v_fmac for the rows, v_mul + v_fmac across them) is spelled out:
+//   fma(hy, fma(lx, p01, hx * p00), ly * fma(lx, p11, hx * p10))
+// tests/test_gpu_ensemble.py::test_ensemble_accumulate_bit_exact compares the two kernels on every build.
+template <bool RESIZE>
+__global__ void ensemble_accumulate_kernel(const float* __restrict__ in, int C, int Hi, int Wi, int mirror,
+                                           uint16_t* __restrict__ acc, int Ho, int Wo, int first, uint8_t* __restrict__ out) {
+    const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+    const size_t P = (size_t)Ho * Wo;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (size_t)gridDim.x * blockDim.x) {
+        const int xo = (int)(e % Wo); const int y = (int)(e / Wo);
+        const int x = mirror ? Wo - 1 - xo : xo;             // torch.flip(prob, dims=[-1]) AFTER the resize
+        int y0 = y, y1 = y, x0 = x, x1 = x; float ly = 0.f, lx = 0.f;
+        if (RESIZE) {
+            bilinear_src(y, sy, Hi, y0, y1, ly);
+            bilinear_src(x, sx, Wi, x0, x1, lx);
+        }
+        unsigned best = 0; int bi = 0;
+        for (int c = 0; c < C; ++c) {
+            const float* p = in + (size_t)c * Hi * Wi;
+            float v;
+            if (RESIZE) {
+                const float hy = 1.f - ly, hx = 1.f - lx;
+                const float top = __builtin_fmaf(lx, p[(size_t)y0 * Wi + x1], hx * p[(size_t)y0 * Wi + x0]);
+                const float bot = __builtin_fmaf(lx, p[(size_t)y1 * Wi + x1], hx * p[(size_t)y1 * Wi + x0]);
+                v = __builtin_fmaf(hy, top, ly * bot);
+            } else {
+                v = p[(size_t)y * Wi + x];
+            }
+            const float t = fminf(fmaxf(v * 255.f, 0.f), 255.f);      // (prob*255).astype(np.uint8): in range, truncation
+            const unsigned q = (unsigned)t + (first ? 0u : (unsigned)acc[(size_t)c * P + e]);
+            acc[(size_t)c * P + e] = (uint16_t)q;
+            if (c == 0 || q > best) { best = q; bi = c; }       // first maximal index, as np.argmax
+        }
+        if (out) out[e] = (uint8_t)bi;
+    }
+}
+
+extern "C" int xmem_ensemble_accumulate(const float* prob, int C, int Hi, int Wi, int mirror, uint16_t* acc, int H, int W,
+                                        int first, uint8_t* out, void* stream) {
+    if (!prob || !acc || C <= 0 || C > 255 || Hi <= 0 || Wi <= 0 || H <= 0 || W <= 0) return XMEM_ERR_BAD_ARG;
+    const dim3 grid(grid_for((size_t)H * W)), block(256);
+    if (Hi == H && Wi == W)
+        hipLaunchKernelGGL(ensemble_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, prob, C, Hi, Wi, mirror, acc, H, W, first, out);
+    else
+        hipLaunchKernelGGL(ensemble_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, prob, C, Hi, Wi, mirror, acc, H, W, first, out);
+    return xmem_check_launch();
+}
+
 // ---------------------------------------------------------------------------------------------
 // layout transposes through a padded LDS tile (32 pixels x 32 channels)
 // ---------------------------------------------------------------------------------------------

@@ -894,6 +894,24 @@ def argmax_u8(prob):
     return out
 
 
+def ensemble_accumulate(prob, shape, mirror, acc, first, out=None):
+    """One pass of the test-time ensemble into `acc` (uint16 [C,H,W], `shape` = (H, W), the original resolution): bilinear resize of
+    prob [C,Hi,Wi] (when its size differs), horizontal flip if `mirror`, (uint8)(p * 255), acc = q if `first` else acc + q.  With
+    `out` (uint8 [H,W]) the first-index argmax of the updated sum is written there too.  Returns `out` (or `acc` without it)."""
+    Cc, Hi, Wi = prob.shape
+    H, W = int(shape[0]), int(shape[1])
+    _req(prob, 'prob')
+    if not prob.is_contiguous():
+        prob = prob.contiguous()
+    if not acc.is_cuda or acc.dtype != torch.uint16 or tuple(acc.shape) != (Cc, H, W) or not acc.is_contiguous():
+        raise RuntimeError(f'acc: expected a contiguous uint16 CUDA (HIP) tensor of shape {(Cc, H, W)}')
+    if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or not out.is_contiguous()):
+        raise RuntimeError(f'out: expected a contiguous uint8 CUDA (HIP) tensor of shape {(H, W)}')
+    check(load().xmem_ensemble_accumulate(ptr(prob), Cc, Hi, Wi, int(bool(mirror)), ptr(acc), H, W, int(bool(first)), ptr(out),
+                                          stream_ptr()))
+    return out if out is not None else acc
+
+
 def nhwc_to_nchw(x, c=None, off=0):
     """x [B,H,W,ld] (channels off..off+c) -> contiguous [B,c,H,W]."""
     B, H, W, ld = x.shape

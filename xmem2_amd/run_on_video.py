@@ -415,6 +415,260 @@ def run_on_video(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks:
                                print_progress=print_progress, **kwargs)
 
 
+MAX_ENSEMBLE_PASSES = 16
+
+
+def parse_ensemble(spec, size):
+    """overwrite_config['ensemble'] -> tuple of (size, flip) passes.  `size` means what config['size'] means (-1: native);
+    absent (None): the flip ensemble at `size`.  Duplicates are kept (each is a pass of its own)."""
+    if spec is None:
+        spec = [[size, False], [size, True]]
+    if not isinstance(spec, (list, tuple)) or not spec:
+        raise ValueError('ensemble: expected a non-empty list of [size, flip] passes')
+    if len(spec) > MAX_ENSEMBLE_PASSES:
+        raise ValueError(f'ensemble: {len(spec)} passes, at most {MAX_ENSEMBLE_PASSES}')
+    passes = []
+    for item in spec:
+        if not isinstance(item, (list, tuple)) or len(item) != 2:
+            raise ValueError(f'ensemble: pass {item!r} is not a [size, flip] pair')
+        s, f = item
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or not (s == -1 or s > 0):
+            raise ValueError(f'ensemble: size {s!r} must be an integer > 0, or -1 for the native size')
+        if not isinstance(f, (bool, np.bool_)) and f not in (0, 1):
+            raise ValueError(f'ensemble: flip {f!r} must be a boolean')
+        passes.append((int(s), bool(f)))
+    return tuple(passes)
+
+
+def _mirror(a):
+    """Horizontal flip of an H x W [x 3] host array (torch.flip(x, dims=[-1]) of eval.py:217-218 in the array's own layout)."""
+    return np.ascontiguousarray(a[:, ::-1])
+
+
+@dataclass
+class EnsembleSample:
+    """One decoded frame and its per-pass inputs: `rgb_u8[p]` is pass p's working-size (mirrored if asked) uint8 frame, `mask` the
+    annotation's raw index array at the ORIGINAL resolution (each pass mirrors it before its own convert / resize)."""
+    rgb_u8: list
+    raw_image_pil: object
+    frame: str
+    save: bool
+    shape: tuple
+    mask: Optional[np.ndarray] = None
+
+
+class EnsembleFramePrefetcher(FramePrefetcher):
+    """FramePrefetcher for an ensemble: each frame is decoded ONCE on a worker thread, resized once per distinct working size
+    (PIL bilinear, VideoReader.frame_u8) and mirrored there for the flipped passes; passes with the same (size, flip) share one
+    array.  The arrays are pinned by `get`, on the calling thread, not on the workers: the P cores capture their graphs over the first
+    frames while the workers decode ahead, and with the pinning on the workers captures failed (hipErrorStreamCaptureInvalidated, in a
+    conv launch of a later core's first key-encoder capture) - the pinned-memory allocator queries events, which a capture in progress
+    on another thread does not allow."""
+
+    def __init__(self, readers, passes, depth=16, workers=8):
+        super().__init__(readers[passes[0][0]], depth=depth, workers=workers)
+        self.readers, self.passes = readers, passes
+
+    def _load(self, idx):
+        base = self.reader[idx]                                   # decode + the first pass's size (+ the raw annotation)
+        by_size = {self.passes[0][0]: base.rgb_u8}
+        variants = {}
+        for s, f in self.passes:
+            if (s, f) not in variants:
+                if s not in by_size:
+                    by_size[s] = self.readers[s].frame_u8(base.raw_image_pil)
+                a = by_size[s]
+                variants[(s, f)] = torch.from_numpy(_mirror(a.numpy())) if f else a
+        return EnsembleSample(rgb_u8=[variants[p] for p in self.passes], raw_image_pil=base.raw_image_pil, frame=base.frame,
+                              save=base.save, shape=base.shape, mask=base.mask)
+
+    def get(self, n):
+        out = super().get(n)
+        for smp in out:
+            pinned = {}
+            for t in smp.rgb_u8:
+                if id(t) not in pinned:
+                    pinned[id(t)] = t.pin_memory()
+            smp.rgb_u8 = [pinned[id(t)] for t in smp.rgb_u8]
+        return out
+
+
+def _pass_mask(mapper, reader, raw, flip, need_resize):
+    """eval.py:191-200 for one pass: mirror the raw index mask, then convert_mask, then the nearest resize (the nearest resize is
+    not mirror-symmetric, so the order matters)."""
+    msk, labels = mapper.convert_mask(_mirror(raw) if flip else raw, exhaustive=True)
+    if need_resize:
+        msk = reader.resize_mask(msk)
+    return msk, labels
+
+
+def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out_path, original_memory_mechanism=False,
+                       compute_iou=False, manually_curated_masks=False, print_progress=True,
+                       augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
+                       object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200):
+    import pandas as pd
+    from PIL import Image
+    config = VIDEO_INFERENCE_CONFIG.copy()
+    overwrite_config = {} if overwrite_config is None else dict(overwrite_config)
+    overwrite_config['masks_out_path'] = masks_out_path
+    config.update(overwrite_config)
+    passes = parse_ensemble(config.get('ensemble'), config['size'])
+    if augment_images_with_masks:
+        raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
+                                  'defined for one working size and orientation); run the passes without it')
+    if not torch.cuda.is_available():
+        raise RuntimeError('xmem2_amd.run_on_video needs an MI355X (HIP) device - there is no CPU path')
+    device = torch.device('cuda', torch.cuda.current_device())
+    torch.autograd.set_grad_enabled(False)
+    frames_with_masks = set(frames_with_masks)
+    P = len(passes)
+
+    # one network (weights uploaded and transformed once), one InferenceCore + MaskMapper per pass
+    model_path = config['model']
+    network = XMem(config, model_path, pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
+    if model_path is None:
+        warn('No model weights were loaded, as config["model"] was not specified.')
+    readers = {}
+    for s, _ in passes:
+        if s not in readers:
+            readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True)
+    vid_reader = readers[passes[0][0]]
+    vid_length = len(vid_reader)
+    config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196, once for all passes
+        config['enable_long_term'] and
+        (vid_length / (config['max_mid_term_frames'] - config['min_mid_term_frames']) * config['num_prototypes'])
+        >= config['max_long_term_elements'])
+    mappers = [MaskMapper() for _ in passes]
+    cores = [InferenceCore(network, config=config) for _ in passes]
+
+    def pass_masks(raw):
+        """per-pass (one-hot mask, labels); every mapper sees the same annotation, so their remappings must agree"""
+        out = [_pass_mask(mappers[p], readers[s], raw, f, s >= 0) for p, (s, f) in enumerate(passes)]
+        for m in mappers[1:]:
+            assert m.remappings == mappers[0].remappings and m.labels == mappers[0].labels, 'ensemble: pass label maps diverged'
+        return out
+
+    to_permanent = [0] if original_memory_mechanism else sorted(frames_with_masks)
+    loaded, preload_time = False, 0.0
+    for j in to_permanent:                                           # _preload_permanent_memory, :201-244, per pass
+        sample = vid_reader[j]
+        if sample.mask is None:
+            raise FileNotFoundError(f"Couldn't find mask {j}! Check that the filename is the same as for frame {j}.")
+        per_pass = pass_masks(sample.mask)
+        if min(per_pass[0][0].shape) == 0:
+            warn(f'Skipping adding frame {j} to permanent memory, as the mask is empty')
+            continue
+        by_size = {passes[0][0]: sample.rgb_u8}
+        a = perf_counter()
+        for p, (s, f) in enumerate(passes):
+            if s not in by_size:
+                by_size[s] = readers[s].frame_u8(sample.raw_image_pil)
+            rgb = torch.from_numpy(_mirror(by_size[s].numpy())) if f else by_size[s]
+            cores[p].set_all_labels(list(mappers[p].remappings.values()))
+            cores[p].put_to_permanent_memory(rgb.to(device), per_pass[p][0].to(device))
+        torch.cuda.synchronize()
+        preload_time += perf_counter() - a
+        loaded = True
+    if not loaded:
+        raise ValueError('No valid masks provided!')
+
+    stats, total_time = [], 0.0
+    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
+    fetcher = AsyncMaskFetcher()
+    mapper = mappers[0]
+
+    def finish(tag, out_mask):                                       # as in run_on_video, on the merged mask
+        sample, had_mask = tag
+        stat = {'frame': sample.frame, 'mask_provided': had_mask}
+        if compute_iou:
+            gt = sample.mask
+            stat['iou'] = float(compute_array_iou(out_mask, gt)) if (gt is not None and not had_mask) else -1
+        stats.append(stat)
+        if saver is not None:
+            ids = mapper.remap_index_mask(out_mask)
+
+            def job(ids=ids, sample=sample):
+                out_img = vid_reader.map_the_colors_back(Image.fromarray(ids))
+                yield out_img, 'masks', sample.frame[:-4] + '.png'
+                if save_overlay:
+                    yield _overlay(sample.raw_image_pil, out_img), 'overlay', sample.frame[:-4] + '.jpg'
+            saver.submit(job)
+
+    key_batch = max(1, int(config.get('key_batch', 4)))
+    decoder = EnsembleFramePrefetcher(readers, passes, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
+    pending, next_idx = collections.deque(), 0
+    bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
+
+    def refill():
+        nonlocal next_idx
+        remaining = vid_length - next_idx
+        if remaining <= 0:
+            return
+        n = key_batch if remaining >= key_batch else 1
+        samples = decoder.get(n)
+        devs = [cores[p].prefetch_keys([smp.rgb_u8[p] for smp in samples]) for p in range(P)]   # each core hints its own variants
+        pending.extend((smp, [devs[p][i] for p in range(P)]) for i, smp in enumerate(samples))
+        next_idx += n
+
+    loop_t0 = perf_counter()
+    try:
+        for ti in range(vid_length):
+            if len(pending) < key_batch:
+                refill()
+            sample, rgbs = pending.popleft()
+            given = ti in frames_with_masks and sample.mask is not None
+            per_pass = pass_masks(sample.mask) if given else None
+            skip_add = (ti == 0) if original_memory_mechanism else given
+            a = perf_counter()
+            H, W = sample.shape
+            for p, (s, f) in enumerate(passes):
+                msk = labels = None
+                if given:
+                    msk, labels = per_pass[p][0].to(device), per_pass[p][1]
+                    cores[p].set_all_labels(list(mappers[p].remappings.values()))
+                prob = cores[p].step(rgbs[p], msk, labels, end=(ti == vid_length - 1),
+                                     manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
+                shp = (prob.shape[0], H, W)                          # one pair per object count (a late object adds a class)
+                if shp not in bufs:
+                    bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
+                acc, merged = bufs[shp]
+                ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
+            done = fetcher.submit((sample, given), merged)
+            total_time += perf_counter() - a
+            for tag, out_mask in done:
+                finish(tag, out_mask)
+        a = perf_counter()
+        done = fetcher.drain()
+        total_time += perf_counter() - a
+        for tag, out_mask in done:
+            finish(tag, out_mask)
+    finally:
+        decoder.close()
+        loop_wall = perf_counter() - loop_t0
+        if saver is not None:
+            saver.close()
+        total_wall = perf_counter() - loop_t0
+    if print_fps:
+        print(f'ENSEMBLE PASSES: {P} (' + ', '.join(str(s) + (' flip' if f else '') for s, f in passes) + ')')
+        print(f'TOTAL PRELOADING TIME: {preload_time:.4f}s')
+        print(f'TOTAL PROCESSING TIME: {total_time:.4f}s')
+        print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
+        print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
+              f'{vid_length / total_wall:.4f}')
+    return pd.DataFrame(stats)
+
+
+def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
+                          compute_iou=False, print_progress=True, **kwargs):
+    """The test-time ensemble of eval.py (--size S [--flip] --save_scores, one run per pass) + merge_multi_scale.py, in one process on
+    one network: `overwrite_config['ensemble']` lists the [size, flip] passes (default: [[size, False], [size, True]]).  Every pass
+    runs its own InferenceCore; per frame, each pass's probabilities are resized to the original size, un-flipped, quantised to
+    uint8 and summed on the device, and the argmax of the sum is the written mask.  Same signature and return as run_on_video."""
+    return _ensemble_on_video(imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
+                              frames_with_masks=frames_with_masks, compute_iou=compute_iou,
+                              print_progress=print_progress, **kwargs)
+
+
 def _pil_to_tensor01(pic):
     """What torchvision's ToTensor yields for the PNG modes the harness writes/reads (run_on_video.py:334,362):
     uint8 planes scaled by 1/255, C x H x W; palette images contribute their raw INDEX plane (so object id 1 becomes
