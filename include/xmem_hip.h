@@ -242,6 +242,15 @@ int xmem_argmax_u8(const float* prob, uint8_t* out, int C, int H, int W, void* s
 int xmem_ensemble_accumulate(const float* prob, int C, int Hi, int Wi, int mirror,
                              uint16_t* acc, int H, int W, int first, uint8_t* out, void* stream);
 
+/* DAVIS J&F counts (util/metrics.py batched_jaccard / batched_f_measure, the width=None _seg2bmap and cv2.dilate with disk(radius)):
+ *   gt, pred  uint8 label maps [B][H][W]; lut (or NULL) a 256-entry uint8 map applied to pred (the MaskMapper dense -> original ids)
+ *   counts    int32 [B][256][7], zeroed on `stream` first; for every frame b and label k in 1..254:
+ *             gt_area, pred_area, inter, n_gt, n_pred, gt_match, pred_match  (boundary pixels; *_match: under the other map's
+ *             boundary dilated by the disk dy^2 + dx^2 <= radius^2).  Labels 0 and 255 are never scored; absent labels count 0.
+ * radius in [0, 63], H and W in [1, 16384] (else XMEM_ERR_UNSUPPORTED); the counts are exact and bit-reproducible. */
+int xmem_jf_counts(const uint8_t* gt, const uint8_t* pred, const uint8_t* lut, int B, int H, int W, int radius,
+                   int32_t* counts, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

@@ -12,7 +12,8 @@ length (``inference/run_experiments.py:418``); videos never exchange state, so t
 * videos are sorted longest first and dealt to the rank with the least work so far (LPT; ``shard_videos``), every
   rank then runs ``run_on_video`` on its videos in that order on its own GPU (``LOCAL_RANK``), writes
   ``<out>/<name>/masks/*.png`` and a per-rank ``<out>/_rank<r>.json``; the parent merges them into
-  ``<out>/summary.json`` (per-video frames, seconds, frames/s, mean IoU if asked) - host-side merge, no RCCL.
+  ``<out>/summary.json`` (per-video frames, seconds, frames/s, mean IoU and J / F / J&F if asked, with their dataset means) -
+  host-side merge, no RCCL.
 * ``--gpus N`` fails if fewer than N devices are visible: it never silently runs on fewer.
 
 ``bench.py`` uses ``spawn_ranks`` of this module for its own ``--gpus N`` replica streams.
@@ -278,19 +279,34 @@ def worker(args):
     results = []
     for v in mine:
         t0 = time.perf_counter()
+        extra = dict(compute_jf=True) if args.compute_jf else {}
         stats = runner(v['frames'], v['masks'], os.path.join(args.out, v['name']), frames_with_masks=fm,
-                       compute_iou=args.compute_iou, print_progress=False, overwrite_config=dict(over))
+                       compute_iou=args.compute_iou, print_progress=False, overwrite_config=dict(over), **extra)
         dt = time.perf_counter() - t0
         row = dict(name=v['name'], frames=v['length'], seconds=dt, fps=v['length'] / dt if dt > 0 else None, rank=rank)
         if args.compute_iou and stats is not None and 'iou' in getattr(stats, 'columns', ()):
             ious = [float(x) for x in stats['iou'] if x >= 0]
             row['mean_iou'] = sum(ious) / len(ious) if ious else None
+        if args.compute_jf:
+            row.update(jf_means(stats))
         results.append(row)
     tmp = mine_path + '.tmp'
     with open(tmp, 'w') as f:
         json.dump(dict(rank=rank, world=world, nonce=run_nonce(), videos=results), f)
     os.replace(tmp, mine_path)
     return 0
+
+
+def jf_means(stats):
+    """mean_J / mean_F / mean_JF of a runner's DataFrame (frames without a ground truth carry NaN and are left out)."""
+    cols = getattr(stats, 'columns', ())
+    if 'J' not in cols or 'F' not in cols:
+        return dict(mean_J=None, mean_F=None, mean_JF=None)
+    J = [float(x) for x in stats['J'] if x == x]
+    F = [float(x) for x in stats['F'] if x == x]
+    mj = sum(J) / len(J) if J else None
+    mf = sum(F) / len(F) if F else None
+    return dict(mean_J=mj, mean_F=mf, mean_JF=(mj + mf) / 2 if mj is not None and mf is not None else None)
 
 
 def run_nonce():
@@ -331,6 +347,10 @@ def merge(out_dir, world, wall, nonce=None):
                    aggregate_fps=frames / wall if wall > 0 else None, ranks_missing=missing,
                    per_rank={str(k): v for k, v in sorted(per_rank.items())},
                    slowest_rank_seconds=max(busy) if busy else None, fastest_rank_seconds=min(busy) if busy else None)
+    for key in ('mean_J', 'mean_F', 'mean_JF'):                     # --compute-jf: dataset means over the videos that have them
+        vals = [v[key] for v in videos if v.get(key) is not None]
+        if any(key in v for v in videos):
+            summary[key] = sum(vals) / len(vals) if vals else None
     with open(os.path.join(out_dir, 'summary.json'), 'w') as f:
         json.dump(summary, f, indent=1)
     return summary
@@ -345,6 +365,8 @@ def main(argv=None):
     ap.add_argument('--frames-with-masks', default='0', help='comma-separated frame indices whose annotation is given')
     ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG (overwrite_config)')
     ap.add_argument('--compute-iou', action='store_true')
+    ap.add_argument('--compute-jf', action='store_true', help='score every frame that has a ground truth: DAVIS J, F and J&F per video '
+                                                               'and their dataset means in summary.json')
     ap.add_argument('--runner', default='xmem2_amd.run_on_video:run_on_video', help='module:function with run_on_video\'s signature')
     ap.add_argument('--device', default='cuda', choices=['cuda', 'cpu'], help='cpu only for launcher tests with a stub runner')
     ap.add_argument('--merge-timeout', type=float, default=86400.0, help='under torchrun: how long rank 0 waits for the other ranks\' results')

@@ -912,6 +912,33 @@ def ensemble_accumulate(prob, shape, mirror, acc, first, out=None):
     return out if out is not None else acc
 
 
+JF_SLOTS = ('gt_area', 'pred_area', 'inter', 'n_gt', 'n_pred', 'gt_match', 'pred_match')
+JF_MAX_RADIUS = 63
+
+
+def jf_counts(gt, pred, radius, lut=None, out=None):
+    """DAVIS J&F counts of uint8 label maps `gt`, `pred` ([H,W] or [B,H,W], same shape) into int32 `out` [B,256,7] (allocated if None):
+    per frame and label k in 1..254 the JF_SLOTS counts, boundaries dilated by the disk of `radius` (0..63).  `lut` (uint8 [256]) maps
+    pred's labels first.  `out` is zeroed and filled on the current stream; returns it."""
+    for t, name in ((gt, 'gt'), (pred, 'pred')):
+        if not t.is_cuda or t.dtype != torch.uint8 or t.dim() not in (2, 3):
+            raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise RuntimeError(f'gt and pred differ in shape: {tuple(gt.shape)} != {tuple(pred.shape)}')
+    gt, pred = gt.contiguous(), pred.contiguous()
+    B, H, W = (1,) + tuple(gt.shape) if gt.dim() == 2 else tuple(gt.shape)
+    if lut is not None:
+        if not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (256,):
+            raise RuntimeError('lut: expected a uint8 CUDA (HIP) tensor of shape (256,)')
+        lut = lut.contiguous()
+    if out is None:
+        out = torch.empty((B, 256, len(JF_SLOTS)), dtype=torch.int32, device=gt.device)
+    elif (not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != (B, 256, len(JF_SLOTS)) or not out.is_contiguous()):
+        raise RuntimeError(f'out: expected a contiguous int32 CUDA (HIP) tensor of shape {(B, 256, len(JF_SLOTS))}')
+    check(load().xmem_jf_counts(ptr(gt), ptr(pred), ptr(lut), B, H, W, int(radius), ptr(out), stream_ptr()))
+    return out
+
+
 def nhwc_to_nchw(x, c=None, off=0):
     """x [B,H,W,ld] (channels off..off+c) -> contiguous [B,c,H,W]."""
     B, H, W, ld = x.shape

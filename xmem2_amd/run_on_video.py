@@ -28,6 +28,7 @@ from . import ops
 from .configuration import VIDEO_INFERENCE_CONFIG
 from .inference_core import InferenceCore
 from .mask_mapper import MaskMapper
+from .metrics import InLoopScorer
 from .network import XMem
 from .tensor_util import compute_array_iou
 
@@ -273,7 +274,8 @@ def _load_main_objects(imgs_in_path, masks_in_path, config, device):
 def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out_path, original_memory_mechanism=False,
                         compute_iou=False, manually_curated_masks=False, print_progress=True,
                         augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
-                        object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200):
+                        object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
+                        compute_jf=False):
     import pandas as pd
     from PIL import Image
     if not torch.cuda.is_available():
@@ -331,6 +333,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     stats, total_time = [], 0.0
     saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
     fetcher = AsyncMaskFetcher()
+    scorer = InLoopScorer(vid_length, device) if compute_jf else None
 
     def finish(tag, out_mask):                                       # host side of a frame whose mask has arrived
         sample, had_mask = tag
@@ -381,7 +384,10 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
             a = perf_counter()
             prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
                                   manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
-            done = fetcher.submit((sample, msk is not None), _post_process_gpu(sample, prob))
+            out_dev = _post_process_gpu(sample, prob)
+            if scorer is not None and sample.mask is not None:
+                scorer.add(ti, sample.mask, out_dev, mapper)
+            done = fetcher.submit((sample, msk is not None), out_dev)
             total_time += perf_counter() - a
             for tag, out_mask in done:
                 finish(tag, out_mask)
@@ -403,13 +409,22 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return pd.DataFrame(stats)
+    return _with_jf(pd.DataFrame(stats), scorer)
+
+
+def _with_jf(df, scorer):
+    """compute_jf=True: the J and F columns (per-frame means over the sequence's ground-truth objects, NaN without a ground truth)."""
+    if scorer is not None:
+        df['J'], df['F'] = scorer.scores()
+    return df
 
 
 def run_on_video(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
                  compute_iou=False, print_progress=True, **kwargs):
     """Same signature / return as inference/run_on_video.py:247-282: per-frame stats DataFrame
-    (frame, mask_provided[, iou]); predicted masks are written under ``masks_out_path/masks``."""
+    (frame, mask_provided[, iou]); predicted masks are written under ``masks_out_path/masks``.
+    ``compute_jf=True`` adds DAVIS J and F columns, scored on the device against every frame's ground truth
+    (xmem2_amd.metrics; frames without one get NaN)."""
     return _inference_on_video(imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
                                frames_with_masks=frames_with_masks, compute_iou=compute_iou,
                                print_progress=print_progress, **kwargs)
@@ -505,7 +520,8 @@ def _pass_mask(mapper, reader, raw, flip, need_resize):
 def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out_path, original_memory_mechanism=False,
                        compute_iou=False, manually_curated_masks=False, print_progress=True,
                        augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
-                       object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200):
+                       object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
+                       compute_jf=False):
     import pandas as pd
     from PIL import Image
     config = VIDEO_INFERENCE_CONFIG.copy()
@@ -576,6 +592,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
     fetcher = AsyncMaskFetcher()
     mapper = mappers[0]
+    scorer = InLoopScorer(vid_length, device) if compute_jf else None
 
     def finish(tag, out_mask):                                       # as in run_on_video, on the merged mask
         sample, had_mask = tag
@@ -633,6 +650,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                     bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
                 acc, merged = bufs[shp]
                 ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
+            if scorer is not None and sample.mask is not None:
+                scorer.add(ti, sample.mask, merged, mapper)
             done = fetcher.submit((sample, given), merged)
             total_time += perf_counter() - a
             for tag, out_mask in done:
@@ -655,7 +674,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return pd.DataFrame(stats)
+    return _with_jf(pd.DataFrame(stats), scorer)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
