@@ -115,6 +115,18 @@ typedef struct {
 size_t xmem_conv2d_workspace_bytes(const xmem_conv_desc* d);
 int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Dilated convolution (atrous), the S2M network's DeepLabV3+ (inference/interact/s2m/s2m_resnet.py:17-20 conv3x3 with dilation, the
+ * layer4 blocks 1-2 of _make_layer's replace_stride_with_dilation, :138-150; ASPPConv, s2m/_deeplab.py:113-119, rates 6 / 12 / 18).
+ * Same descriptor and epilogue as xmem_conv2d_nhwc (scale / shift, res, relu_in / relu_out, ldin / ldout channel slices); tap (kh, kw)
+ * reads input pixel (oh*stride - pad + kh*dilation, ow*stride - pad + kw*dilation), Ho = (H + 2 pad - dilation (KH - 1) - 1) / stride + 1.
+ * The direct implicit GEMM only: plan_tile 0 (heuristic) or 1..6, plan_splitk as there; no Winograd, no half / split-operand modes,
+ * no res_broadcast, Cout >= 2 (else XMEM_ERR_UNSUPPORTED).  Each workgroup skips the taps that fall outside the input for its whole
+ * output tile (flags & XMEM_DILATED_NO_TAP_SKIP turns that off, for measurement: same bits either way).  With dilation 1 the result
+ * is bit-identical to xmem_conv2d_nhwc under the same direct plan. */
+#define XMEM_DILATED_NO_TAP_SKIP 1
+size_t xmem_conv2d_dilated_workspace_bytes(const xmem_conv_desc* d, int dilation);
+int xmem_conv2d_nhwc_dilated(const xmem_conv_desc* d, int dilation, int flags, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Deterministic permanent-memory augmentations on the device: every augmented uint8 frame and float mask
  * of one annotated frame in ONE launch.  Replaces the per-annotation loop of inference/run_on_video.py:231-242 over
@@ -250,6 +262,38 @@ int xmem_ensemble_accumulate(const float* prob, int C, int Hi, int Wi, int mirro
  * radius in [0, 63], H and W in [1, 16384] (else XMEM_ERR_UNSUPPORTED); the counts are exact and bit-reproducible. */
 int xmem_jf_counts(const uint8_t* gt, const uint8_t* pred, const uint8_t* lut, int B, int H, int W, int radius,
                    int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Scribble-to-mask (S2M) around its convolutions (inference/interact/s2m_controller.py, s2m/_deeplab.py, s2m/utils.py).
+ * ------------------------------------------------------------------------------------------ */
+/* Input of every object at once, s2m_controller.py:21-35 + pad_divide_by(., 16) (util/tensor_util.py:47-62): image [3][H][W]
+ * (normalised), prev_mask [H][W] (float object index), scr [H][W] uint8 -> out [K][Hp][Wp][8], per object k = 1..K the channels
+ * (r, g, b, prev == k, scr == k, scr != k && scr != ignore_class, 0, 0), all zero in the centred padding (top lh, left lw). */
+int xmem_s2m_pack(const float* image, const float* prev_mask, const uint8_t* scr, int ignore_class, int K,
+                  int H, int W, int Hp, int Wp, int lh, int lw, float* out, void* stream);
+
+/* nn.AdaptiveAvgPool2d(1) of the ASPP pooling branch (s2m/_deeplab.py:122-133) on NHWC: in [B][P][ld] -> out [B][C], mean over the
+ * P pixels in a fixed summation order (the same bits on every call).  C % 4 == 0, ld % 4 == 0, 16-byte aligned pointers. */
+int xmem_channel_mean(const float* in, int ld, int B, int P, int C, float* out, void* stream);
+
+/* The pooling branch's upsample from 1 x 1 (_deeplab.py:132): vec [B][C] written to every pixel of out [B][P][ld] (a channel slice
+ * of the ASPP concat buffer; C % 4 == 0, ld % 4 == 0, 16-byte aligned). */
+int xmem_broadcast_channels(const float* vec, float* out, int ld, int B, int P, int C, void* stream);
+
+/* F.interpolate(x, size=(Ho, Wo), mode='bilinear', align_corners=False) on NHWC into a channel slice (the DeepLabV3+ decoder,
+ * _deeplab.py:49-53): in [B][Hi][Wi][ldin] -> out [B][Ho][Wo][ldout], first C channels of each; source arithmetic as
+ * xmem_resize_bilinear.  C, ldin, ldout multiples of 4, 16-byte aligned pointers. */
+int xmem_resize_bilinear_nhwc(const float* in, int ldin, int B, int Hi, int Wi, int C, float* out, int ldout, int Ho, int Wo, void* stream);
+
+/* S2M output (s2m/utils.py:15-20 x4 bilinear, s2m_controller.py:36 sigmoid + unpad): logits [K][h4][w4] -> prob [K][H][W] (crop
+ * offsets lh, lw inside 4h4 x 4w4).  prob_wbg (nullable) [K+1][H][W] = aggregate_wbg(prob, keep_bg=True) with the logit temperature
+ * `temperature` (1000 = hard=True, interaction.py:36-51, 193-196); mask (nullable) [H][W] uint8 = its first-index argmax. */
+int xmem_s2m_output(const float* logits, int K, int h4, int w4, int H, int W, int lh, int lw,
+                    float* prob, float* prob_wbg, uint8_t* mask, float temperature, void* stream);
+
+/* aggregate_wbg(prob, keep_bg, hard) of interaction.py:36-51 on its own: prob [K][H][W] -> out [K+1][H][W] (keep_bg) or [K][H][W]
+ * (nullable), mask (nullable) = first-index argmax over the K + 1 softmax values; temperature 1 (hard=False) or 1000 (hard=True). */
+int xmem_aggregate_wbg(const float* prob, int K, int H, int W, int keep_bg, float temperature, float* out, uint8_t* mask, void* stream);
 
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);

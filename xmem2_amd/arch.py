@@ -117,3 +117,31 @@ def infer_dims(state_dict):
     else:
         hidden_dim = 0
     return key_dim, value_dim, hidden_dim
+
+
+def s2m_state_dict_spec():
+    """The 368 tensors of the S2M network, deeplabv3plus_resnet50(num_classes=1, output_stride=16)
+    (inference/interact/s2m/s2m_network.py:19-35): a ResNet-50 backbone with a 6-channel stem (s2m_resnet.py:92), layer1 and
+    layer4 as IntermediateLayerGetter keeps them, and the DeepLabV3+ head (s2m/_deeplab.py:30-45, 136-155), in state_dict order."""
+    spec = OrderedDict()
+    _conv(spec, 'backbone.conv1', 64, 6, 7, False)
+    _bn(spec, 'backbone.bn1', 64)
+    c = _bottleneck_layer(spec, 'backbone.layer1', 64, 64, 3, 1)
+    c = _bottleneck_layer(spec, 'backbone.layer2', c, 128, 4, 2)
+    c = _bottleneck_layer(spec, 'backbone.layer3', c, 256, 6, 2)
+    _bottleneck_layer(spec, 'backbone.layer4', c, 512, 3, 2)       # stride replaced by dilation: the same tensors
+    _conv(spec, 'classifier.project.0', 48, 256, 1, False)
+    _bn(spec, 'classifier.project.1', 48)
+    _conv(spec, 'classifier.aspp.convs.0.0', 256, 2048, 1, False)
+    _bn(spec, 'classifier.aspp.convs.0.1', 256)
+    for i in (1, 2, 3):
+        _conv(spec, f'classifier.aspp.convs.{i}.0', 256, 2048, 3, False)
+        _bn(spec, f'classifier.aspp.convs.{i}.1', 256)
+    _conv(spec, 'classifier.aspp.convs.4.1', 256, 2048, 1, False)
+    _bn(spec, 'classifier.aspp.convs.4.2', 256)
+    _conv(spec, 'classifier.aspp.project.0', 256, 1280, 1, False)
+    _bn(spec, 'classifier.aspp.project.1', 256)
+    _conv(spec, 'classifier.classifier.0', 256, 304, 3, False)
+    _bn(spec, 'classifier.classifier.1', 256)
+    _conv(spec, 'classifier.classifier.3', 1, 256, 1, True)
+    return spec

@@ -36,6 +36,7 @@ struct ConvArgs {
     int a_presplit;                            // SPLIT kernels: the A operand already holds [hi4|lo4] groups (Winograd-domain V)
     int dbg;                                   // tools builds only (-DXMEM_TOOLS, env XMEM_CONV_DBG): 1 = no epilogue stores, 2 = every M-tile loads
                                                // tile 0's A rows (L2-resident operands); results are then wrong - they attribute time
+    int dil, skip_taps;                        // DIL kernels only (xmem_conv2d_nhwc_dilated): tap spacing, 1 = skip taps outside the tile
 };
 #ifdef XMEM_TOOLS
 #define CDBG(bit) (p.dbg & (bit))
@@ -83,7 +84,11 @@ __device__ __forceinline__ f32x4 split_pack(const f32x4 v) {
 // projection, split-K partials) or rounded once to fp16 (HALF = 2: every activation).  Eight halfs occupy the 16 bytes of four
 // floats, so with Cin, ldin and K passed in 4-byte units (Cin / 2, ...) every loader of this file is unchanged; a 16-byte
 // fragment is ONE fp16 MFMA (k = 16: 8 halfs per lane half) instead of four fp32 ones.
-template <int BM, int BN, int TM, int TN, int BK, bool GENERIC, bool ONE = false, bool SPLIT = false, int HALF = 0, int NW = 4>
+// DIL (xmem_conv2d_nhwc_dilated, fp32 direct form only): tap (kh, kw) reads input pixel (oh*stride - pad + kh*dil, ow*stride - pad + kw*dil).
+// With skip_taps, a workgroup first bounds the output rows / columns its M-tile covers and drops every tap whose input rows or
+// columns fall outside the map for ALL of them (a k-tile of a !GENERIC plan lies inside one tap: Cin % BK == 0).  A dropped tap
+// would only have added exact zero products (acc + 0 * w == acc, and the accumulator starts at +0), so the sum keeps its bits.
+template <int BM, int BN, int TM, int TN, int BK, bool GENERIC, bool ONE = false, bool SPLIT = false, int HALF = 0, int NW = 4, bool DIL = false>
 __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
     constexpr int WN = BN / (32 * TN);
     constexpr int WM = BM / (32 * TM);
@@ -167,7 +172,8 @@ __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
         }
         if (!GENERIC) {
             const int tap = k0 / p.Cin, c0 = k0 - tap * p.Cin;
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
+            int kh = tap / p.KW, kw = tap - kh * p.KW;
+            if (DIL) { kh *= p.dil; kw *= p.dil; }
 #pragma unroll
             for (int i = 0; i < RA; ++i) {
                 const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
@@ -179,7 +185,8 @@ __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
             const int k = k0 + c4 * 4;
             const bool kok = k < p.K;
             const int tap = k / p.Cin, c0 = k - tap * p.Cin;
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
+            int kh = tap / p.KW, kw = tap - kh * p.KW;
+            if (DIL) { kh *= p.dil; kw *= p.dil; }
 #pragma unroll
             for (int i = 0; i < RA; ++i) {
                 const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
@@ -248,8 +255,46 @@ __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
     // before the k-loop: they fly under the first k-tile's MFMAs, and the next tile's operand loads - younger - are waited for as a whole
     // anyway.  (Between the first operand request and its wait they lose: the compiler's load counter is the minimum over all paths to
     // a join, so with a path that loads no residual the operand wait becomes vmcnt(0..3), behind every younger residual load.)
-    if (kt_begin < kt_end) {
-        load_tile(kt_begin);
+    // DIL + skip_taps: bit t of `taps` = tap t reads at least one in-bounds input pixel for some output pixel of this M-tile
+    unsigned long long taps = ~0ull;
+    if (DIL && !GENERIC && p.skip_taps) {
+        const int mlast = min(m0 + BM, p.M) - 1;
+        const int b0 = m0 / p.HoWo, b1 = mlast / p.HoWo;
+        const int r0 = m0 - b0 * p.HoWo, r1 = mlast - b1 * p.HoWo;
+        int oh_lo = 0, oh_hi = p.Ho - 1, ow_lo = 0, ow_hi = p.Wo - 1;     // conservative: the whole map
+        if (b0 == b1) {
+            oh_lo = r0 / p.Wo; oh_hi = r1 / p.Wo;
+            if (oh_lo == oh_hi) { ow_lo = r0 - oh_lo * p.Wo; ow_hi = r1 - oh_hi * p.Wo; }
+        }
+        unsigned rows = 0, cols = 0;
+        for (int t = 0; t < p.KH; ++t) {
+            const int lo = oh_lo * p.stride - p.pad + t * p.dil, hi = oh_hi * p.stride - p.pad + t * p.dil;
+            if (hi >= 0 && lo < p.H) rows |= 1u << t;
+        }
+        for (int t = 0; t < p.KW; ++t) {
+            const int lo = ow_lo * p.stride - p.pad + t * p.dil, hi = ow_hi * p.stride - p.pad + t * p.dil;
+            if (hi >= 0 && lo < p.W) cols |= 1u << t;
+        }
+        taps = 0;
+        for (int kh = 0; kh < p.KH; ++kh)
+            if ((rows >> kh) & 1u) taps |= (unsigned long long)cols << (kh * p.KW);
+    }
+    const int kt_per_tap = DIL && !GENERIC ? p.Cin / BK : 1;
+    // first k-tile at or after k whose tap is kept (the identity unless DIL + skip_taps)
+    auto next_kt = [&](int k) {
+        if (DIL && !GENERIC) {
+            while (k < kt_end) {
+                const int tap = k / kt_per_tap;
+                if ((taps >> tap) & 1ull) break;
+                k = (tap + 1) * kt_per_tap;
+            }
+        }
+        return k;
+    };
+    const int kt_first = next_kt(kt_begin);
+
+    if (kt_first < kt_end) {
+        load_tile(kt_first);
         CTRACE(1);
         store_tile(0);
     }
@@ -307,10 +352,12 @@ __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
         }
     }
 
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int buf = (kt - kt_begin) & 1;
-        const bool has_next = kt + 1 < kt_end;
-        if (has_next) load_tile(kt + 1);           // global loads in flight under the MFMAs below
+    int step = 0;
+    for (int kt = kt_first; kt < kt_end; ) {
+        const int buf = DIL ? (step & 1) : ((kt - kt_begin) & 1);
+        const int kt_next = next_kt(kt + 1);
+        const bool has_next = kt_next < kt_end;
+        if (has_next) load_tile(kt_next);          // global loads in flight under the MFMAs below
 
         const float* As = smem + buf * BUF + (wm * 32 * TM + l31) * LDK + lh * 4;
         const float* Bs = smem + buf * BUF + BM * LDK + (wn * 32 * TN + l31) * LDK + lh * 4;
@@ -362,6 +409,7 @@ __global__ __launch_bounds__(64 * NW) void conv_mfma_kernel(ConvArgs p) {
         }
         if (has_next) store_tile(buf ^ 1);
         __syncthreads();
+        kt = kt_next; ++step;
     }
 
     CTRACE(3);
@@ -1632,4 +1680,100 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
         rc = xmem_check_launch();
     }
     return rc;
+}
+
+// ----------------------------------------------------------------------------------------------
+// dilated convolution: the direct implicit GEMM with tap spacing `dilation` (DIL kernels above).  Plans are the direct tiles only
+// (plan_tile 0 = the heuristic of make_plan, 1..6 = {128x128, 128x64, 64x64} x {BK 32, BK 64}; split-K as there); no Winograd,
+// no fp16 / split-operand modes, Cout >= 2.  With dilation 1 and the same plan the products and their order are those of
+// xmem_conv2d_nhwc: the same bits.
+// ----------------------------------------------------------------------------------------------
+namespace {
+
+int validate_dilated(const xmem_conv_desc* d, int dilation) {
+    if (!d || !d->in || !d->w || !d->scale || !d->shift || !d->out) return XMEM_ERR_BAD_ARG;
+    if (dilation <= 0 || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 ||
+        d->stride <= 0 || d->pad < 0) return XMEM_ERR_BAD_ARG;
+    if (d->Cin % 4 != 0 || d->ldin % 4 != 0 || d->ldin < d->Cin || d->ldout < d->Cout) return XMEM_ERR_UNSUPPORTED;
+    if (d->res && d->ldres < d->Cout) return XMEM_ERR_BAD_ARG;
+    if ((long)d->H + 2 * d->pad - (long)dilation * (d->KH - 1) - 1 < 0 || (long)d->W + 2 * d->pad - (long)dilation * (d->KW - 1) - 1 < 0)
+        return XMEM_ERR_BAD_ARG;
+    if (d->plan_tile < 0 || d->plan_tile > 6 || d->plan_splitk < 0) return XMEM_ERR_BAD_ARG;
+    if (d->Cout == 1 || d->in_half || d->out_half || d->arith != 0 || d->res_broadcast) return XMEM_ERR_UNSUPPORTED;
+    if ((long)dilation * (d->KH - 1) > (1 << 20) || (long)dilation * (d->KW - 1) > (1 << 20)) return XMEM_ERR_UNSUPPORTED;
+    return XMEM_OK;
+}
+
+// the plan of the undilated descriptor with the same output size: H' = H - (dil - 1)(KH - 1) gives (H' + 2 pad - KH) / s + 1 =
+// (H + 2 pad - dil (KH - 1) - 1) / s + 1 (make_plan only reads the output size, K, Cin and Cout of a direct plan)
+Plan make_plan_dilated(const xmem_conv_desc* d, int dilation) {
+    xmem_conv_desc v = *d;
+    v.H = d->H - (dilation - 1) * (d->KH - 1);
+    v.W = d->W - (dilation - 1) * (d->KW - 1);
+    v.w_winograd = nullptr; v.w_winograd4 = nullptr; v.w_winograd_f16 = nullptr; v.w_split = nullptr; v.arith = 0;
+    return make_plan(&v);
+}
+
+template <int BM, int BN, int TM, int TN, int BK, bool G>
+int launch_dil_cfg(const ConvArgs& a, hipStream_t s) {
+    const size_t lds = (a.kt_per_split == 1 ? 1 : 2) * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
+    auto kern = conv_mfma_kernel<BM, BN, TM, TN, BK, G, false, false, 0, 4, true>;
+    if (xmem_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds) != XMEM_OK) return XMEM_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, 1, a.splitk), dim3(256), lds, s, a);
+    return xmem_check_launch();
+}
+
+template <int BK, bool G>
+int launch_dil(const Plan& pl, const ConvArgs& a, hipStream_t s) {
+    if (pl.bm == 128 && pl.bn == 128) return launch_dil_cfg<128, 128, 2, 2, BK, G>(a, s);
+    if (pl.bm == 128 && pl.bn == 64) return launch_dil_cfg<128, 64, 2, 1, BK, G>(a, s);
+    return launch_dil_cfg<64, 64, 1, 1, BK, G>(a, s);
+}
+
+}  // namespace
+
+extern "C" size_t xmem_conv2d_dilated_workspace_bytes(const xmem_conv_desc* d, int dilation) {
+    if (validate_dilated(d, dilation) != XMEM_OK) return 0;
+    const Plan pl = make_plan_dilated(d, dilation);
+    if (pl.splitk == 1) return 0;
+    const int Ho = (d->H + 2 * d->pad - dilation * (d->KH - 1) - 1) / d->stride + 1;
+    const int Wo = (d->W + 2 * d->pad - dilation * (d->KW - 1) - 1) / d->stride + 1;
+    return (size_t)pl.splitk * d->B * Ho * Wo * d->Cout * sizeof(float);
+}
+
+extern "C" int xmem_conv2d_nhwc_dilated(const xmem_conv_desc* d, int dilation, int flags, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    int rc = validate_dilated(d, dilation);
+    if (rc != XMEM_OK) return rc;
+    if (flags & ~XMEM_DILATED_NO_TAP_SKIP) return XMEM_ERR_BAD_ARG;
+    const Plan pl = make_plan_dilated(d, dilation);
+    const int Ho = (d->H + 2 * d->pad - dilation * (d->KH - 1) - 1) / d->stride + 1;
+    const int Wo = (d->W + 2 * d->pad - dilation * (d->KW - 1) - 1) / d->stride + 1;
+    if ((double)d->B * Ho * Wo >= 2.0e9 || (double)d->B * d->H * d->W * d->ldin >= 2.0e9) return XMEM_ERR_UNSUPPORTED;
+    ConvArgs a;
+    a.in = d->in; a.w = d->w; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.out = d->out;
+    a.partial = reinterpret_cast<float*>(workspace);
+    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldin = d->ldin;
+    a.Ho = Ho; a.Wo = Wo; a.Cout = d->Cout; a.ldout = d->ldout; a.ldres = d->ldres;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+    a.K = d->KH * d->KW * d->Cin; a.M = d->B * Ho * Wo; a.HoWo = Ho * Wo;
+    a.relu_in = d->relu_in; a.relu_out = d->relu_out;
+    a.nk = pl.nk; a.splitk = pl.splitk; a.kt_per_split = pl.kt_per_split;
+    a.tiles_m = cdiv(a.M, pl.bm); a.tiles_n = cdiv(a.Cout, pl.bn);
+    a.raw = 0; a.res_mod = 0; a.in_gstride = 0; a.w_gstride = 0; a.out_gstride = 0;
+    a.a_presplit = 0; a.dbg = 0;
+    a.dil = dilation;
+    a.skip_taps = (flags & XMEM_DILATED_NO_TAP_SKIP) || d->KH * d->KW > 64 || d->KH > 32 || d->KW > 32 ? 0 : 1;
+    if (pl.splitk > 1) {
+        const size_t need = (size_t)pl.splitk * a.M * a.Cout * sizeof(float);
+        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (pl.bk == 64) rc = pl.generic ? launch_dil<64, true>(pl, a, s) : launch_dil<64, false>(pl, a, s);
+    else rc = pl.generic ? launch_dil<32, true>(pl, a, s) : launch_dil<32, false>(pl, a, s);
+    if (rc != XMEM_OK || pl.splitk == 1) return rc;
+    const size_t total = (size_t)a.M * a.Cout;
+    int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+    return xmem_check_launch();
 }

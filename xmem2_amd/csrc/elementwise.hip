@@ -880,3 +880,184 @@ extern "C" int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(cdiv(P, 32), cdiv(C, 32), B), dim3(256), 0, (hipStream_t)stream, in, out, ld, P, C);
     return xmem_check_launch();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Scribble-to-mask (S2M, inference/interact/s2m_controller.py) around the DeepLabV3+ convolutions
+// ---------------------------------------------------------------------------------------------
+
+// s2m_controller.py:27-35 + pad_divide_by (util/tensor_util.py:47-62): per object k and padded pixel, the 8-channel NHWC input
+// (r, g, b, prev == k, scr == k, scr != k && scr != ignore, 0, 0); zero in the padding (F.pad pads every channel with zeros)
+__global__ void s2m_pack_kernel(const float* __restrict__ image, const float* __restrict__ prev, const uint8_t* __restrict__ scr,
+                                int ignore_class, int K, int H, int W, int Hp, int Wp, int lh, int lw, float* __restrict__ out) {
+    const size_t P = (size_t)Hp * Wp, total = (size_t)K * P;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int pix = (int)(e % P), k = (int)(e / P) + 1;
+        const int y = pix / Wp - lh, x = pix % Wp - lw;
+        f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+        if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
+            const size_t q = (size_t)y * W + x;
+            const int s = scr[q];
+            lo.x = image[q]; lo.y = image[(size_t)H * W + q]; lo.z = image[(size_t)2 * H * W + q];
+            lo.w = prev[q] == (float)k ? 1.f : 0.f;
+            hi.x = s == k ? 1.f : 0.f;
+            hi.y = (s != k && s != ignore_class) ? 1.f : 0.f;
+        }
+        *reinterpret_cast<f32x4*>(out + e * 8) = lo;
+        *reinterpret_cast<f32x4*>(out + e * 8 + 4) = hi;
+    }
+}
+
+extern "C" int xmem_s2m_pack(const float* image, const float* prev_mask, const uint8_t* scr, int ignore_class, int K,
+                             int H, int W, int Hp, int Wp, int lh, int lw, float* out, void* stream) {
+    if (!image || !prev_mask || !scr || !out || K <= 0 || K > 254 || H <= 0 || W <= 0 || lh < 0 || lw < 0) return XMEM_ERR_BAD_ARG;
+    if (lh + H > Hp || lw + W > Wp) return XMEM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(s2m_pack_kernel, dim3(grid_for((size_t)K * Hp * Wp)), dim3(256), 0, (hipStream_t)stream,
+                       image, prev_mask, scr, ignore_class, K, H, W, Hp, Wp, lh, lw, out);
+    return xmem_check_launch();
+}
+
+// nn.AdaptiveAvgPool2d(1) of NHWC in [B][P][ld] (first C channels) -> out [B][C] = sum / P.  One workgroup per (64 channels, batch):
+// thread (row slice r = tid / 16, channel quad q = tid % 16) sums pixels r, r + 16, ... in order, then slice 0 adds the 16 partial
+// sums in slice order: a fixed reduction order, the same bits on every call.
+__global__ __launch_bounds__(256) void channel_mean_kernel(const float* __restrict__ in, int ld, int P, int C, float* __restrict__ out) {
+    __shared__ f32x4 part[16][16];
+    const int q = threadIdx.x & 15, r = threadIdx.x >> 4;
+    const int b = blockIdx.y, c = blockIdx.x * 64 + q * 4;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+        const float* base = in + (size_t)b * P * ld + c;
+        for (int p = r; p < P; p += 16) s += *reinterpret_cast<const f32x4*>(base + (size_t)p * ld);
+    }
+    part[r][q] = s;
+    __syncthreads();
+    if (r == 0 && c < C) {
+        f32x4 t = part[0][q];
+        for (int i = 1; i < 16; ++i) t += part[i][q];
+        const float inv = (float)P;
+        f32x4 m = {t.x / inv, t.y / inv, t.z / inv, t.w / inv};
+        *reinterpret_cast<f32x4*>(out + (size_t)b * C + c) = m;
+    }
+}
+
+extern "C" int xmem_channel_mean(const float* in, int ld, int B, int P, int C, float* out, void* stream) {
+    if (!in || !out || B <= 0 || P <= 0 || C <= 0 || ld < C) return XMEM_ERR_BAD_ARG;
+    if (C % 4 || ld % 4 || (((uintptr_t)in) & 15) || (((uintptr_t)out) & 15)) return XMEM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(channel_mean_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, (hipStream_t)stream, in, ld, P, C, out);
+    return xmem_check_launch();
+}
+
+// the ASPP pooling branch's upsample of a 1 x 1 map (_deeplab.py:128-133: bilinear from one pixel = that pixel):
+// vec [B][C] -> out[b][p][0..C) for every pixel p of an NHWC map with pixel stride ld (a channel slice of a wider buffer)
+__global__ void broadcast_channels_kernel(const float* __restrict__ vec, float* __restrict__ out, int ld, int P, int C4, int B) {
+    const size_t total = (size_t)B * P * C4;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(e % C4);
+        const size_t bp = e / C4;
+        const int b = (int)(bp / P);
+        *reinterpret_cast<f32x4*>(out + bp * ld + q * 4) = *reinterpret_cast<const f32x4*>(vec + ((size_t)b * C4 + q) * 4);
+    }
+}
+
+extern "C" int xmem_broadcast_channels(const float* vec, float* out, int ld, int B, int P, int C, void* stream) {
+    if (!vec || !out || B <= 0 || P <= 0 || C <= 0 || ld < C) return XMEM_ERR_BAD_ARG;
+    if (C % 4 || ld % 4 || (((uintptr_t)vec) & 15) || (((uintptr_t)out) & 15)) return XMEM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(broadcast_channels_kernel, dim3(grid_for((size_t)B * P * (C / 4))), dim3(256), 0, (hipStream_t)stream,
+                       vec, out, ld, P, C / 4, B);
+    return xmem_check_launch();
+}
+
+// F.interpolate(x, size=(Ho, Wo), mode='bilinear', align_corners=False) on NHWC (_deeplab.py:51-52, the DeepLabV3+ decoder's
+// 1/16 -> 1/4 upsample): in [B][Hi][Wi][ldin] (first C channels) -> out [B][Ho][Wo][ldout] (first C channels: `out` may point at a
+// channel slice of the concat buffer).  Source indices and weights as xmem_resize_bilinear (bilinear_src, scale = in / out).
+__global__ void resize_bilinear_nhwc_kernel(const float* __restrict__ in, int ldin, int Hi, int Wi, float* __restrict__ out, int ldout,
+                                            int Ho, int Wo, int C4, int B) {
+    const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+    const size_t total = (size_t)B * Ho * Wo * C4;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(e % C4);
+        const size_t pix = e / C4;
+        const int x = (int)(pix % Wo), y = (int)((pix / Wo) % Ho), b = (int)(pix / ((size_t)Wo * Ho));
+        int y0, y1, x0, x1; float ly, lx;
+        bilinear_src(y, sy, Hi, y0, y1, ly);
+        bilinear_src(x, sx, Wi, x0, x1, lx);
+        const float* p = in + (size_t)b * Hi * Wi * ldin + q * 4;
+        const f32x4 p00 = *reinterpret_cast<const f32x4*>(p + ((size_t)y0 * Wi + x0) * ldin);
+        const f32x4 p01 = *reinterpret_cast<const f32x4*>(p + ((size_t)y0 * Wi + x1) * ldin);
+        const f32x4 p10 = *reinterpret_cast<const f32x4*>(p + ((size_t)y1 * Wi + x0) * ldin);
+        const f32x4 p11 = *reinterpret_cast<const f32x4*>(p + ((size_t)y1 * Wi + x1) * ldin);
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const f32x4 v = hy * (hx * p00 + lx * p01) + ly * (hx * p10 + lx * p11);
+        *reinterpret_cast<f32x4*>(out + pix * ldout + q * 4) = v;
+    }
+}
+
+extern "C" int xmem_resize_bilinear_nhwc(const float* in, int ldin, int B, int Hi, int Wi, int C, float* out, int ldout,
+                                         int Ho, int Wo, void* stream) {
+    if (!in || !out || B <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || ldin < C || ldout < C) return XMEM_ERR_BAD_ARG;
+    if (C % 4 || ldin % 4 || ldout % 4 || (((uintptr_t)in) & 15) || (((uintptr_t)out) & 15)) return XMEM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(resize_bilinear_nhwc_kernel, dim3(grid_for((size_t)B * Ho * Wo * (C / 4))), dim3(256), 0, (hipStream_t)stream,
+                       in, ldin, Hi, Wi, out, ldout, Ho, Wo, C / 4, B);
+    return xmem_check_launch();
+}
+
+// aggregate_wbg (inference/interact/interaction.py:36-51) of one pixel: p[k * stride], k < K ->
+//   new = clamp(cat(prod_k (1 - p_k), p), 1e-7, 1 - 1e-7); l = log(new / (1 - new)) * temp; softmax over the K + 1 channels
+// written to out[c * ostride] for c = first .. K (first = 0: keep_bg; 1: without the background row, at out[(c - 1) * ostride]);
+// arg (nullable) = first index of the largest of the K + 1 softmax values, as torch.argmax
+__device__ __forceinline__ void wbg_pixel(const float* p, size_t stride, int K, float temp, int first, float* out, size_t ostride,
+                                          uint8_t* arg) {
+    float bg = 1.f, mx;
+    for (int k = 0; k < K; ++k) bg *= (1.f - p[k * stride]);
+    const float l0 = agg_logit(bg) * temp;
+    mx = l0;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, agg_logit(p[k * stride]) * temp);
+    const float e0 = expf(l0 - mx);
+    float den = e0;
+    for (int k = 0; k < K; ++k) den += expf(agg_logit(p[k * stride]) * temp - mx);
+    float best = e0 / den; int bi = 0;
+    if (first == 0 && out) out[0] = best;
+    for (int k = 0; k < K; ++k) {
+        const float v = expf(agg_logit(p[k * stride]) * temp - mx) / den;
+        if (out) out[(size_t)(k + 1 - first) * ostride] = v;
+        if (v > best) { best = v; bi = k + 1; }
+    }
+    if (arg) *arg = (uint8_t)bi;
+}
+
+// S2M output: logits [K][h4][w4] (the 1/4-resolution head) -> prob [K][H][W] = unpad(sigmoid(bilinear x4)) (s2m/utils.py:15-20,
+// s2m_controller.py:36); optional wbg [K+1][H][W] = aggregate_wbg(prob, keep_bg=True, hard=temp > 1) and its argmax (uint8)
+__global__ void s2m_output_kernel(const float* __restrict__ logits, int K, int h4, int w4, int H, int W, int lh, int lw,
+                                  float* __restrict__ prob, float* __restrict__ wbg, uint8_t* __restrict__ arg, float temp) {
+    const size_t P = (size_t)H * W;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(e % W), y = (int)(e / W);
+        int y0, y1, x0, x1; float ly, lx;
+        bilinear_src(y + lh, 0.25f, h4, y0, y1, ly);
+        bilinear_src(x + lw, 0.25f, w4, x0, x1, lx);
+        for (int k = 0; k < K; ++k) prob[k * P + e] = sigmoidf_(bilinear4(logits + (size_t)k * h4 * w4, h4, w4, y0, y1, x0, x1, ly, lx));
+        if (wbg || arg) wbg_pixel(prob + e, P, K, temp, 0, wbg ? wbg + e : nullptr, P, arg ? arg + e : nullptr);
+    }
+}
+
+extern "C" int xmem_s2m_output(const float* logits, int K, int h4, int w4, int H, int W, int lh, int lw,
+                               float* prob, float* prob_wbg, uint8_t* mask, float temperature, void* stream) {
+    if (!logits || !prob || K <= 0 || K > 254 || h4 <= 0 || w4 <= 0 || H <= 0 || W <= 0 || lh < 0 || lw < 0) return XMEM_ERR_BAD_ARG;
+    if (lh + H > 4 * h4 || lw + W > 4 * w4 || !(temperature > 0.f)) return XMEM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(s2m_output_kernel, dim3(grid_for((size_t)H * W)), dim3(256), 0, (hipStream_t)stream,
+                       logits, K, h4, w4, H, W, lh, lw, prob, prob_wbg, mask, temperature);
+    return xmem_check_launch();
+}
+
+__global__ void aggregate_wbg_kernel(const float* __restrict__ prob, int K, size_t P, float temp, int keep_bg, float* __restrict__ out,
+                                     uint8_t* __restrict__ arg) {
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (size_t)gridDim.x * blockDim.x)
+        wbg_pixel(prob + e, P, K, temp, keep_bg ? 0 : 1, out ? out + e : nullptr, P, arg ? arg + e : nullptr);
+}
+
+extern "C" int xmem_aggregate_wbg(const float* prob, int K, int H, int W, int keep_bg, float temperature, float* out, uint8_t* mask,
+                                  void* stream) {
+    if (!prob || (!out && !mask) || K <= 0 || K > 254 || H <= 0 || W <= 0 || !(temperature > 0.f)) return XMEM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(aggregate_wbg_kernel, dim3(grid_for((size_t)H * W)), dim3(256), 0, (hipStream_t)stream,
+                       prob, K, (size_t)H * W, temperature, keep_bg, out, mask);
+    return xmem_check_launch();
+}

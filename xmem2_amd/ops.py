@@ -187,12 +187,14 @@ class precision:
 class ConvWeights:
     """Device-resident convolution parameters in kernel layout: w [Cout][KH][KW][Cin_pad], scale, shift."""
     __slots__ = ('w', 'scale', 'shift', 'cout', 'cin', 'kh', 'kw', 'stride', 'pad', 'cin_true', 'wu', 'wu_f16', 'wu4',
-                 'sp_shift', 'scale_sp', 'w_sp', 'wu_sp', 'wu4_sp', 'w_h')
+                 'sp_shift', 'scale_sp', 'w_sp', 'wu_sp', 'wu4_sp', 'w_h', 'dilation')
 
-    def __init__(self, w, scale, shift, stride, pad, cin_true=None, winograd=True):
+    def __init__(self, w, scale, shift, stride, pad, cin_true=None, winograd=True, dilation=1):
         self.w, self.scale, self.shift = w, scale, shift
         self.cout, self.kh, self.kw, self.cin = w.shape
         self.stride, self.pad = stride, pad
+        self.dilation = dilation         # > 1: conv2d runs the dilated direct form (xmem_conv2d_nhwc_dilated)
+        winograd = winograd and dilation == 1
         self.cin_true = cin_true if cin_true is not None else self.cin     # un-padded Cin (algorithmic FLOPs)
         self.wu = None
         self.wu_f16 = None
@@ -683,11 +685,56 @@ def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False
         return _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype)
     if out_dtype is not None and out_dtype != torch.float32:
         raise RuntimeError('conv2d: a float32 input gives a float32 output (the fp16 loop converts at the max-pool after the stems)')
+    if cw.dilation != 1:
+        if res_broadcast:
+            raise RuntimeError('conv2d: a dilated convolution takes no broadcast residual')
+        return conv2d_dilated(x, cw, out=out, out_ld=out_ld, res=res, relu_in=relu_in, relu_out=relu_out, in_ld=in_ld, cin=cin, plan=plan)
     cin = cin if cin is not None else cw.cin
     if cin != cw.cin:
         raise RuntimeError(f'conv2d: weight expects Cin={cw.cin}, got {cin}')
     ldin = in_ld if in_ld is not None else x.shape[3]
     return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False)
+
+
+def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
+                   tap_skip=True):
+    """Dilated (atrous) convolution, fp32: x [B,H,W,C] NHWC (pixel stride `in_ld`) -> out [B,Ho,Wo,Cout], Ho = (H + 2 pad -
+    dilation (KH - 1) - 1) / stride + 1.  `dilation` defaults to cw.dilation; `plan` = (tile 0..6, split-K) of the direct form (None:
+    the library's heuristic); tap_skip=False keeps every tap (measurement only: the same bits)."""
+    _req(x, 'conv2d_dilated input')
+    dil = int(cw.dilation if dilation is None else dilation)
+    cin = cin if cin is not None else cw.cin
+    if cin != cw.cin:
+        raise RuntimeError(f'conv2d_dilated: weight expects Cin={cw.cin}, got {cin}')
+    ldin = in_ld if in_ld is not None else x.shape[3]
+    lib = load()
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    Ho = (H + 2 * cw.pad - dil * (cw.kh - 1) - 1) // cw.stride + 1
+    Wo = (W + 2 * cw.pad - dil * (cw.kw - 1) - 1) // cw.stride + 1
+    if Ho <= 0 or Wo <= 0:
+        raise RuntimeError(f'conv2d_dilated: empty output for a {H}x{W} input (pad {cw.pad}, dilation {dil})')
+    if out is None:
+        out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float32, device=x.device), cw.cout
+    elif out_ld is None:
+        out_ld = out.shape[-1]
+    d = ConvDesc()
+    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
+    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
+    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
+    d.res = res.data_ptr() if res is not None else None
+    d.ldres = res.shape[-1] if res is not None else 0
+    d.out = out.data_ptr(); d.ldout = out_ld
+    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
+    d.plan_tile, d.plan_splitk = tuple(plan) if plan is not None else (0, 0)
+    flags = 0 if tap_skip else _lib.DILATED_NO_TAP_SKIP
+    need = lib.xmem_conv2d_dilated_workspace_bytes(C.byref(d), dil)
+    ws = workspace(need, x.device, 'conv') if need else None
+    launch = lambda: lib.xmem_conv2d_nhwc_dilated(C.byref(d), dil, flags, ptr(ws), need, stream_ptr())
+    check(launch())
+    if RECORD is not None:
+        key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad}d{dil} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
+        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch, (x, out, res, cw, ws, dict(dilation=dil))))
+    return out
 
 
 _HIPRT = None
@@ -1137,3 +1184,77 @@ def select_greater(usage, threshold_dev):
     cnt = torch.empty((1,), dtype=torch.int32, device=usage.device)
     check(load().xmem_select_greater(ptr(usage), n, ptr(threshold_dev), ptr(idx), ptr(cnt), stream_ptr()))
     return idx, cnt
+
+
+# ---- scribble-to-mask (S2M) ---------------------------------------------------------------------------------
+
+def s2m_pack(image, prev_mask, scr, K, ignore_class, Hp, Wp, lh, lw, out=None):
+    """image [3,H,W] float, prev_mask [H,W] float (object index), scr [H,W] uint8 -> [K,Hp,Wp,8] (the S2M input of every object)."""
+    _req(image, 'image')
+    _req(prev_mask, 'prev_mask')
+    if not scr.is_cuda or scr.dtype != torch.uint8:
+        raise RuntimeError('s2m_pack: expected a CUDA (HIP) uint8 scribble map')
+    H, W = image.shape[-2:]
+    if tuple(prev_mask.shape[-2:]) != (H, W) or tuple(scr.shape[-2:]) != (H, W):
+        raise RuntimeError(f's2m_pack: image {H}x{W}, prev_mask {tuple(prev_mask.shape)} and scribbles {tuple(scr.shape)} differ in size')
+    image, prev_mask, scr = image.contiguous(), prev_mask.contiguous(), scr.contiguous()
+    if out is None:
+        out = torch.empty((K, Hp, Wp, 8), dtype=torch.float32, device=image.device)
+    check(load().xmem_s2m_pack(ptr(image), ptr(prev_mask), ptr(scr), int(ignore_class), int(K), H, W, Hp, Wp, lh, lw, ptr(out), stream_ptr()))
+    return out
+
+
+def channel_mean(x, out=None):
+    """x [B,H,W,C] NHWC -> [B,C], the mean over the pixels (fixed summation order)."""
+    B, H, W, Cc = _req(x, 'channel_mean input').shape
+    if out is None:
+        out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
+    check(load().xmem_channel_mean(ptr(x), x.stride(2), B, H * W, Cc, ptr(out), stream_ptr()))
+    return out
+
+
+def broadcast_channels(vec, out):
+    """vec [B,C] -> every pixel of `out` [B,H,W,C] (a channel slice of a wider NHWC buffer: pixel stride out.stride(2))."""
+    B, H, W, Cc = out.shape
+    check(load().xmem_broadcast_channels(ptr(_req(vec, 'vec').contiguous()), ptr(out), out.stride(2), B, H * W, Cc, stream_ptr()))
+    return out
+
+
+def resize_bilinear_nhwc(x, shape, out=None):
+    """F.interpolate(x, size=shape, mode='bilinear', align_corners=False) on NHWC x [B,Hi,Wi,C] (pixel stride x.stride(2)) into
+    `out` [B,Ho,Wo,C] (may be a channel slice of a wider buffer)."""
+    B, Hi, Wi, Cc = _req(x, 'resize_bilinear_nhwc input').shape
+    Ho, Wo = int(shape[0]), int(shape[1])
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cc), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, Ho, Wo, Cc):
+        raise RuntimeError(f'resize_bilinear_nhwc: out has shape {tuple(out.shape)}, expected {(B, Ho, Wo, Cc)}')
+    check(load().xmem_resize_bilinear_nhwc(ptr(x), x.stride(2), B, Hi, Wi, Cc, ptr(out), out.stride(2), Ho, Wo, stream_ptr()))
+    return out
+
+
+def s2m_output(logits, H, W, lh, lw, temperature=1000.0, want_wbg=True, prob=None, wbg=None, mask=None):
+    """logits [K,h4,w4] -> prob [K,H,W] (sigmoid of the x4 bilinear upsample, cropped at lh, lw) and, with want_wbg,
+    aggregate_wbg(prob, keep_bg=True) at `temperature` [K+1,H,W] and its argmax (uint8 [H,W])."""
+    K, h4, w4 = _req(logits, 'logits').shape
+    dev = logits.device
+    if prob is None:
+        prob = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    if want_wbg and wbg is None:
+        wbg = torch.empty((K + 1, H, W), dtype=torch.float32, device=dev)
+    if want_wbg and mask is None:
+        mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    check(load().xmem_s2m_output(ptr(logits.contiguous()), K, h4, w4, H, W, lh, lw, ptr(prob), ptr(wbg), ptr(mask),
+                                 float(temperature), stream_ptr()))
+    return prob, wbg, mask
+
+
+def aggregate_wbg(prob, keep_bg=False, temperature=1.0, want_mask=False):
+    """interaction.py aggregate_wbg: prob [K,H,W] -> [K+1,H,W] (keep_bg) or [K,H,W]; with want_mask also the uint8 argmax of
+    the K + 1 softmax values."""
+    K, H, W = _req(prob, 'prob').shape
+    out = torch.empty((K + 1 if keep_bg else K, H, W), dtype=torch.float32, device=prob.device)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=prob.device) if want_mask else None
+    check(load().xmem_aggregate_wbg(ptr(prob.contiguous()), K, H, W, int(bool(keep_bg)), float(temperature), ptr(out), ptr(mask),
+                                    stream_ptr()))
+    return (out, mask) if want_mask else out

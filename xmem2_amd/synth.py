@@ -171,3 +171,50 @@ def synthetic_masks(num_frames, num_objects=1, height=480, width=854):
             rect = (yy >= y0) & (yy < y0 + int(height * 0.09)) & (xx >= x0) & (xx < x0 + int(width * 0.12))
             masks[t, k] = rect & (masks[t, 0] == 0)
     return masks
+
+
+def synthetic_s2m_state_dict(seed=0, as_torch=True):
+    """Conditioned synthetic checkpoint of the S2M network (the 368 names of arch.s2m_state_dict_spec), from the same integer hash.
+
+    Convolutions He-normal (backbone: fan-out as s2m_resnet.py:104-106; head: fan-in as _deeplab.py:55-61), BatchNorm with
+    non-trivial affine and running statistics, the last BN of every residual branch damped (x0.35) as in synthetic_state_dict.
+    Two conditionings keep the output informative: the stem's scribble channels (4: positive, 5: negative) x20 / x-20, so the
+    strokes visibly move the mask (plain He init: max |dp| 0.02), and the final 1x1 classifier x8 with bias 0, so that the
+    probabilities spread over (0, 1) instead of sitting at 0.5 (tests/golden/make_s2m_goldens.py asserts both on the reference's
+    outputs)."""
+    from .arch import s2m_state_dict_spec
+    spec = s2m_state_dict_spec()
+    out = {}
+    for ti, (name, shape) in enumerate(spec.items()):
+        stream = seed * 100003 + 50000 + ti
+        n = int(np.prod(shape)) if len(shape) else 1
+        if name.endswith('num_batches_tracked'):
+            arr = np.array(0, dtype=np.int64)
+        elif name.endswith('running_mean'):
+            arr = 0.05 * hash_normal(n, stream)
+        elif name.endswith('running_var'):
+            arr = hash_uniform(n, stream, 0.8, 1.25)
+        elif len(shape) == 1 and name.endswith('.weight'):      # BN gamma
+            arr = hash_uniform(n, stream, 0.85, 1.15)
+            if name.split('.')[-2] == 'bn3':
+                arr = arr * np.float32(0.35)
+        elif name == 'classifier.classifier.3.bias':
+            arr = np.zeros(n, np.float32)
+        elif len(shape) == 1:                                     # BN beta
+            arr = 0.02 * hash_normal(n, stream)
+        else:
+            cout, cin, kh, kw = shape
+            fan = kh * kw * (cout if name.startswith('backbone') else cin)
+            arr = hash_normal(n, stream) * np.float32(math.sqrt(2.0 / fan))
+            if name == 'backbone.conv1.weight':
+                arr = arr.reshape(shape).copy()
+                arr[:, 4] *= np.float32(20.0)
+                arr[:, 5] *= np.float32(-20.0)
+            elif name == 'classifier.classifier.3.weight':
+                arr = arr * np.float32(8.0)
+        out[name] = np.asarray(arr).reshape(shape)
+    if as_torch:
+        import torch
+        return {k: (torch.from_numpy(np.ascontiguousarray(v)) if v.ndim else torch.tensor(int(v), dtype=torch.int64))
+                for k, v in out.items()}
+    return out
