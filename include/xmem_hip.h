@@ -376,7 +376,9 @@ typedef struct {
 
 /* out[obj][q][c] = sum_s w[q][s] * V_obj[idx[q][s]][c]   (sparse form of v @ affinity).
  * vsegs_host: n_obj * n_seg entries, object-major; all objects share the index space of the group.
- * out [n_obj][HW][ldout] NHWC rows (pixel stride ldout >= C_v). */
+ * out [n_obj][HW][ldout] NHWC rows (pixel stride ldout >= C_v).
+ * top_k in [1, 64] (what xmem_affinity_topk emits); a larger top_k returns XMEM_ERR_UNSUPPORTED and writes nothing.
+ * C_v, ldout and obj_stride are multiples of 4; n_seg <= XMEM_MAX_SEGMENTS; every object has object 0's segment sizes. */
 int xmem_readout_sparse(const xmem_value_segment* vsegs_host, int n_obj, int n_seg,
                         const float* w, const int32_t* idx, int HW, int top_k, int Cv,
                         float* out, int ldout, size_t obj_stride, void* stream);

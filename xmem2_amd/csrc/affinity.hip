@@ -1380,6 +1380,7 @@ extern "C" int xmem_readout_sparse_t(const xmem_value_segment* vsegs, int n_obj,
     float* out = reinterpret_cast<float*>(out_v);
     if (!vsegs || n_obj <= 0 || n_seg <= 0 || n_seg > XMEM_MAX_SEGMENTS || !w || !idx || !out || HW <= 0 || top_k <= 0) return XMEM_ERR_BAD_ARG;
     if (Cv % 4 || ldout % 4 || ldout < Cv || obj_stride % 4) return XMEM_ERR_UNSUPPORTED;
+    if (top_k > AFF_MAX_TOPK) return XMEM_ERR_UNSUPPORTED;      // rows[] / wsm[] of the kernel hold AFF_MAX_TOPK entries
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int per = RO_MAX_ENT / n_seg;
     for (int o0 = 0; o0 < n_obj; o0 += per) {
