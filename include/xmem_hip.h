@@ -40,8 +40,8 @@ typedef enum {
 
 /* ABI version of this header.  2 (round 4): xmem_conv_desc grew (in_half / out_half / w_half), storage-typed `_t` entry points, plan
  * tiles 23..40.  3 (round 5): no layout change, but the MEANING of w_winograd4 / w_winograd4_split changed - the F(4x4) transforms use the
- * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
-#define XMEM_ABI_VERSION 3
+ * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
+#define XMEM_ABI_VERSION 4
 int xmem_version(void);
 const char* xmem_last_error_string(int code); /* static string for a status code */
 
@@ -69,20 +69,44 @@ typedef struct {
     const float* res;   int ldres;
     float* out;         int ldout;
     int relu_in, relu_out;
-    int plan_tile;      /* 0 = built-in heuristic; 1..6 = {128x128, 128x64, 64x64} x {BK 32, BK 64} (autotuner override);
-                           7..12 = the same GEMM tiles inside the Winograd F(2x2,3x3) path (needs w_winograd);
-                           13..15 = fused Winograd GEMM + output transform, tiles {128x64, 64x64, 64x128};
-                           16 = REDUCED PRECISION (opt-in mode only, never the default): Winograd path whose transformed
-                                operands are stored in fp16 and multiplied on v_mfma_f32_32x32x16_f16 with fp32 accumulation
-                                (needs w_winograd_f16, Cin % 64 == 0) - the counterpart of the reference's
-                                torch.cuda.amp.autocast loop, inference/run_on_video.py:76 */
+    int plan_tile;      /* PLAN CODE 0..40 (anything else: XMEM_ERR_BAD_ARG): algorithm, GEMM tile (rows = output pixels or Winograd tiles
+                           x output channels), k-tile depth BK and kernel.  The one table behind it is kPlanCodes in csrc/conv_mfma.hip
+                           (Python: xmem2_amd/conv_plan.py CODES); xmem_conv2d_plan_info() reports what a descriptor resolves to.
+                             0       built-in heuristic: direct form, tile by the number of tiles (128x128, 128x64, else 64x64), BK 32
+                             1..6    direct implicit GEMM, {128x128, 128x64, 64x64} x BK {32, 64}
+                             7..12   Winograd F(2x2,3x3) (needs w_winograd), the same six GEMM tiles for its 16 position GEMMs
+                             13..15  F(2x2) with the output transform fused into the GEMM, tiles {128x64, 64x64, 64x128}, BK 32
+                             16      REDUCED PRECISION (opt-in mode 'fp16w' only, never the default): F(2x2) whose transformed operands
+                                     are stored in fp16 and multiplied on v_mfma_f32_32x32x16_f16 with fp32 accumulation (needs
+                                     w_winograd_f16, Cin % 64 == 0); its kernel picks 128x128 or 64x64 from the size
+                             17..22  Winograd F(4x4,3x3) (needs w_winograd4), the six GEMM tiles for its 36 position GEMMs
+                             23..28  F(4x4) with the position GEMMs on the streaming kernel (csrc/gemm_stream.hip):
+                                     tile {64x64, 128x64, 128x128} x ring of {3, 4} LDS stages
+                             29..34  F(2x2) likewise
+                             35..40  a 1x1 / pad 0 convolution itself on the streaming kernel, likewise
+                           FALLBACKS, applied in this order, of a code that does not apply to the layer ("Winograd-eligible": w_winograd
+                           given, 3x3 / stride 1 / pad 1, Cin % 32 == 0, Cout % 4 == 0, ldout % 4 == 0, ldres % 4 == 0, out and res
+                           16-byte aligned):
+                             - a streaming code the streaming kernel does not take (split arithmetic, Cin % 32 != 0, not Winograd-
+                               eligible or no F(4x4) operand, a 1x1 with padding) becomes 19 / 9 / 3: the 64x64 tile of its form;
+                             - F(4x4) without its operand (w_winograd4, or w_winograd4_split under arith = 1) becomes code - 10: F(2x2)
+                               with the same tile;
+                             - 16 without w_winograd_f16, with Cin % 64 != 0, not Winograd-eligible or under arith = 1 becomes 9;
+                             - 13 / 14 / 15 become 8 / 9 / 9 under arith = 1 (no split variant of the fused kernel), and 2 / 3 / 3 when
+                               the layer is not Winograd-eligible;
+                             - F(2x2) on a layer that is not Winograd-eligible (or, under arith = 1, without w_winograd_split) becomes
+                               code - 6: the direct form with the same tile.
+                           Cout = 1 ignores the code (a GEMV on the VALU).
+                           HALF MODE (in_half = 1) runs the direct BK-32 tiles only: 1..3 as above, 4 = 256x128 (8 waves; split-K as for
+                           128x128), 5 / 6 = the tiles of 2 / 3, 0 and everything above 6 = the heuristic.
+                           The dilated entry point takes 0..6. */
     int plan_splitk;    /* 0 = heuristic; >0 = number of K splits */
     const float* w_winograd; /* optional [16][Cout][Cin]: G g G^T of the 3x3 filter (3x3 / stride 1 / pad 1 only) */
     int res_broadcast;  /* 1: res is ONE image [Ho][Wo][ldres] added to every batch element (the per-object halves of the
                            fuser convolutions share the f16 half, model/modules.py:31-41 on cat([x, g])) */
-    const void* w_winograd_f16; /* optional [16][Cout][Cin] IEEE half: the same G g G^T rounded to fp16 (plan_tile 16 only) */
-    const float* w_winograd4;   /* optional [36][Cout][Cin]: G g G^T of Winograd F(4x4,3x3) (plan_tile 17..28 = the GEMM tiles of
-                                   plans 7..12 / the streaming GEMM inside the F(4x4) path; fp32).  INTERPOLATION POINTS
+    const void* w_winograd_f16; /* optional [16][Cout][Cin] IEEE half: the same G g G^T rounded to fp16 (see plan_tile) */
+    const float* w_winograd4;   /* optional [36][Cout][Cin]: G g G^T of Winograd F(4x4,3x3), fp32 (the F(4x4) plan codes, see plan_tile).
+                                   INTERPOLATION POINTS
                                    p = (0, 3/4, -3/4, 3/2, -3/2, inf) since ABI version 3 (version 2: 0, +-1, +-2, inf): row i of G is
                                    (1, p_i, p_i^2) / N_i with N_i = prod_{k != i} (p_i - p_k) over the finite points, the row of
                                    infinity (0, 0, 1):  64/81 0 0 | -128/243 -32/81 -8/27 | -128/243 32/81 -8/27 | 32/243 16/81 8/27 |
@@ -105,14 +129,28 @@ typedef struct {
      * CONTRACT: the kernel reads all Cin (the layer's channel count padded to 8) halfs of every pixel; a caller whose layer has
      * fewer true channels keeps the padding channels of `in` ZERO (finite is not enough of a promise: the zero weights there would turn
      * an Inf / NaN into NaN), and a channel slice of a wider buffer holds a multiple of 8 channels and ends inside its pixel.  The contraction runs
-     * on v_mfma_f32_32x32x16_f16 in the DIRECT form (no Winograd: plan_tile 1..3 / 0) with fp32 accumulation and an fp32 epilogue.
+     * on v_mfma_f32_32x32x16_f16 in the DIRECT form (no Winograd; its tiles: see plan_tile, HALF MODE) with fp32 accumulation and an fp32 epilogue.
      * out_half = 1: `out` and `res` are halfs too (ldout / ldres count halfs; the result is rounded once, to nearest even);
-     * out_half = 0 stores fp32 (key projection, mask head).  plan_tile 23..40, arith and the Winograd operands are ignored. */
+     * out_half = 0 stores fp32 (key projection, mask head).  arith and the Winograd operands are ignored. */
     int in_half, out_half;
     const void* w_half;
 } xmem_conv_desc;
 
 size_t xmem_conv2d_workspace_bytes(const xmem_conv_desc* d);
+
+/* The plan xmem_conv2d_nhwc would execute for `d` (plan_tile after its fallbacks, split-K after its rule).  Host only: no GPU call,
+ * no pointer of `d` is dereferenced.  Returns XMEM_OK or what xmem_conv2d_nhwc's argument validation returns. */
+enum { XMEM_CONV_GEMV = 0,      /* Cout = 1: a VALU GEMV, no tile */
+       XMEM_CONV_DIRECT = 1, XMEM_CONV_F2 = 2, XMEM_CONV_F2_FUSED = 3, XMEM_CONV_F2_F16 = 4, XMEM_CONV_F4 = 5 };
+typedef struct {
+    int form;           /* XMEM_CONV_* */
+    int bm, bn, bk;     /* GEMM tile (pixels or Winograd tiles x output channels) and k-tile depth; bm = bn = 0: no tile (GEMV), or
+                           chosen at launch from the size (XMEM_CONV_F2_F16) */
+    int splitk;         /* slabs of the contraction (1: no workspace reduction) */
+    int stream, ring;   /* stream = 1: the GEMM runs on the streaming kernel with a ring of `ring` stages; else 0, 0 */
+} xmem_conv_plan_info;
+int xmem_conv2d_plan_info(const xmem_conv_desc* d, xmem_conv_plan_info* out);
+
 int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Dilated convolution (atrous), the S2M network's DeepLabV3+ (inference/interact/s2m/s2m_resnet.py:17-20 conv3x3 with dilation, the

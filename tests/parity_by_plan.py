@@ -18,7 +18,7 @@ torch.set_grad_enabled(False)
 
 import clip_util as U  # noqa: E402
 from oracle import cpu_ref  # noqa: E402
-from xmem2_amd import ops  # noqa: E402
+from xmem2_amd import conv_plan  # noqa: E402
 from xmem2_amd.network import XMem  # noqa: E402
 from xmem2_amd.synth import synthetic_state_dict  # noqa: E402
 
@@ -45,7 +45,7 @@ def main():
         for form, label in ((None, 'shipped plans (F(4x4)+F(2x2)+direct)'), ('f2', 'F(4x4) -> F(2x2)'), ('direct', 'direct form everywhere'),
                             ('direct_sk2', 'direct form, every contraction summed in 2 slabs'),
                             ('direct_sk3', 'direct form, every contraction summed in 3 slabs')):
-            ops.CONV_FORM = form
+            conv_plan.CONV_FORM = form
             net = XMem({'key_dim': 64, 'value_dim': 512, 'hidden_dim': 64}, None).to('cuda').eval()
             net.load_weights(sd)
             a, _, s = U.run_gpu(net, clip)
@@ -53,7 +53,7 @@ def main():
             for name, lo, hi in spans:
                 print(f'   {name:26s} HIP [{label}] vs oracle(1 thr): {U.fmt(U.compare(a, o1, clip.labels, lo, hi))}')
             del net
-        ops.CONV_FORM = None
+        conv_plan.CONV_FORM = None
 
 
 if __name__ == '__main__':

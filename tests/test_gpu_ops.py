@@ -89,10 +89,12 @@ def test_conv2d(case):
 
 @pytest.mark.parametrize('plan', [(1, 1), (2, 2), (3, 4), (4, 1), (5, 3), (6, 2), (7, 1), (9, 1), (10, 1), (12, 1),
                                   (13, 1), (14, 1), (15, 1), (17, 1), (19, 1), (22, 1),
-                                  (23, 1), (24, 1), (25, 1), (26, 1), (27, 1), (28, 1), (29, 1), (30, 1), (31, 1), (32, 1)])
+                                  (23, 1), (24, 1), (25, 1), (26, 1), (27, 1), (28, 1), (29, 1), (30, 1), (31, 1), (32, 1),
+                                  (8, 1), (11, 1), (16, 1), (18, 1), (20, 1), (21, 1), (33, 1), (34, 1), (35, 1), (40, 1)])
 @pytest.mark.parametrize('shape', [(1, 30, 54, 256, 128), (2, 15, 27, 64, 96), (1, 17, 23, 32, 64)])
 def test_conv2d_every_plan(plan, shape):
-    """Every tile / split-K / Winograd plan the autotuner may pick computes the same 3x3 convolution."""
+    """Every tile / split-K / Winograd plan the autotuner may pick computes the same 3x3 convolution - and so does a code that
+    does not apply here and falls back: 16 (no fp16 operand in the fp32 mode), 35 / 40 (pointwise streaming codes on a 3x3)."""
     from xmem2_amd import ops
     from xmem2_amd.ops import ConvWeights
     B, H, W, Cin, Cout = shape

@@ -34,7 +34,7 @@ for (kind, key), (count, flop, fn) in rows.items():
 out.sort(reverse=True)
 tot = sum(o[0] for o in out)
 print(f'total {tot:.0f} us over {sum(o[2] for o in out)} launches')
-plans = ops._load_plans() if hasattr(ops, '_load_plans') else {}
+from xmem2_amd import conv_plan
 for t, us, c, kind, key, flop in out:
-    plan = plans.get(key) if isinstance(plans, dict) else None
+    plan = conv_plan.FP32.get(key)
     print(f'{t:8.1f} us  {c:2d} x {us:7.1f} us  {flop / us / 1e6:6.1f} TF  {kind:8s} {key}  plan={plan}')

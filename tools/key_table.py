@@ -34,6 +34,6 @@ for (kind, key), (count, flop, fn, keep) in rows.items():
 out.sort(reverse=True)
 tot = sum(o[0] for o in out)
 print(f'batch {B}: total {tot:.0f} us over {sum(o[2] for o in out)} conv launches = {tot / B:.0f} us per frame')
-plans = ops._load_plans()
+from xmem2_amd import conv_plan
 for t, us, c, kind, key, flop, nb in out:
-    print(f'{t:8.1f} us  {c:2d} x {us:7.1f} us  {flop / us / 1e6:6.1f} TF  {nb / us / 1e3:7.0f} GB/s(act)  {kind:5s} {key}  plan={plans.get(key)}')
+    print(f'{t:8.1f} us  {c:2d} x {us:7.1f} us  {flop / us / 1e6:6.1f} TF  {nb / us / 1e3:7.0f} GB/s(act)  {kind:5s} {key}  plan={conv_plan.FP32.get(key)}')

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
 import bench
-from xmem2_amd import InferenceCore, XMem, ops
+from xmem2_amd import InferenceCore, XMem, conv_plan, ops
 from xmem2_amd.synth import synthetic_state_dict
 torch.set_grad_enabled(False)
 dev = torch.device('cuda:0')
@@ -51,7 +51,7 @@ for kind, key, flop, fn, keep in recs:
             y = ops.conv2d(x, cw, res=res, relu_in=meta['relu_in'], relu_out=meta['relu_out'],
                            in_ld=meta['in_ld'] if meta['in_ld'] != x.shape[3] else None, cin=cin, res_broadcast=meta['res_broadcast'])
         errs[mode] = float((y.double().cpu().permute(0, 3, 1, 2) - ref).abs().max()) / max(scale, 1e-30)
-        plans[mode] = ops._lookup_plan(key, mode == 'fp32x')
+        plans[mode] = conv_plan.TABLES[mode].get(key, conv_plan.AUTOTUNE)
     rows.append((key, plans['fp32'], errs['fp32'], plans['fp32x'], errs['fp32x']))
 print(f'{"layer (B x H x W x Cin/ld -> Cout/ld, kernel, res/relu flags)":64s} {"fp32 plan":>10s} {"fp32 err":>10s} {"fp32x plan":>11s} {"fp32x err":>10s}')
 for key, p0, e0, p1, e1 in rows:

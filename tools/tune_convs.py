@@ -4,17 +4,14 @@ os.environ.setdefault('XMEM_CONV_AUTOTUNE', '1')          # this tool IS the aut
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 torch.set_grad_enabled(False)
-from xmem2_amd import ops, XMem, InferenceCore
+from xmem2_amd import conv_plan, ops, XMem, InferenceCore
 from xmem2_amd.synth import synthetic_state_dict, synthetic_frames, synthetic_masks
 import bench
 
 PREC = os.environ.get('XMEM_PRECISION', 'fp32')               # fp32x: measure the split-operand kernels -> conv_plans_fp32x.json
-if PREC == 'fp32x':
-    ops._load_plans(True)
-    if os.environ.get('XMEM_RETUNE_ALL'):
-        ops._plans_x = {}
-else:
-    ops._plans = {} if os.environ.get('XMEM_RETUNE_ALL') else ops._load_plans()   # default: keep shipped plans, add new shapes
+TABLE = conv_plan.TABLES.get(PREC, conv_plan.FP32)                                # the table of the kernels this run measures
+if os.environ.get('XMEM_RETUNE_ALL') and PREC != 'fp16':      # default: keep shipped plans, add new shapes
+    TABLE.forget_shipped()
 net = XMem(dict(bench.b32_config(), precision=PREC), None).to('cuda').eval(); net.load_weights(synthetic_state_dict(0))
 net.use_graphs = False
 GEOMS = [(480, 854, 1), (480, 854, 2), (480, 854, 3), (720, 1280, 1), (240, 427, 1), (240, 427, 2), (1080, 1920, 1)]
@@ -39,14 +36,8 @@ for (H, W, K) in GEOMS:
         pre = (ops.conv2d(xf, net._w['decoder.fuser.block1.conv1@x'], relu_in=True), ops.conv2d(xf, net._w['decoder.fuser.block1.downsample@x']))
         net._fusion(torch.randn(K, h16, w16, 1024 + 512 + 64, device='cuda').to(ops.act_dtype()), 'decoder.fuser', x=xf, pre=pre)
     torch.cuda.synchronize()
-    print(H, W, K, 'plans so far', len(ops._tuned_now_x if PREC == 'fp32x' else ops._tuned_now))
-if PREC == 'fp16':                           # the fp16 loop's half kernels: their own table (conv_plans_fp16.json)
-    n = ops.dump_tuned_plans_half(sys.argv[1] if len(sys.argv) > 1 else 'gpurun_out/conv_plans_fp16.json')
-    print('dumped', n)
-    for k, v in sorted(ops._tuned_now_h.items()):
-        print(k, v)
-    sys.exit(0)
-n = ops.dump_tuned_plans(sys.argv[1] if len(sys.argv) > 1 else 'gpurun_out/conv_plans.json', split=(PREC == 'fp32x'))
+    print(H, W, K, 'plans so far', len(TABLE.chosen))
+n = TABLE.dump(sys.argv[1] if len(sys.argv) > 1 else os.path.basename(TABLE.path))     # default: the table's file name, in the working directory
 print('dumped', n)
-for k, v in sorted((ops._tuned_now_x if PREC == 'fp32x' else ops._tuned_now).items()):
+for k, v in sorted(TABLE.chosen.items()):
     print(k, v)

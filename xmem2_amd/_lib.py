@@ -16,7 +16,7 @@ c_float_p = C.c_void_p
 c_void_p = C.c_void_p
 
 
-ABI_VERSION = 3          # include/xmem_hip.h XMEM_ABI_VERSION: the layout of ConvDesc below belongs to it
+ABI_VERSION = 4          # include/xmem_hip.h XMEM_ABI_VERSION: the layout of ConvDesc below belongs to it
 
 
 class ConvDesc(C.Structure):
@@ -31,6 +31,12 @@ class ConvDesc(C.Structure):
                 ('in_half', C.c_int), ('out_half', C.c_int), ('w_half', C.c_void_p)]
 
 
+class ConvPlanInfo(C.Structure):
+    _fields_ = [('form', C.c_int), ('bm', C.c_int), ('bn', C.c_int), ('bk', C.c_int), ('splitk', C.c_int), ('stream', C.c_int),
+                ('ring', C.c_int)]
+
+
+CONV_FORMS = ('gemv', 'direct', 'f2', 'f2_fused', 'f2_f16', 'f4')    # include/xmem_hip.h XMEM_CONV_*
 DILATED_NO_TAP_SKIP = 1  # include/xmem_hip.h XMEM_DILATED_NO_TAP_SKIP
 
 
@@ -55,6 +61,7 @@ _SIGS = {
     'xmem_last_error_string': (C.c_char_p, [C.c_int]),
     'xmem_trace_marker': (C.c_int, [C.c_int, C.c_void_p]),
     'xmem_conv2d_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc)]),
+    'xmem_conv2d_plan_info': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvPlanInfo)]),
     'xmem_conv2d_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     'xmem_conv2d_dilated_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc), C.c_int]),
     'xmem_conv2d_nhwc_dilated': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

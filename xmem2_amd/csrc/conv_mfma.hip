@@ -1273,91 +1273,101 @@ __global__ __launch_bounds__(256) void wino_gemm_f16_kernel(WinoF16Args p) {
 // ----------------------------------------------------------------------------------------------
 namespace {
 
-struct Plan { int bm, bn, bk, splitk, kt_per_split, nk; bool generic; bool wino; int fused; bool f16; bool wino4; bool split;
-              int stream, sv, sring; int half; };      // stream: 1 = GEMM on the streaming kernel (csrc/gemm_stream.hip), tile variant sv, ring sring
+// ---- plan codes ----------------------------------------------------------------------------------------------------------------
+// xmem_conv_desc.plan_tile -> what it asks for (include/xmem_hip.h documents the codes; xmem2_amd/conv_plan.py CODES is the Python
+// statement of this table, tests/test_conv_plan_host.py holds the two against each other).  ring > 0: the GEMM runs on the
+// streaming kernel (csrc/gemm_stream.hip) with that many LDS stages; bm = bn = 0: the tile is chosen from the size; fallback: the
+// code that takes over on a layer this one does not apply to (make_plan: applies).
+enum { GEMV = XMEM_CONV_GEMV, DIRECT = XMEM_CONV_DIRECT, F2 = XMEM_CONV_F2, F2_FUSED = XMEM_CONV_F2_FUSED, F2_F16 = XMEM_CONV_F2_F16,
+       F4 = XMEM_CONV_F4 };
+struct PlanCode { int form, bm, bn, bk, ring, fallback; };
+// six classic tiles; each falls back to the same tile of the form whose codes start at `fb`
+#define XMEM_TILES6(form, fb) {form, 128, 128, 32, 0, fb}, {form, 128, 64, 32, 0, fb + 1}, {form, 64, 64, 32, 0, fb + 2}, \
+                              {form, 128, 128, 64, 0, fb + 3}, {form, 128, 64, 64, 0, fb + 4}, {form, 64, 64, 64, 0, fb + 5}
+// six streaming variants; all fall back to the classic code `fb`
+#define XMEM_STREAM6(form, fb) {form, 64, 64, 32, 3, fb}, {form, 128, 64, 32, 3, fb}, {form, 128, 128, 32, 3, fb}, \
+                               {form, 64, 64, 32, 4, fb}, {form, 128, 64, 32, 4, fb}, {form, 128, 128, 32, 4, fb}
+constexpr PlanCode kPlanCodes[41] = {
+    {DIRECT, 0, 0, 32, 0, 0},                                                       //  0     the heuristic
+    XMEM_TILES6(DIRECT, 0),                                                         //  1..6  (apply to every layer)
+    XMEM_TILES6(F2, 1),                                                             //  7..12 -> the direct form with the same tile
+    {F2_FUSED, 128, 64, 32, 0, 8}, {F2_FUSED, 64, 64, 32, 0, 9}, {F2_FUSED, 64, 128, 32, 0, 9},   // 13..15 -> F(2x2), separate transform
+    {F2_F16, 0, 0, 32, 0, 9},                                                       // 16     (its own kernel contracts 64 halfs per k-tile)
+    XMEM_TILES6(F4, 7),                                                             // 17..22 -> F(2x2) with the same tile
+    XMEM_STREAM6(F4, 19), XMEM_STREAM6(F2, 9), XMEM_STREAM6(DIRECT, 3)              // 23..28, 29..34, 35..40 -> the classic 64x64 tile
+};
+#undef XMEM_TILES6
+#undef XMEM_STREAM6
+// a half-typed call (in_half) runs the BK-32 direct tiles only: plan_tile 1..3, 4 = the 256x128 tile (8 waves, planned as code 1),
+// 5 / 6 = the tiles of codes 2 / 3, anything else = the heuristic
+constexpr int kHalfCodes[7] = {0, 1, 2, 3, 1, 2, 3};
+
+struct Plan { int form, bm, bn, bk, splitk, kt_per_split, nk; bool generic, split; int ring, half; };
+
+inline bool winograd(const Plan& pl) { return pl.form == F2 || pl.form == F2_FUSED || pl.form == F2_F16 || pl.form == F4; }
 
 inline bool wino_ok(const xmem_conv_desc* d) {
     return d->w_winograd && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->Cin % 32 == 0 && d->Cout % 4 == 0 &&
            d->ldout % 4 == 0 && (!d->res || d->ldres % 4 == 0) && (((uintptr_t)d->out) & 15) == 0 && (!d->res || (((uintptr_t)d->res) & 15) == 0);
 }
 
-int validate(const xmem_conv_desc* d) {
+// argument checks common to the plain (dilation 1, codes 0..40) and the dilated (codes 0..6) entry points
+int validate(const xmem_conv_desc* d, int dilation = 1, int max_code = 40) {
     if (!d || !d->in || !d->w || !d->scale || !d->shift || !d->out) return XMEM_ERR_BAD_ARG;
-    if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 ||
+    if (dilation <= 0 || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 ||
         d->stride <= 0 || d->pad < 0) return XMEM_ERR_BAD_ARG;
     if (d->Cin % 4 != 0 || d->ldin % 4 != 0 || d->ldin < d->Cin || d->ldout < d->Cout) return XMEM_ERR_UNSUPPORTED;
     if (d->res && d->ldres < d->Cout) return XMEM_ERR_BAD_ARG;
-    if ((d->H + 2 * d->pad - d->KH) < 0 || (d->W + 2 * d->pad - d->KW) < 0) return XMEM_ERR_BAD_ARG;
-    if (d->plan_tile < 0 || d->plan_tile > 40 || d->plan_splitk < 0) return XMEM_ERR_BAD_ARG;
+    if ((long)d->H + 2 * d->pad - (long)dilation * (d->KH - 1) - 1 < 0 || (long)d->W + 2 * d->pad - (long)dilation * (d->KW - 1) - 1 < 0)
+        return XMEM_ERR_BAD_ARG;
+    if (d->plan_tile < 0 || d->plan_tile > max_code || d->plan_splitk < 0) return XMEM_ERR_BAD_ARG;
     return XMEM_OK;
 }
 
-inline void out_dims(const xmem_conv_desc* d, int& Ho, int& Wo) {
-    Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-    Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
+inline void out_dims(const xmem_conv_desc* d, int dilation, int& Ho, int& Wo) {
+    Ho = (d->H + 2 * d->pad - dilation * (d->KH - 1) - 1) / d->stride + 1;
+    Wo = (d->W + 2 * d->pad - dilation * (d->KW - 1) - 1) / d->stride + 1;
 }
 
-// plan_tile: 0 = heuristic, 1..6 = {128x128, 128x64, 64x64} x {BK 32, BK 64}
-Plan make_plan(const xmem_conv_desc* d) {
-    int Ho, Wo; out_dims(d, Ho, Wo);
+// The plan of `d` under plan code `code`: the table entry, the fallbacks of a code that does not apply to this layer, the split-K rule.
+Plan make_plan(const xmem_conv_desc* d, int code) {
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
     const int M = d->B * Ho * Wo, K = d->KH * d->KW * d->Cin;
-    Plan pl;
-    pl.bk = 32;
-    pl.generic = false;
-    pl.wino = false;
-    pl.fused = 0;
-    pl.f16 = false;
-    pl.wino4 = false;
-    pl.stream = 0; pl.sv = 0; pl.sring = 3; pl.half = 0;
+    Plan pl = {};
     // split-operand arithmetic ('fp32x', opt-in): every GEMM-shaped path; the Cout = 1 GEMV stays fp32 (it is HBM-bound)
     pl.split = d->arith == 1 && d->w_split != nullptr;
-    if (d->Cout == 1) { pl.split = false; pl.bm = 0; pl.bn = 0; pl.nk = cdiv(K, 32); pl.splitk = 1; pl.kt_per_split = pl.nk; return pl; }   // GEMV path
+    if (d->Cout == 1) { pl.form = GEMV; pl.split = false; pl.bk = 32; pl.nk = cdiv(K, 32); pl.splitk = 1; pl.kt_per_split = pl.nk; return pl; }
+    const bool wok = wino_ok(d);
+    // does code `c` apply to this layer?  A code that does not hands over to its fallback (kPlanCodes), until one applies.
+    auto applies = [&](const PlanCode& c) {
+        if (c.ring)              // the streaming kernel: fp32 operands with Cin % 32 == 0; the Winograd position GEMMs, or a 1x1 / pad 0
+            return !pl.split && d->Cin % 32 == 0 &&                                // convolution itself (32-bit byte offsets into both operands)
+                   (c.form == DIRECT ? (d->KH == 1 && d->KW == 1 && d->pad == 0 && (double)d->B * d->H * d->W * d->ldin * 4.0 < 2.0e9 &&
+                                        (double)d->Cout * d->Cin * 4.0 < 2.0e9)
+                                     : (wok && (c.form != F4 || d->w_winograd4 != nullptr)));
+        const bool f2_ok = wok && (!pl.split || d->w_winograd_split);
+        switch (c.form) {
+            case F4: return f2_ok && (pl.split ? d->w_winograd4_split : (const void*)d->w_winograd4) != nullptr;
+            case F2_F16: return wok && !pl.split && d->w_winograd_f16 && d->Cin % 64 == 0;    // fp16 storage and split mode exclude each other
+            case F2_FUSED: return wok && !pl.split;                                           // no split variant of the fused kernel
+            case F2: return f2_ok;
+            default: return true;
+        }
+    };
+    while (!applies(kPlanCodes[code])) code = kPlanCodes[code].fallback;
+    const PlanCode& c = kPlanCodes[code];
+    pl.form = c.form; pl.bm = c.bm; pl.bn = c.bn; pl.bk = c.bk; pl.ring = c.ring;
     auto tiles = [&](int bm, int bn) { return (long)cdiv(M, bm) * cdiv(d->Cout, bn); };
-    if (d->plan_tile > 0) {
-        static const int cfg[6][3] = {{128, 128, 32}, {128, 64, 32}, {64, 64, 32}, {128, 128, 64}, {128, 64, 64}, {64, 64, 64}};
-        int t = d->plan_tile;
-        if (t >= 23) {
-            // 23..28: F(4x4) with the position GEMMs on the streaming kernel, 29..34: F(2x2) likewise, 35..40: the pointwise
-            // (1x1, pad 0) convolution itself on it; within a group: tile {64x64, 128x64, 128x128} x ring {3, 4} stages.
-            // Shapes the streaming kernel does not take (split arithmetic, Cin % 32 != 0, 1x1 with padding) fall back to the
-            // 64x64 tile of the corresponding classic plan.
-            const int grp = (t - 23) / 6, v = (t - 23) % 6;
-            const bool ok = !pl.split && d->Cin % 32 == 0 &&
-                            (grp == 2 ? (d->KH == 1 && d->KW == 1 && d->pad == 0 &&
-                                         (double)d->B * d->H * d->W * d->ldin * 4.0 < 2.0e9 && (double)d->Cout * d->Cin * 4.0 < 2.0e9)
-                                      : (wino_ok(d) && (grp == 0 ? d->w_winograd4 != nullptr : true)));
-            if (ok) { pl.stream = 1; pl.sv = v % 3; pl.sring = 3 + v / 3; }
-            t = grp == 0 ? 19 : (grp == 1 ? 9 : 3);
-        }
-        if (t >= 17) {                     // F(4x4, 3x3) with the GEMM tile of plan t - 10; F(2x2) when its operand is absent
-            if (wino_ok(d) && (pl.split ? d->w_winograd4_split : (const void*)d->w_winograd4)) pl.wino4 = true;
-            t -= 10;
-        }
-        if (pl.split && t == 16) t = 9;    // the fp16-storage mode and the split mode exclude each other
-        if (pl.split && t > 12) t = (t == 13) ? 8 : 9;   // fused GEMM + output transform has no split variant: separate transform
-        if (t == 16) {                     // reduced-precision Winograd (opt-in); falls back to the fp32 Winograd tile 64x64
-            if (wino_ok(d) && d->w_winograd_f16 && d->Cin % 64 == 0) {
-                pl.wino = true; pl.f16 = true; pl.bm = 0; pl.bn = 0; pl.nk = d->Cin / 64; pl.splitk = 1; pl.kt_per_split = pl.nk;
-                return pl;
-            }
-            t = 9;
-        }
-        if (t > 12) {                      // 13..15: fused Winograd GEMM + output transform {128x64, 64x64, 64x128}, BK 32
-            if (wino_ok(d)) { pl.wino = true; pl.fused = t - 12; }
-            t = (t == 13) ? 2 : 3;         // fall back to a direct tile when Winograd is not applicable
-        }
-        if (t > 6 && wino_ok(d) && (!pl.split || d->w_winograd_split)) { pl.wino = true; }
-        if (t > 6) t -= 6;
-        pl.bm = cfg[t - 1][0]; pl.bn = cfg[t - 1][1]; pl.bk = cfg[t - 1][2];
-        if (pl.wino) {           // the GEMM runs per tile position: M = tiles, K = Cin, no split-K
-            pl.generic = (d->Cin % pl.bk) != 0; pl.nk = cdiv(d->Cin, pl.bk); pl.splitk = 1; pl.kt_per_split = pl.nk;
-            return pl;
-        }
-    } else {
+    if (code == 0) {
         // 256 CUs; two resident workgroups per CU is the sweet spot for the 128-wide tiles
         if (d->Cout > 64 && tiles(128, 128) >= 384) { pl.bm = 128; pl.bn = 128; }
         else if (tiles(128, 64) >= 384) { pl.bm = 128; pl.bn = 64; }
         else { pl.bm = 64; pl.bn = 64; }
+    }
+    if (winograd(pl)) {          // the GEMM runs per tile position: M = tiles, K = Cin, no split-K
+        pl.generic = pl.form != F2_F16 && (d->Cin % pl.bk) != 0;
+        pl.nk = pl.form == F2_F16 ? d->Cin / 64 : cdiv(d->Cin, pl.bk); pl.splitk = 1; pl.kt_per_split = pl.nk;
+        return pl;
     }
     pl.generic = (d->Cin % pl.bk) != 0;
     pl.nk = cdiv(K, pl.bk);
@@ -1374,44 +1384,100 @@ Plan make_plan(const xmem_conv_desc* d) {
             if (pl.splitk < 1) pl.splitk = 1;
         }
     }
-    if (pl.stream) pl.splitk = 1;                  // the streaming kernel contracts the whole K of a unit
+    if (pl.ring) pl.splitk = 1;                    // the streaming kernel contracts the whole K of a unit
     pl.kt_per_split = cdiv(pl.nk, pl.splitk);
     pl.splitk = cdiv(pl.nk, pl.kt_per_split);
     return pl;
 }
 
-// the Winograd-domain position GEMMs M[xi] = V[xi] U[xi]^T on the streaming kernel: G positions of [P x Cin] x [Cin x Cout]
-int launch_stream_positions(const Plan& pl, const float* V, const float* U, float* Mt, int G, int P, int Cin, int Cout, hipStream_t s) {
-    GemmStreamArgs g = {};
-    g.A = V; g.B = U; g.C = Mt;
-    g.a_gstride = (long)P * Cin; g.b_gstride = (long)Cout * Cin; g.c_gstride = (long)P * Cout;
-    g.M = P; g.N = Cout; g.K = Cin; g.G = G;
-    g.lda = Cin; g.ldb = Cin; g.ldc = Cout;
-    g.mode = 0; g.stride = 1;
-    return gemm_stream_launch(g, pl.sv, pl.sring, s);
+// fp16 loop: the descriptor as the fp32 machinery sees it - channels in 4-byte units (two halfs), direct plans only
+bool half_view(const xmem_conv_desc* d, xmem_conv_desc& v) {
+    if (!d->w_half || d->Cin % 8 != 0 || d->ldin % 8 != 0 || (((uintptr_t)d->in) & 15) != 0 || (((uintptr_t)d->w_half) & 15) != 0) return false;
+    v = *d;
+    v.Cin = d->Cin / 2; v.ldin = d->ldin / 2;
+    v.w_winograd = nullptr; v.w_winograd4 = nullptr; v.w_winograd_f16 = nullptr; v.arith = 0; v.w_split = nullptr;
+    return true;
 }
 
-// the 1x1 fast path needs 32-bit byte offsets into both operands (per group)
+// plan of a half-typed call (v: its half view); the 256x128 tile keeps the split-K of the 128x128 plan it is made from
+Plan make_plan_half(const xmem_conv_desc* v) {
+    Plan pl = make_plan(v, v->plan_tile <= 6 ? kHalfCodes[v->plan_tile] : 0);
+    if (v->plan_tile == 4 && pl.form == DIRECT) { pl.bm = 256; pl.bn = 128; }
+    return pl;
+}
+
+// the plan of a validated descriptor; a half-typed call continues on its half view `hv` (false: it has none)
+bool plan_of(const xmem_conv_desc*& d, xmem_conv_desc& hv, Plan& pl) {
+    if (d->in_half) {
+        if (!half_view(d, hv)) return false;
+        d = &hv;
+        pl = make_plan_half(d);
+    } else pl = make_plan(d, d->plan_tile);
+    return true;
+}
+
+// half output needs half input (the stems stay fp32); the mask head (Cout = 1) writes fp32 logits
+inline bool storage_types_ok(const xmem_conv_desc* d) { return d->in_half ? !(d->out_half && d->Cout == 1) : !d->out_half; }
+
+// ---- workspace: one formula per form, for the size queries and the launches ----
+inline size_t wino_tiles(const xmem_conv_desc* d, int Ho, int Wo, int r) { return (size_t)d->B * cdiv(Ho, r) * cdiv(Wo, r); }
+// V [(r+2)^2][P][Cin] and, unless the GEMM transforms its own output (fused), M [(r+2)^2][P][Cout]
+inline size_t wino_workspace(size_t P, int r, int Cin, int Cout, bool fused) {
+    return (size_t)(r + 2) * (r + 2) * P * (Cin + (fused ? 0 : Cout)) * sizeof(float);
+}
+inline size_t wino_f16_v_bytes(size_t P, int Cin) { return align_up((size_t)16 * P * Cin * 2, 256); }
+inline size_t splitk_workspace(const Plan& pl, const xmem_conv_desc* d, int Ho, int Wo) {
+    return pl.splitk == 1 ? 0 : (size_t)pl.splitk * d->B * Ho * Wo * d->Cout * sizeof(float);
+}
+size_t workspace_need(const Plan& pl, const xmem_conv_desc* d, int Ho, int Wo) {
+    if (pl.form == F4) return wino_workspace(wino_tiles(d, Ho, Wo, 4), 4, d->Cin, d->Cout, false);
+    const size_t P = wino_tiles(d, Ho, Wo, 2);
+    if (pl.form == F2_F16) return wino_f16_v_bytes(P, d->Cin) + (size_t)16 * P * d->Cout * sizeof(float);
+    if (pl.form == F2 || pl.form == F2_FUSED) return wino_workspace(P, 2, d->Cin, d->Cout, pl.form == F2_FUSED);
+    return splitk_workspace(pl, d, Ho, Wo);
+}
+
+// ---- launches ----
+// what both entry points pass to the direct kernels
+ConvArgs conv_args(const xmem_conv_desc* d, const Plan& pl, int Ho, int Wo, void* workspace) {
+    ConvArgs a;
+    a.in = d->in; a.w = d->w; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.out = d->out;
+    a.partial = reinterpret_cast<float*>(workspace);
+    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldin = d->ldin;
+    a.Ho = Ho; a.Wo = Wo; a.Cout = d->Cout; a.ldout = d->ldout; a.ldres = d->ldres;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+    a.K = d->KH * d->KW * d->Cin; a.M = d->B * Ho * Wo; a.HoWo = Ho * Wo;
+    a.relu_in = d->relu_in; a.relu_out = d->relu_out;
+    a.nk = pl.nk; a.splitk = pl.splitk; a.kt_per_split = pl.kt_per_split;
+    a.tiles_m = pl.bm ? cdiv(a.M, pl.bm) : 0; a.tiles_n = pl.bn ? cdiv(a.Cout, pl.bn) : 0;
+    a.raw = 0; a.res_mod = 0; a.in_gstride = 0; a.w_gstride = 0; a.out_gstride = 0;
+    a.a_presplit = 0; a.dbg = 0;
+    a.dil = 1; a.skip_taps = 0;
+    return a;
+}
+
 // Transform kernels are grid-stride over (tile, channel quad) items, one item per thread.  A 1/16-resolution layer has ~15 000 items:
 // as 256-thread workgroups that is ~60 workgroups on 60 of the 256 CUs, each bound by its own CU's load / store path (measured
 // 10-17 us for 12 MB).  Below 512 workgroups of 256 the items are dealt as 64-thread workgroups instead: four times the CUs.
-static inline void transform_grid(size_t items, int& blocks, int& threads) {
+inline void transform_grid(size_t items, int& blocks, int& threads) {
     threads = items < (size_t)512 * 256 ? 64 : 256;
     size_t b = (items + threads - 1) / threads;
     blocks = (int)(b > 16384 ? 16384 : b);
 }
 
-static bool conv_is_one(const ConvArgs& a) {
+// the 1x1 fast path needs 32-bit byte offsets into both operands (per group)
+bool conv_is_one(const ConvArgs& a) {
     return a.KH == 1 && a.KW == 1 && a.pad == 0 &&
            (double)a.B * a.H * a.W * a.ldin * 4.0 < 4.0e9 && (double)a.Cout * a.K * 4.0 < 4.0e9;
 }
 
 template <int BM, int BN, int TM, int TN, int BK, bool G>
-int launch_cfg(const ConvArgs& a, hipStream_t s, int groups = 1, bool split = false, int half = 0) {
+int launch_cfg(const ConvArgs& a, hipStream_t s, int groups, bool split, int half, bool dilated) {
     // (a workgroup that contracts a single k-tile never touches the second buffer: half the LDS, twice the resident workgroups)
     const size_t lds = (a.kt_per_split == 1 ? 1 : 2) * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
     auto kern = conv_mfma_kernel<BM, BN, TM, TN, BK, G, false, false>;
-    if (half && BK == 32) {                        // fp16 loop: half operands (HALF 1: fp32 output, 2: half output + residual)
+    if (dilated) kern = conv_mfma_kernel<BM, BN, TM, TN, BK, G, false, false, 0, 4, true>;
+    else if (half && BK == 32) {                   // fp16 loop: half operands (HALF 1: fp32 output, 2: half output + residual)
         const bool one = !G && conv_is_one(a);
         if (half == 2) kern = one ? conv_mfma_kernel<BM, BN, TM, TN, 32, false, true, false, 2> : conv_mfma_kernel<BM, BN, TM, TN, 32, G, false, false, 2>;
         else kern = one ? conv_mfma_kernel<BM, BN, TM, TN, 32, false, true, false, 1> : conv_mfma_kernel<BM, BN, TM, TN, 32, G, false, false, 1>;
@@ -1441,124 +1507,117 @@ int launch_half_256(const ConvArgs& a, hipStream_t s, int half) {
 }
 
 template <int BK, bool G>
-int launch_bk(const Plan& pl, const ConvArgs& a, hipStream_t s, int groups = 1) {
+int launch_bk(const Plan& pl, const ConvArgs& a, hipStream_t s, int groups, bool dilated) {
     if (pl.bm == 256) return launch_half_256<G>(a, s, pl.half);
-    if (pl.bm == 128 && pl.bn == 128) return launch_cfg<128, 128, 2, 2, BK, G>(a, s, groups, pl.split, pl.half);
-    if (pl.bm == 128 && pl.bn == 64) return launch_cfg<128, 64, 2, 1, BK, G>(a, s, groups, pl.split, pl.half);
-    return launch_cfg<64, 64, 1, 1, BK, G>(a, s, groups, pl.split, pl.half);
+    if (pl.bm == 128 && pl.bn == 128) return launch_cfg<128, 128, 2, 2, BK, G>(a, s, groups, pl.split, pl.half, dilated);
+    if (pl.bm == 128 && pl.bn == 64) return launch_cfg<128, 64, 2, 1, BK, G>(a, s, groups, pl.split, pl.half, dilated);
+    return launch_cfg<64, 64, 1, 1, BK, G>(a, s, groups, pl.split, pl.half, dilated);
 }
 
-}  // namespace
-
-// fp16 loop: the descriptor as the fp32 machinery sees it - channels in 4-byte units (two halfs), direct plans only
-static bool half_view(const xmem_conv_desc* d, xmem_conv_desc& v) {
-    if (!d->w_half || d->Cin % 8 != 0 || d->ldin % 8 != 0 || (((uintptr_t)d->in) & 15) != 0 || (((uintptr_t)d->w_half) & 15) != 0) return false;
-    v = *d;
-    v.Cin = d->Cin / 2; v.ldin = d->ldin / 2;
-    v.w_winograd = nullptr; v.w_winograd4 = nullptr; v.w_winograd_f16 = nullptr; v.arith = 0; v.w_split = nullptr;
-    if (v.plan_tile == 4) v.plan_tile = 104;                                          // 256x128 (8 waves), resolved by the caller
-    else if (v.plan_tile > 3) v.plan_tile = (v.plan_tile <= 6) ? v.plan_tile - 3 : 0;  // BK = 32 (64 halfs) tiles only
-    return true;
+// the implicit-GEMM kernel of the plan's tile: `groups` GEMMs (blockIdx.y: the Winograd positions), or the dilated form
+int launch_tile(const Plan& pl, const ConvArgs& a, hipStream_t s, int groups = 1, bool dilated = false) {
+    if (pl.bk == 64) return pl.generic ? launch_bk<64, true>(pl, a, s, groups, dilated) : launch_bk<64, false>(pl, a, s, groups, dilated);
+    return pl.generic ? launch_bk<32, true>(pl, a, s, groups, dilated) : launch_bk<32, false>(pl, a, s, groups, dilated);
 }
 
-// plan of a half-typed call: plan_tile 1..3 = {128x128, 128x64, 64x64}, 4 = 256x128 (8 waves), 0 = heuristic
-static Plan make_plan_half(xmem_conv_desc& v) {
-    const bool big = v.plan_tile == 104;
-    if (big) v.plan_tile = 1;
-    Plan pl = make_plan(&v);
-    if (big && pl.bm != 0) { pl.bm = 256; pl.bn = 128; }
-    return pl;
+int launch_splitk_reduce(const ConvArgs& a, bool half_out, hipStream_t s) {
+    const size_t total = (size_t)a.M * a.Cout;
+    int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+    if (half_out) hipLaunchKernelGGL(conv_splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
+    return xmem_check_launch();
 }
 
-extern "C" size_t xmem_conv2d_workspace_bytes(const xmem_conv_desc* d) {
-    if (validate(d) != XMEM_OK) return 0;
-    xmem_conv_desc hv;
-    if (d->in_half) {
-        if (!half_view(d, hv)) return 0;
-        d = &hv;
-    }
-    Plan pl = d->in_half ? make_plan_half(hv) : make_plan(d);
-    int Ho, Wo; out_dims(d, Ho, Wo);
-    if (pl.wino && pl.wino4) return (size_t)36 * d->B * cdiv(Ho, 4) * cdiv(Wo, 4) * (d->Cin + d->Cout) * sizeof(float);
-    if (pl.wino && pl.f16) return align_up((size_t)16 * d->B * cdiv(Ho, 2) * cdiv(Wo, 2) * d->Cin * 2, 256) +
-                                  (size_t)16 * d->B * cdiv(Ho, 2) * cdiv(Wo, 2) * d->Cout * sizeof(float);
-    if (pl.wino && pl.fused) return (size_t)16 * d->B * cdiv(Ho, 2) * cdiv(Wo, 2) * d->Cin * sizeof(float);
-    if (pl.wino) return (size_t)16 * d->B * cdiv(Ho, 2) * cdiv(Wo, 2) * (d->Cin + d->Cout) * sizeof(float);
-    if (pl.splitk == 1) return 0;
-    return (size_t)pl.splitk * d->B * Ho * Wo * d->Cout * sizeof(float);
-}
+int stream_variant(const Plan& pl) { return pl.bm == 64 ? 0 : (pl.bn == 64 ? 1 : 2); }     // gemm_stream.hpp: 64x64, 128x64, 128x128
 
-extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = validate(d);
-    if (rc != XMEM_OK) return rc;
-    xmem_conv_desc hv;
-    const int half = d->in_half ? (d->out_half ? 2 : 1) : 0;
-    if (half) {
-        if (d->out_half && d->Cout == 1) return XMEM_ERR_UNSUPPORTED;      // the mask head writes fp32 logits
-        if (!half_view(d, hv)) return XMEM_ERR_UNSUPPORTED;
-        d = &hv;
-    } else if (d->out_half) return XMEM_ERR_UNSUPPORTED;                    // half output needs half input (the stems stay fp32)
-    Plan pl = half ? make_plan_half(hv) : make_plan(d);
-    pl.half = half;
-    int Ho, Wo; out_dims(d, Ho, Wo);
-    ConvArgs a;
-    a.in = d->in; a.w = half ? reinterpret_cast<const float*>(d->w_half) : (pl.split ? reinterpret_cast<const float*>(d->w_split) : d->w);
-    a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.out = d->out;
-    a.a_presplit = 0;
-    a.partial = reinterpret_cast<float*>(workspace);
-    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldin = d->ldin;
-    a.Ho = Ho; a.Wo = Wo; a.Cout = d->Cout; a.ldout = d->ldout; a.ldres = d->ldres;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.K = d->KH * d->KW * d->Cin; a.M = d->B * Ho * Wo; a.HoWo = Ho * Wo;
-    a.relu_in = d->relu_in; a.relu_out = d->relu_out;
-    a.nk = pl.nk; a.splitk = pl.splitk; a.kt_per_split = pl.kt_per_split;
-    a.tiles_m = pl.bm ? cdiv(a.M, pl.bm) : 0; a.tiles_n = pl.bn ? cdiv(a.Cout, pl.bn) : 0;
-    a.raw = 0; a.res_mod = d->res_broadcast ? Ho * Wo : 0; a.in_gstride = 0; a.w_gstride = 0; a.out_gstride = 0;
-    a.dbg = 0;
-#ifdef XMEM_TOOLS
-    { static const int dbg = getenv("XMEM_CONV_DBG") ? atoi(getenv("XMEM_CONV_DBG")) : 0; a.dbg = dbg; }
-#endif
-    if (pl.wino && pl.wino4) {
-        const int th = cdiv(Ho, 4), tw = cdiv(Wo, 4);
-        const size_t P = (size_t)d->B * th * tw;
-        const size_t need = (size_t)36 * P * (d->Cin + d->Cout) * sizeof(float);
-        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
-        if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
-        float* V = reinterpret_cast<float*>(workspace);
-        float* Mt = V + (size_t)36 * P * d->Cin;
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        int blocks, threads;
-        transform_grid(P * (d->Cin / 4), blocks, threads);
-        hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W, d->Cin, th, tw,
-                           d->relu_in, V, pl.split ? 1 : 0);
+// Unfused Winograd F(r x r, 3x3), r = 2 or 4: input transform -> V, the (r+2)^2 position GEMMs M[xi] = V[xi] U[xi]^T of
+// [P x Cin] x [Cin x Cout] (on the plan's tile of the implicit-GEMM kernel, or on the streaming kernel), output transform + epilogue.
+int run_winograd(const Plan& pl, const xmem_conv_desc* d, const ConvArgs& a, int r, void* workspace, hipStream_t s) {
+    const int th = cdiv(a.Ho, r), tw = cdiv(a.Wo, r), G = (r + 2) * (r + 2);
+    const size_t P = wino_tiles(d, a.Ho, a.Wo, r);
+    if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
+    const float* U = r == 4 ? d->w_winograd4 : d->w_winograd;
+    const void* U_split = r == 4 ? d->w_winograd4_split : d->w_winograd_split;
+    float* V = reinterpret_cast<float*>(workspace);
+    float* Mt = V + (size_t)G * P * d->Cin;
+    const auto input_kernel = r == 4 ? wino4_input_kernel : wino_input_kernel;
+    const auto output_kernel = r == 4 ? wino4_output_kernel : wino_output_kernel;
+    int blocks, threads, rc;
+    transform_grid(P * (d->Cin / 4), blocks, threads);
+    hipLaunchKernelGGL(input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W,
+                       d->Cin, th, tw, d->relu_in, V, pl.split ? 1 : 0);
+    if (pl.ring) {
+        GemmStreamArgs g = {};
+        g.A = V; g.B = U; g.C = Mt;
+        g.a_gstride = (long)P * d->Cin; g.b_gstride = (long)d->Cout * d->Cin; g.c_gstride = (long)P * d->Cout;
+        g.M = (int)P; g.N = d->Cout; g.K = d->Cin; g.G = G;
+        g.lda = d->Cin; g.ldb = d->Cin; g.ldc = d->Cout;
+        g.mode = 0; g.stride = 1;
+        rc = gemm_stream_launch(g, stream_variant(pl), pl.ring, s);
+    } else {
         ConvArgs g = a;
-        g.in = V; g.w = pl.split ? reinterpret_cast<const float*>(d->w_winograd4_split) : d->w_winograd4;
+        g.in = V; g.w = pl.split ? reinterpret_cast<const float*>(U_split) : U;
         g.a_presplit = 1; g.out = Mt; g.res = nullptr; g.partial = nullptr;
         g.B = 1; g.H = 1; g.W = (int)P; g.ldin = d->Cin; g.Ho = 1; g.Wo = (int)P; g.ldout = d->Cout; g.ldres = 0;
         g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.K = d->Cin; g.M = (int)P; g.HoWo = (int)P;
         g.relu_in = 0; g.relu_out = 0; g.nk = pl.nk; g.splitk = 1; g.kt_per_split = pl.nk;
         g.tiles_m = cdiv(g.M, pl.bm); g.tiles_n = cdiv(g.Cout, pl.bn);
         g.raw = 1; g.in_gstride = (long)P * d->Cin; g.w_gstride = (long)d->Cout * d->Cin; g.out_gstride = (long)P * d->Cout;
-        if (pl.stream) rc = launch_stream_positions(pl, V, d->w_winograd4, Mt, 36, (int)P, d->Cin, d->Cout, s);
-        else
-        rc = (pl.bk == 64) ? (pl.generic ? launch_bk<64, true>(pl, g, s, 36) : launch_bk<64, false>(pl, g, s, 36))
-                           : (pl.generic ? launch_bk<32, true>(pl, g, s, 36) : launch_bk<32, false>(pl, g, s, 36));
-        if (rc != XMEM_OK) return rc;
-        transform_grid(P * (d->Cout / 4), blocks, threads);
-        hipLaunchKernelGGL(wino4_output_kernel, dim3(blocks), dim3(threads), 0, s, Mt, d->B, Ho, Wo, d->Cout, th, tw, d->scale, d->shift,
-                           d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
-        return xmem_check_launch();
+        rc = launch_tile(pl, g, s, G);
     }
-    if (pl.wino && pl.f16) {
+    if (rc != XMEM_OK) return rc;
+    transform_grid(P * (d->Cout / 4), blocks, threads);
+    hipLaunchKernelGGL(output_kernel, dim3(blocks), dim3(threads), 0, s, Mt, d->B, a.Ho, a.Wo, d->Cout,
+                       th, tw, d->scale, d->shift, d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
+    return xmem_check_launch();
+}
+
+}  // namespace
+
+extern "C" size_t xmem_conv2d_workspace_bytes(const xmem_conv_desc* d) {
+    xmem_conv_desc hv; Plan pl;
+    if (validate(d) != XMEM_OK || !plan_of(d, hv, pl)) return 0;
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
+    return workspace_need(pl, d, Ho, Wo);
+}
+
+extern "C" int xmem_conv2d_plan_info(const xmem_conv_desc* d, xmem_conv_plan_info* out) {
+    if (!out) return XMEM_ERR_BAD_ARG;
+    const int rc = validate(d);
+    if (rc != XMEM_OK) return rc;
+    xmem_conv_desc hv; Plan pl;
+    if (!storage_types_ok(d) || !plan_of(d, hv, pl)) return XMEM_ERR_UNSUPPORTED;
+    out->form = pl.form; out->bm = pl.bm; out->bn = pl.bn; out->bk = pl.bk; out->splitk = pl.splitk;
+    out->stream = pl.ring ? 1 : 0; out->ring = pl.ring;
+    return XMEM_OK;
+}
+
+extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = validate(d);
+    if (rc != XMEM_OK) return rc;
+    xmem_conv_desc hv; Plan pl;
+    if (!storage_types_ok(d) || !plan_of(d, hv, pl)) return XMEM_ERR_UNSUPPORTED;
+    const int half = d->in_half ? (d->out_half ? 2 : 1) : 0;
+    pl.half = half;
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
+    const size_t need = workspace_need(pl, d, Ho, Wo);
+    if (need && (!workspace || workspace_bytes < need)) return XMEM_ERR_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ConvArgs a = conv_args(d, pl, Ho, Wo, workspace);
+    if (half) a.w = reinterpret_cast<const float*>(d->w_half);
+    else if (pl.split) a.w = reinterpret_cast<const float*>(d->w_split);
+    a.res_mod = d->res_broadcast ? Ho * Wo : 0;
+#ifdef XMEM_TOOLS
+    { static const int dbg = getenv("XMEM_CONV_DBG") ? atoi(getenv("XMEM_CONV_DBG")) : 0; a.dbg = dbg; }
+#endif
+    if (pl.form == F4) return run_winograd(pl, d, a, 4, workspace, s);
+    if (pl.form == F2) return run_winograd(pl, d, a, 2, workspace, s);
+    if (pl.form == F2_F16) {
         const int th = cdiv(Ho, 2), tw = cdiv(Wo, 2);
-        const size_t P = (size_t)d->B * th * tw;
-        const size_t vbytes = align_up((size_t)16 * P * d->Cin * 2, 256);
-        const size_t need = vbytes + (size_t)16 * P * d->Cout * sizeof(float);
-        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
+        const size_t P = wino_tiles(d, Ho, Wo, 2);
         if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
         _Float16* V = reinterpret_cast<_Float16*>(workspace);
-        float* Mt = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + vbytes);
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        float* Mt = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + wino_f16_v_bytes(P, d->Cin));
         size_t tot = P * (d->Cin / 4);
         int blocks = (int)((tot + 255) / 256); if (blocks > 16384) blocks = 16384;
         hipLaunchKernelGGL(wino_input_f16_kernel, dim3(blocks), dim3(256), 0, s, d->in, d->ldin, d->B, d->H, d->W, d->Cin, th, tw,
@@ -1582,67 +1641,38 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
                            d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
         return xmem_check_launch();
     }
-    if (pl.wino) {
+    if (pl.form == F2_FUSED) {
         const int th = cdiv(Ho, 2), tw = cdiv(Wo, 2);
-        const size_t P = (size_t)d->B * th * tw;
-        const size_t need = (size_t)16 * P * (d->Cin + (pl.fused ? 0 : d->Cout)) * sizeof(float);
-        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
+        const size_t P = wino_tiles(d, Ho, Wo, 2);
         if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
         float* V = reinterpret_cast<float*>(workspace);
-        float* Mt = V + (size_t)16 * P * d->Cin;
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         int blocks, threads;
         transform_grid(P * (d->Cin / 4), blocks, threads);
         hipLaunchKernelGGL(wino_input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W, d->Cin, th, tw,
                            d->relu_in, V, pl.split ? 1 : 0);
-        if (pl.fused) {
-            WinoArgs wa;
-            wa.V = V; wa.U = d->w_winograd; wa.scale = d->scale; wa.shift = d->shift; wa.res = d->res; wa.out = d->out;
-            wa.P = (int)P; wa.Cin = d->Cin; wa.Cout = d->Cout; wa.B = d->B; wa.Ho = Ho; wa.Wo = Wo; wa.th = th; wa.tw = tw;
-            wa.ldout = d->ldout; wa.ldres = d->ldres; wa.relu_out = d->relu_out; wa.nk = cdiv(d->Cin, 32);
-            wa.res_bcast = d->res_broadcast ? 1 : 0;
-            const int bm = pl.fused == 1 ? 128 : 64, bn = pl.fused == 3 ? 128 : 64;
-            wa.tiles_m = cdiv(wa.P, bm); wa.tiles_n = cdiv(wa.Cout, bn);
-            const size_t lds = 2 * (size_t)(bm + bn) * 36 * sizeof(float);
-            dim3 grid(wa.tiles_m * wa.tiles_n);
-            if (pl.fused == 1) hipLaunchKernelGGL((wino_fused_kernel<128, 64, 2, 1, 32>), grid, dim3(256), lds, s, wa);
-            else if (pl.fused == 2) hipLaunchKernelGGL((wino_fused_kernel<64, 64, 1, 1, 32>), grid, dim3(256), lds, s, wa);
-            else hipLaunchKernelGGL((wino_fused_kernel<64, 128, 1, 2, 32>), grid, dim3(256), lds, s, wa);
-            return xmem_check_launch();
-        }
-        ConvArgs g = a;
-        g.in = V; g.w = pl.split ? reinterpret_cast<const float*>(d->w_winograd_split) : d->w_winograd;
-        g.a_presplit = 1; g.out = Mt; g.res = nullptr; g.partial = nullptr;
-        g.B = 1; g.H = 1; g.W = (int)P; g.ldin = d->Cin; g.Ho = 1; g.Wo = (int)P; g.ldout = d->Cout; g.ldres = 0;
-        g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.K = d->Cin; g.M = (int)P; g.HoWo = (int)P;
-        g.relu_in = 0; g.relu_out = 0; g.nk = pl.nk; g.splitk = 1; g.kt_per_split = pl.nk;
-        g.tiles_m = cdiv(g.M, pl.bm); g.tiles_n = cdiv(g.Cout, pl.bn);
-        g.raw = 1; g.in_gstride = (long)P * d->Cin; g.w_gstride = (long)d->Cout * d->Cin; g.out_gstride = (long)P * d->Cout;
-        if (pl.stream) rc = launch_stream_positions(pl, V, d->w_winograd, Mt, 16, (int)P, d->Cin, d->Cout, s);
-        else
-        rc = (pl.bk == 64) ? (pl.generic ? launch_bk<64, true>(pl, g, s, 16) : launch_bk<64, false>(pl, g, s, 16))
-                           : (pl.generic ? launch_bk<32, true>(pl, g, s, 16) : launch_bk<32, false>(pl, g, s, 16));
-        if (rc != XMEM_OK) return rc;
-        transform_grid(P * (d->Cout / 4), blocks, threads);
-        hipLaunchKernelGGL(wino_output_kernel, dim3(blocks), dim3(threads), 0, s, Mt, d->B, Ho, Wo, d->Cout, th, tw, d->scale, d->shift,
-                           d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
+        WinoArgs wa;
+        wa.V = V; wa.U = d->w_winograd; wa.scale = d->scale; wa.shift = d->shift; wa.res = d->res; wa.out = d->out;
+        wa.P = (int)P; wa.Cin = d->Cin; wa.Cout = d->Cout; wa.B = d->B; wa.Ho = Ho; wa.Wo = Wo; wa.th = th; wa.tw = tw;
+        wa.ldout = d->ldout; wa.ldres = d->ldres; wa.relu_out = d->relu_out; wa.nk = cdiv(d->Cin, 32);
+        wa.res_bcast = d->res_broadcast ? 1 : 0;
+        wa.tiles_m = cdiv(wa.P, pl.bm); wa.tiles_n = cdiv(wa.Cout, pl.bn);
+        const size_t lds = 2 * (size_t)(pl.bm + pl.bn) * 36 * sizeof(float);
+        dim3 grid(wa.tiles_m * wa.tiles_n);
+        if (pl.bm == 128) hipLaunchKernelGGL((wino_fused_kernel<128, 64, 2, 1, 32>), grid, dim3(256), lds, s, wa);
+        else if (pl.bn == 64) hipLaunchKernelGGL((wino_fused_kernel<64, 64, 1, 1, 32>), grid, dim3(256), lds, s, wa);
+        else hipLaunchKernelGGL((wino_fused_kernel<64, 128, 1, 2, 32>), grid, dim3(256), lds, s, wa);
         return xmem_check_launch();
     }
-    if (pl.splitk > 1) {
-        const size_t need = (size_t)pl.splitk * a.M * a.Cout * sizeof(float);
-        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (pl.stream && pl.bm != 0) {                 // pointwise convolution on the streaming kernel, fused epilogue
+    if (pl.ring) {                                 // pointwise convolution on the streaming kernel, fused epilogue
         GemmStreamArgs g = {};
         g.A = d->in; g.B = d->w; g.C = d->out; g.scale = d->scale; g.shift = d->shift; g.res = d->res;
         g.M = a.M; g.N = d->Cout; g.K = d->Cin; g.G = 1;
         g.lda = d->ldin; g.ldb = d->Cin; g.ldc = d->ldout; g.ldres = d->ldres;
         g.mode = 1; g.relu_in = d->relu_in; g.relu_out = d->relu_out; g.res_mod = a.res_mod;
         g.stride = d->stride; g.H = d->H; g.W = d->W; g.Wo = Wo; g.HoWo = Ho * Wo;
-        return gemm_stream_launch(g, pl.sv, pl.sring, s);
+        return gemm_stream_launch(g, stream_variant(pl), pl.ring, s);
     }
-    if (pl.bm == 0) {
+    if (pl.form == GEMV) {
         // (round 4: a variant with EIGHT output pixels of a row per wave measured 28.0 us against 24.9 us for the one-pixel-per-wave form at
         // the 480p mask head - its taps were fetched one after the other behind their bounds branches.  Round 6, with every load of a wave
         // requested together: four pixels per wave 26.8 us against 31.2 (host-side events, same bits), +0.6 % on the B32 line; small maps
@@ -1653,9 +1683,7 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
         else hipLaunchKernelGGL(conv_cout1_kernel<false>, dim3(cdiv(a.M, 4)), dim3(256), 0, s, a);
         return xmem_check_launch();
     }
-    if (pl.bk == 64) rc = pl.generic ? launch_bk<64, true>(pl, a, s) : launch_bk<64, false>(pl, a, s);
-    else rc = pl.generic ? launch_bk<32, true>(pl, a, s) : launch_bk<32, false>(pl, a, s);
-    if (rc != XMEM_OK) return rc;
+    if ((rc = launch_tile(pl, a, s)) != XMEM_OK) return rc;
 #ifdef XMEM_TOOLS
     if (a.dbg & 8) {
         static int printed = 0;
@@ -1672,33 +1700,19 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
         }
     }
 #endif
-    if (pl.splitk > 1) {
-        const size_t total = (size_t)a.M * a.Cout;
-        int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-        if (half == 2) hipLaunchKernelGGL(conv_splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-        rc = xmem_check_launch();
-    }
-    return rc;
+    return pl.splitk > 1 ? launch_splitk_reduce(a, half == 2, s) : rc;
 }
 
 // ----------------------------------------------------------------------------------------------
 // dilated convolution: the direct implicit GEMM with tap spacing `dilation` (DIL kernels above).  Plans are the direct tiles only
-// (plan_tile 0 = the heuristic of make_plan, 1..6 = {128x128, 128x64, 64x64} x {BK 32, BK 64}; split-K as there); no Winograd,
-// no fp16 / split-operand modes, Cout >= 2.  With dilation 1 and the same plan the products and their order are those of
-// xmem_conv2d_nhwc: the same bits.
+// (plan codes 0..6, split-K as in make_plan); no Winograd, no fp16 / split-operand modes, Cout >= 2.  With dilation 1 and the same
+// plan the products and their order are those of xmem_conv2d_nhwc: the same bits.
 // ----------------------------------------------------------------------------------------------
 namespace {
 
 int validate_dilated(const xmem_conv_desc* d, int dilation) {
-    if (!d || !d->in || !d->w || !d->scale || !d->shift || !d->out) return XMEM_ERR_BAD_ARG;
-    if (dilation <= 0 || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 ||
-        d->stride <= 0 || d->pad < 0) return XMEM_ERR_BAD_ARG;
-    if (d->Cin % 4 != 0 || d->ldin % 4 != 0 || d->ldin < d->Cin || d->ldout < d->Cout) return XMEM_ERR_UNSUPPORTED;
-    if (d->res && d->ldres < d->Cout) return XMEM_ERR_BAD_ARG;
-    if ((long)d->H + 2 * d->pad - (long)dilation * (d->KH - 1) - 1 < 0 || (long)d->W + 2 * d->pad - (long)dilation * (d->KW - 1) - 1 < 0)
-        return XMEM_ERR_BAD_ARG;
-    if (d->plan_tile < 0 || d->plan_tile > 6 || d->plan_splitk < 0) return XMEM_ERR_BAD_ARG;
+    const int rc = validate(d, dilation, 6);
+    if (rc != XMEM_OK) return rc;
     if (d->Cout == 1 || d->in_half || d->out_half || d->arith != 0 || d->res_broadcast) return XMEM_ERR_UNSUPPORTED;
     if ((long)dilation * (d->KH - 1) > (1 << 20) || (long)dilation * (d->KW - 1) > (1 << 20)) return XMEM_ERR_UNSUPPORTED;
     return XMEM_OK;
@@ -1711,34 +1725,15 @@ Plan make_plan_dilated(const xmem_conv_desc* d, int dilation) {
     v.H = d->H - (dilation - 1) * (d->KH - 1);
     v.W = d->W - (dilation - 1) * (d->KW - 1);
     v.w_winograd = nullptr; v.w_winograd4 = nullptr; v.w_winograd_f16 = nullptr; v.w_split = nullptr; v.arith = 0;
-    return make_plan(&v);
-}
-
-template <int BM, int BN, int TM, int TN, int BK, bool G>
-int launch_dil_cfg(const ConvArgs& a, hipStream_t s) {
-    const size_t lds = (a.kt_per_split == 1 ? 1 : 2) * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
-    auto kern = conv_mfma_kernel<BM, BN, TM, TN, BK, G, false, false, 0, 4, true>;
-    if (xmem_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds) != XMEM_OK) return XMEM_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, 1, a.splitk), dim3(256), lds, s, a);
-    return xmem_check_launch();
-}
-
-template <int BK, bool G>
-int launch_dil(const Plan& pl, const ConvArgs& a, hipStream_t s) {
-    if (pl.bm == 128 && pl.bn == 128) return launch_dil_cfg<128, 128, 2, 2, BK, G>(a, s);
-    if (pl.bm == 128 && pl.bn == 64) return launch_dil_cfg<128, 64, 2, 1, BK, G>(a, s);
-    return launch_dil_cfg<64, 64, 1, 1, BK, G>(a, s);
+    return make_plan(&v, v.plan_tile);
 }
 
 }  // namespace
 
 extern "C" size_t xmem_conv2d_dilated_workspace_bytes(const xmem_conv_desc* d, int dilation) {
     if (validate_dilated(d, dilation) != XMEM_OK) return 0;
-    const Plan pl = make_plan_dilated(d, dilation);
-    if (pl.splitk == 1) return 0;
-    const int Ho = (d->H + 2 * d->pad - dilation * (d->KH - 1) - 1) / d->stride + 1;
-    const int Wo = (d->W + 2 * d->pad - dilation * (d->KW - 1) - 1) / d->stride + 1;
-    return (size_t)pl.splitk * d->B * Ho * Wo * d->Cout * sizeof(float);
+    int Ho, Wo; out_dims(d, dilation, Ho, Wo);
+    return splitk_workspace(make_plan_dilated(d, dilation), d, Ho, Wo);
 }
 
 extern "C" int xmem_conv2d_nhwc_dilated(const xmem_conv_desc* d, int dilation, int flags, void* workspace, size_t workspace_bytes,
@@ -1747,33 +1742,15 @@ extern "C" int xmem_conv2d_nhwc_dilated(const xmem_conv_desc* d, int dilation, i
     if (rc != XMEM_OK) return rc;
     if (flags & ~XMEM_DILATED_NO_TAP_SKIP) return XMEM_ERR_BAD_ARG;
     const Plan pl = make_plan_dilated(d, dilation);
-    const int Ho = (d->H + 2 * d->pad - dilation * (d->KH - 1) - 1) / d->stride + 1;
-    const int Wo = (d->W + 2 * d->pad - dilation * (d->KW - 1) - 1) / d->stride + 1;
+    int Ho, Wo; out_dims(d, dilation, Ho, Wo);
     if ((double)d->B * Ho * Wo >= 2.0e9 || (double)d->B * d->H * d->W * d->ldin >= 2.0e9) return XMEM_ERR_UNSUPPORTED;
-    ConvArgs a;
-    a.in = d->in; a.w = d->w; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.out = d->out;
-    a.partial = reinterpret_cast<float*>(workspace);
-    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldin = d->ldin;
-    a.Ho = Ho; a.Wo = Wo; a.Cout = d->Cout; a.ldout = d->ldout; a.ldres = d->ldres;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.K = d->KH * d->KW * d->Cin; a.M = d->B * Ho * Wo; a.HoWo = Ho * Wo;
-    a.relu_in = d->relu_in; a.relu_out = d->relu_out;
-    a.nk = pl.nk; a.splitk = pl.splitk; a.kt_per_split = pl.kt_per_split;
-    a.tiles_m = cdiv(a.M, pl.bm); a.tiles_n = cdiv(a.Cout, pl.bn);
-    a.raw = 0; a.res_mod = 0; a.in_gstride = 0; a.w_gstride = 0; a.out_gstride = 0;
-    a.a_presplit = 0; a.dbg = 0;
+    ConvArgs a = conv_args(d, pl, Ho, Wo, workspace);
     a.dil = dilation;
     a.skip_taps = (flags & XMEM_DILATED_NO_TAP_SKIP) || d->KH * d->KW > 64 || d->KH > 32 || d->KW > 32 ? 0 : 1;
-    if (pl.splitk > 1) {
-        const size_t need = (size_t)pl.splitk * a.M * a.Cout * sizeof(float);
-        if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
-    }
+    const size_t need = splitk_workspace(pl, d, Ho, Wo);
+    if (need && (!workspace || workspace_bytes < need)) return XMEM_ERR_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (pl.bk == 64) rc = pl.generic ? launch_dil<64, true>(pl, a, s) : launch_dil<64, false>(pl, a, s);
-    else rc = pl.generic ? launch_dil<32, true>(pl, a, s) : launch_dil<32, false>(pl, a, s);
+    rc = launch_tile(pl, a, s, 1, true);
     if (rc != XMEM_OK || pl.splitk == 1) return rc;
-    const size_t total = (size_t)a.M * a.Cout;
-    int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, s, a);
-    return xmem_check_launch();
+    return launch_splitk_reduce(a, false, s);
 }

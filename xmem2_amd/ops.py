@@ -6,15 +6,13 @@ torch is plumbing only: allocation, streams.  No torch compute op is used on the
 """
 import contextlib
 import ctypes as C
-import json
 import math
 import os
-import sys
 import threading
 
 import torch
 
-from . import _lib
+from . import _lib, conv_plan
 from ._lib import AffinityHint, ConvDesc, KeySegment, ValueSegment, check, load, ptr, stream_ptr
 
 _workspaces = {}
@@ -273,17 +271,6 @@ def winograd4_weights(w):
     return u.reshape(36, w.shape[0], w.shape[3]).to(torch.float32).contiguous()
 
 
-# The heuristic plan (shapes the table does not list) takes F(4x4,3x3) from this many output pixels (1/8 resolution of 480p and
-# up), F(2x2,3x3) below: there the 36 tile-position GEMMs are too small to fill the chip.
-F4_MIN_PIXELS = 4096
-# Tools knob (parity attribution, tests/parity_by_plan.py): 'direct' runs every convolution in the direct implicit-GEMM form,
-# 'f2' replaces F(4x4) by F(2x2), 'direct_sk2' / 'direct_sk3' = the direct form summed in 2 / 3 slabs; None / '' = the shipped plan table.  Read at call time so that a tool can switch it.
-CONV_FORM = os.environ.get('XMEM_CONV_FORM') or None
-# the CONV_FORM forms that fix the plan outright: the library's deterministic direct-form heuristic; the direct form with every
-# contraction cut into 2 / 3 slabs summed afterwards (the SAME products in another fp32 summation order)
-_DIRECT_FORMS = {'direct': (0, 0), 'direct_sk2': (3, 2), 'direct_sk3': (3, 3)}
-
-
 def winograd_weights(w):
     """[Cout][3][3][Cin] -> G g G^T as [16][Cout][Cin] (load-time, fp32; F(2x2,3x3) of Lavin & Gray)."""
     g = _WINO_G.to(w.device)
@@ -291,229 +278,9 @@ def winograd_weights(w):
     return u.reshape(16, w.shape[0], w.shape[3]).contiguous()
 
 
-# ---- convolution plans ---------------------------------------------------------------------------------------
-# Tile shape / split-K of the implicit-GEMM kernel are chosen per layer shape.  Plans measured on an MI355X are
-# shipped in conv_plans.json (deterministic: the same plan -> the same summation order); shapes not listed there
-# take the library's built-in deterministic heuristic (same shape -> same tiles -> same summation order on every machine).
-# XMEM_CONV_AUTOTUNE=1 opts in to timing the candidates at first use (tools/tune_convs.py does, to refresh conv_plans.json).
-AUTOTUNE = os.environ.get('XMEM_CONV_AUTOTUNE', '0') == '1'
-_PLAN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans.json')
-_PLAN_FILE_X = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans_fp32x.json')   # measured with the split kernels
-_PLAN_FILE_H = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'conv_plans_fp16.json')    # measured with the half kernels
-_plans = None
-_plans_x = None
-_plans_h = None
-_tuned_now = {}
-_tuned_now_x = {}
-_tuned_now_h = {}
-
-
-def _read_plan_file(path):
-    if os.path.exists(path):
-        try:
-            return {k: tuple(v) for k, v in json.load(open(path)).items()}
-        except Exception:
-            pass
-    return {}
-
-
-def _load_plans(split=False):
-    """Plan table of the fp32 kernels, or (split=True) of the split-operand kernels: the GEMMs are ~4x cheaper there, so other
-    tiles win; shapes the fp32x table does not list fall back to the fp32 entry."""
-    global _plans, _plans_x
-    if _plans is None:
-        _plans = _read_plan_file(_PLAN_FILE)
-    if not split:
-        return _plans
-    if _plans_x is None:
-        _plans_x = _read_plan_file(_PLAN_FILE_X)
-    return _plans_x
-
-
-def _lookup_plan(key, split):
-    if split:
-        p = _load_plans(True).get(key) or _tuned_now_x.get(key)
-        if p is not None or AUTOTUNE:                 # the tuner measures the split kernels instead of inheriting the fp32 entry
-            return p
-        return _load_plans().get(key) or _tuned_now.get(key)
-    return _load_plans().get(key) or _tuned_now.get(key)
-
-
-def _half_plans():
-    global _plans_h
-    if _plans_h is None:
-        _plans_h = _read_plan_file(_PLAN_FILE_H)
-    return _plans_h
-
-
-def dump_tuned_plans(path, split=False):
-    """Write every plan known to this process (shipped + tuned now) - used to refresh conv_plans.json."""
-    if _PRECISION == 'fp32x' or split:
-        allp = dict(_load_plans(True))
-        allp.update(_tuned_now_x)
-        with open(path, 'w') as f:
-            json.dump({k: list(v) for k, v in sorted(allp.items())}, f, indent=0)
-        return len(allp)
-    allp = dict(_load_plans())
-    allp.update(_tuned_now)
-    if os.environ.get('XMEM_RETUNE_ALL') or '__tuned_with_f4__' in allp:
-        allp['__tuned_with_f4__'] = (1, 0)           # EVERY entry was measured against the F(4x4) candidates (full retune only)
-    with open(path, 'w') as f:
-        json.dump({k: list(v) for k, v in sorted(allp.items())}, f, indent=0)
-    return len(allp)
-
-
-# Tools (tools/tune_convs.py): XMEM_RETUNE_MARGIN=0.05 re-measures every TABLED shape against its candidates and replaces the tabled plan
-# only when a candidate is more than that fraction faster (12-launch timings, best of two): a table refresh after a kernel change
-# without the churn of equal-within-noise entries.
-RETUNE_MARGIN = float(os.environ.get('XMEM_RETUNE_MARGIN', '0') or 0)
-_retuned = set()
-
-
-def _tune_conv(lib, d, x_device, cw=None, incumbent=None):
-    """Time the candidate (tile, split-K) plans for this descriptor; returns the fastest (or `incumbent` unless beaten by RETUNE_MARGIN)."""
-    Ho = (d.H + 2 * d.pad - d.KH) // d.stride + 1
-    Wo = (d.W + 2 * d.pad - d.KW) // d.stride + 1
-    M, K = d.B * Ho * Wo, d.KH * d.KW * d.Cin
-    best, best_t = (0, 0), None
-    tiles = {1: (128, 128, 32), 2: (128, 64, 32), 3: (64, 64, 32), 4: (128, 128, 64), 5: (128, 64, 64), 6: (64, 64, 64)}
-    cands = list(tiles.items())
-    if d.w_winograd and d.ldout % 4 == 0 and (not d.res or d.ldres % 4 == 0):
-        cands += [(t + 6, cfg) for t, cfg in tiles.items()]
-        cands += [(13, (128, 64, 32)), (14, (64, 64, 32)), (15, (64, 128, 32))]
-        if cw is not None and Ho * Wo >= 256:          # F(4x4,3x3): the same GEMM tiles over 36 positions
-            _f4_operand(cw, d)
-            cands += [(t + 16, cfg) for t, cfg in tiles.items()]
-    for tile, (bm, bn, bk) in cands:
-        if bn == 128 and d.Cout <= 64 and tile != 15:
-            continue
-        nt = -(-M // bm) * -(-d.Cout // bn)
-        nk = -(-K // bk)
-        for sk in ((1,) if tile > 6 else (1, 2, 3, 4, 6, 8, 12, 16)):
-            if tile > 16 and nt * 36 < 128:
-                continue
-            if sk > 1 and (nt * sk > 2048 or nk // sk < 2):
-                continue
-            if sk == 1 and nt < 48 and nk >= 16:
-                continue
-            if incumbent is not None:
-                t = _time_plan(lib, d, x_device, (tile, sk))
-                if t is not None and (best_t is None or t < best_t):
-                    best, best_t = (tile, sk), t
-                continue
-            d.plan_tile, d.plan_splitk = tile, sk
-            need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-            ws = workspace(need, x_device, 'conv') if need else None
-            st = stream_ptr()
-            for _ in range(2):
-                if lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, st) != 0:
-                    break
-            else:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(4):
-                    lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, st)
-                e1.record()
-                e1.synchronize()
-                t = e0.elapsed_time(e1)
-                if best_t is None or t < best_t:
-                    best, best_t = (tile, sk), t
-    if incumbent is not None:
-        t_inc = _time_plan(lib, d, x_device, tuple(incumbent))
-        if t_inc is not None and (best_t is None or best_t > (1.0 - RETUNE_MARGIN) * t_inc):
-            return tuple(incumbent)
-        print(f'[retune] {tuple(incumbent)} {t_inc and round(t_inc * 1e3, 1)} us -> {best} {best_t and round(best_t * 1e3, 1)} us', file=sys.stderr)
-    return best
-
-
-# Streaming-GEMM variants of a tabled Winograd plan (csrc/gemm_stream.hip): plan 19 (F(4x4), 64x64 tile) -> 23 (64x64, ring 3),
-# 26 (64x64, ring 4), 24 (128x64, ring 3); plan 9 (F(2x2)) -> 29, 32.  XMEM_TUNE_STREAM=1 (tools/tune_convs.py) times the tabled
-# plan against them once per shape and keeps a variant only when it is at least 3 % faster (same arithmetic, same summation
-# order: results are bit-identical either way).
-TUNE_STREAM = os.environ.get('XMEM_TUNE_STREAM', '0') == '1'
-_STREAM_VARIANTS = {19: (23, 26, 24), 9: (29, 32)}
-_stream_checked = set()
-
-
-def _time_plan(lib, d, dev, plan, reps=12):
-    d.plan_tile, d.plan_splitk = plan
-    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-    ws = workspace(need, dev, 'conv') if need else None
-    st = stream_ptr()
-    for _ in range(3):
-        if lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, st) != 0:
-            return None
-    best = None
-    for _ in range(2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, st)
-        e1.record()
-        e1.synchronize()
-        t = e0.elapsed_time(e1) / reps
-        best = t if best is None or t < best else best
-    return best
-
-
-def _tune_conv_half(lib, d, dev):
-    """The same for the half kernels: tiles 1..3 and 4 = 256x128 (8 waves, half kernels only), split-K 1..8."""
-    best, best_t = (0, 0), None
-    for tile in (1, 2, 3, 4):
-        for sk in (1, 2, 4, 8):
-            t = _time_plan(lib, d, dev, (tile, sk), reps=8)
-            if t is not None and (best_t is None or t < best_t):
-                best, best_t = (tile, sk), t
-    return best
-
-
-def _tune_stream(lib, d, dev, plan):
-    base = _time_plan(lib, d, dev, plan)
-    best, best_t = plan, base
-    if base is not None:
-        for t in _STREAM_VARIANTS[plan[0]]:
-            tt = _time_plan(lib, d, dev, (t, 1))
-            if tt is not None and tt < 0.97 * base and tt < best_t:
-                best, best_t = (t, 1), tt
-    return best
-
-
-_TILES = {1: (128, 128), 2: (128, 64), 3: (64, 64), 4: (128, 128), 5: (128, 64), 6: (64, 64)}
-_STREAM_TILES = ((64, 64), (128, 64), (128, 128))
-
-
-def conv_executed_mfma_flops(B, Ho, Wo, cin, cout, kh, kw, stride, pad, plan_tile, winograd_ok):
-    """MFMA FLOPs the library really issues for one conv2d call under `plan_tile` (what an EXECUTED roofline fraction must count,
-    bench.py conv_roofline): the direct form contracts 2 * M * Cout * KH * KW * Cin with M / Cout padded to the tile and K to the
-    32-deep k-tile; F(2x2) runs 16 position GEMMs over ceil(Ho/2) * ceil(Wo/2) tiles per image (1/2.25 of the direct FLOPs before
-    padding), F(4x4) 36 over ceil(Ho/4) * ceil(Wo/4) (1/4).  Cout = 1 is a VALU GEMV: no MFMA work.  Mirrors make_plan() of
-    csrc/conv_mfma.hip; the built-in heuristic (plan 0) is counted with the 64x64 tile."""
-    if cout == 1:
-        return 0.0
-    t = int(plan_tile)
-    up = lambda a, b: -(-a // b) * b
-    form, tile = 'direct', (64, 64)
-    if 23 <= t <= 40:
-        grp, v = (t - 23) // 6, (t - 23) % 6
-        tile = _STREAM_TILES[v % 3]
-        form = ('f4', 'f2', 'direct')[grp]
-    elif 17 <= t <= 22:
-        form, tile = 'f4', _TILES[t - 16]
-    elif t == 16:
-        form, tile = 'f2', (64, 64)
-    elif 13 <= t <= 15:
-        form, tile = 'f2', {13: (128, 64), 14: (64, 64), 15: (64, 128)}[t]
-    elif 7 <= t <= 12:
-        form, tile = 'f2', _TILES[t - 6]
-    elif 1 <= t <= 6:
-        tile = _TILES[t]
-    if form != 'direct' and not winograd_ok:
-        form = 'direct'
-    if form == 'direct':
-        return 2.0 * up(B * Ho * Wo, tile[0]) * up(cout, tile[1]) * up(kh * kw * cin, 32)
-    r, npos = (4, 36) if form == 'f4' else (2, 16)
-    tiles = B * (-(-Ho // r)) * (-(-Wo // r))
-    return npos * 2.0 * up(tiles, tile[0]) * up(cout, tile[1]) * up(cin, 32)
+# ---- convolutions ---------------------------------------------------------------------------------------------
+# Which plan (tile / algorithm / split-K) a call runs under is decided in conv_plan.py: plan tables, tuner, heuristic.
+conv_executed_mfma_flops = conv_plan.executed_mfma_flops
 
 
 def _f4_operand(cw, d):
@@ -528,56 +295,22 @@ def _f4_operand(cw, d):
         d.w_winograd4_split = cw.wu4_sp.data_ptr()
 
 
-def _conv_plan(lib, d, cw, key, plan, dev, pixels, wino_ok):
-    """(tile, split-K) of one conv2d call, with `d` pointed at the F(4x4) operand when the plan reads it.  The plan is, in this order:
-    1. the caller's plan, taken literally (tests, tools, the fp16w mode);
-    2. a CONV_FORM attribution form (fp32 mode);
-    3. the plan table of the mode (the shipped conv_plans*.json, then the plans this process chose before);
-    4. the tuner: AUTOTUNE times the candidates of a shape the table lacks (with RETUNE_MARGIN also those of a tabled shape),
-       TUNE_STREAM tries the streaming-GEMM variants of a Winograd plan;
-    5. the deterministic heuristic: same shape -> same plan -> same summation order on every machine.
-    CONV_FORM 'f2' then runs the GEMM tile of an F(4x4) plan under F(2x2)."""
-    half, split = bool(d.in_half), d.arith == 1
-    fp32 = not half and _PRECISION == 'fp32'
-    explicit = plan is not None or (fp32 and CONV_FORM in _DIRECT_FORMS)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if explicit:
-        plan = tuple(plan) if plan is not None else _DIRECT_FORMS[CONV_FORM]
-    else:
-        tune = AUTOTUNE and cw.cout > 1 and not capturing
-        tuned = _tuned_now_h if half else _tuned_now_x if split else _tuned_now
-        plan = (_half_plans().get(key) or _tuned_now_h.get(key)) if half else _lookup_plan(key, split)
-        if plan is not None and tune and fp32 and RETUNE_MARGIN > 0 and key not in _retuned:
-            _retuned.add(key)                     # tools: the tabled plan against its candidates, replaced only when clearly beaten
-            if 17 <= plan[0] <= 28 and cw.wu is not None:
-                _f4_operand(cw, d)
-            new_plan = _tune_conv(lib, d, dev, cw, incumbent=plan)
-            if new_plan != plan:
-                plan = tuned[key] = new_plan
-        if plan is None:
-            if tune:
-                plan = _tune_conv_half(lib, d, dev) if half else _tune_conv(lib, d, dev, cw)
-            elif not half and cw.wu is not None and wino_ok:
-                # a shape the table does not know (another resolution / object count): the 3x3 stride-1 layers still take Winograd
-                # with the 64x64 GEMM tile instead of the direct form
-                plan = (19, 1) if pixels >= F4_MIN_PIXELS else (9, 1)
-            else:
-                plan = (0, 0)
-            tuned[key] = plan
-        if CONV_FORM == 'f2' and 17 <= plan[0] <= 28:     # F(4x4): classic tiles 17..22, streaming GEMM 23..28
-            plan = (plan[0] - 10 if plan[0] <= 22 else plan[0] + 6, plan[1])
-    d.w_winograd4 = None
-    if not half and 17 <= plan[0] <= 28 and cw.wu is not None:
-        _f4_operand(cw, d)
-    if TUNE_STREAM and not (explicit or half or split) and plan[0] in _STREAM_VARIANTS and key not in _stream_checked and not capturing:
-        _stream_checked.add(key)
-        plan = _tuned_now[key] = _tune_stream(lib, d, dev, plan)
-    return plan
+def _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out):
+    """The descriptor fields every convolution entry point takes: operands, geometry, epilogue."""
+    d = ConvDesc()
+    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = x.shape[0], x.shape[1], x.shape[2], cin, ldin
+    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
+    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
+    d.res = res.data_ptr() if res is not None else None
+    d.ldres = res.shape[-1] if res is not None else 0
+    d.out = out.data_ptr(); d.ldout = out_ld
+    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
+    return d
 
 
 def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half):
-    """One convolution of either path: descriptor, the operands of the precision mode, plan (_conv_plan), workspace, launch on the
-    current stream, and the RECORD entry."""
+    """One convolution of either path: descriptor, the operands of the precision mode, plan (conv_plan.choose), workspace, launch
+    on the current stream, and the RECORD entry."""
     lib = load()
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
     Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
@@ -586,15 +319,8 @@ def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, 
         out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=out_dtype, device=x.device), cw.cout
     elif out_ld is None:
         out_ld = out.shape[-1]
-    d = ConvDesc()
-    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
-    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
-    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.ldres = res.shape[-1] if res is not None else 0
+    d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
     d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
-    d.out = out.data_ptr(); d.ldout = out_ld
-    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
     wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
     key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
     if half:
@@ -604,7 +330,7 @@ def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, 
         d.w_winograd = cw.wu.data_ptr() if cw.wu is not None else None
         if _PRECISION == 'fp16w' and cw.wu_f16 is not None and plan is None and wino_ok:
             d.w_winograd_f16 = cw.wu_f16.data_ptr()
-            plan = (16, 1)                       # the library falls back to the fp32 Winograd tile if its own conditions fail
+            plan = (conv_plan.F2_F16, 1)         # the library falls back to the fp32 Winograd tile if its own conditions fail
         if _PRECISION == 'fp32x' and cw.cout > 1:
             # split-operand arithmetic for every GEMM-shaped path (the Cout = 1 mask head is a GEMV on the fp32 VALU)
             if cw.sp_shift is None or (cw.wu4 is not None and cw.wu4_sp is None):
@@ -618,20 +344,20 @@ def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, 
             d.w_winograd_split = cw.wu_sp.data_ptr() if cw.wu_sp is not None else None
             d.w_winograd4_split = cw.wu4_sp.data_ptr() if cw.wu4_sp is not None else None    # taken only by an F(4x4) plan
             d.scale = cw.scale_sp.data_ptr()
-    plan = _conv_plan(lib, d, cw, key, plan, x.device, B * Ho * Wo, wino_ok)
+    plan = conv_plan.choose(lib, d, key, plan, x.device, _PRECISION, cw.cout, cw.wu is not None, wino_ok, B * Ho * Wo,
+                            lambda: _f4_operand(cw, d))
     d.plan_tile, d.plan_splitk = plan
     need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
     ws = workspace(need, x.device, 'conv') if need else None
     launch = lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr())
     check(launch())
     if RECORD is not None:
-        tile = ({4: 1}.get(plan[0], plan[0]) if plan[0] <= 6 else 0) if half else plan[0]    # the half 256x128 tile counts as 128x128
         RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch,
                        (x, out, res, cw, ws, dict(relu_in=bool(relu_in), relu_out=bool(relu_out), in_ld=ldin, cin=cin, out_ld=out_ld,
                                                   res_broadcast=bool(res_broadcast), plan=tuple(plan),
-                                                  executed_mfma_flops=conv_executed_mfma_flops(
-                                                      B, Ho, Wo, cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, tile,
-                                                      bool(d.w_winograd) and wino_ok)))))
+                                                  executed_mfma_flops=conv_plan.executed_mfma_flops(
+                                                      B, Ho, Wo, cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, plan[0],
+                                                      bool(d.w_winograd) and wino_ok, half=half)))))
     return out
 
 
@@ -667,14 +393,6 @@ def _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, r
     if res is not None and res.dtype != odt:
         raise RuntimeError('conv2d (half): the residual must have the output storage type')
     return _conv_run(x, cw, cin_h, ldin, out, out_ld, odt, res, relu_in, relu_out, res_broadcast, plan, half=True)
-
-
-def dump_tuned_plans_half(path):
-    allp = dict(_half_plans())
-    allp.update(_tuned_now_h)
-    with open(path, 'w') as f:
-        json.dump({k: list(v) for k, v in sorted(allp.items())}, f, indent=0)
-    return len(allp)
 
 
 def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
@@ -717,14 +435,7 @@ def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_i
         out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float32, device=x.device), cw.cout
     elif out_ld is None:
         out_ld = out.shape[-1]
-    d = ConvDesc()
-    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
-    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
-    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.ldres = res.shape[-1] if res is not None else 0
-    d.out = out.data_ptr(); d.ldout = out_ld
-    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
+    d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
     d.plan_tile, d.plan_splitk = tuple(plan) if plan is not None else (0, 0)
     flags = 0 if tap_skip else _lib.DILATED_NO_TAP_SKIP
     need = lib.xmem_conv2d_dilated_workspace_bytes(C.byref(d), dil)
