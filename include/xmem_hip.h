@@ -214,6 +214,16 @@ int xmem_copy_channels(const float* src, int ldsrc, int srcB, float* dst, int ld
 int xmem_hidden_update_gather(const float* g16, int c16, const float* g8, int c8, const float* g4, int c4, const float* logits,
                               float* out, int ldout, int K, int h, int w, void* stream);
 
+/* The end of the decoder in one launch: the mask head (decoder.pred: 3x3, stride 1, pad 1, c4 -> 1, relu on its input; w [9][c4],
+ * scale[1], shift[1]) on g4 [K][4h][4w][c4] -> logits [K][4h][4w], the tensor xmem_hidden_update_gather builds (g4d, pixel stride
+ * ldg4d; channels past c16 + c8 + c4 + 1 are not written) from g16 / g8 / g4 and those logits, and hidden [K][h][w][hd] ->
+ * cat[k][y][x][0..hd) (pixel stride ldcat; pass the address of the first destination channel).  g4 is read once.  c4 <= 256; every
+ * channel count and stride a multiple of 4, every pointer 16-byte aligned.  Same bits as xmem_conv2d_nhwc (relu_in, no residual) +
+ * xmem_hidden_update_gather + xmem_copy_channels. */
+int xmem_mask_head_gather(const float* g16, int c16, const float* g8, int c8, const float* g4, int c4, const float* w,
+                          const float* scale, const float* shift, const float* hidden, int hd, float* logits, float* g4d,
+                          int ldg4d, float* cat, int ldcat, int K, int h, int wd, void* stream);
+
 /* CBAM (model/cbam.py:21-77) on g [B][P=H*W][C] and the residual add of FeatureFusionBlock
  * (modules.py:36-39): out = g + CBAM(g).  mlp weights as in the checkpoint: w1 [C/16][C], b1, w2 [C][C/16], b2;
  * spatial 7x7 conv weight sw [2][7][7] (channel 0 = max, 1 = mean), bias sb[1].

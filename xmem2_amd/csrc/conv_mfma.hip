@@ -649,6 +649,137 @@ __global__ __launch_bounds__(256) void conv_cout1_row4_kernel(ConvArgs p) {
     }
 }
 
+// The end of the decoder in ONE launch (xmem_mask_head_gather): the mask head, the input of HiddenUpdater's fused pointwise convolution and
+// the hidden-state half of `cat`.  The mask head read relu(g4) through its 3x3 window and hidden_gather_kernel read the same g4 (26.5 MB
+// at 480p, the largest tensor of the tail) again for the 4x4 block means, one launch after the other on the decoder's chain.  A pixel
+// (k, y, x) of the 1/16 map owns one 4x4 block of g4 and of the logits, one 2x2 block of g8 and one pixel of g16: ONE WAVE per such pixel
+// loads the 6x6 patch of g4 around its block once (clamped coordinates, all 36 + 9 weight loads requested together) and makes from it
+//   - area4(g4) from the un-relu'd interior, in hidden_gather_kernel's order (dy, then dx, then one multiply by 1/16),
+//   - the 16 logits, per pixel the products and the order of the additions of conv_cout1_row4_kernel / conv_cout1_kernel (taps 0..8 with
+//     the padding taps skipped, x y z w fma chain, wave_sum, a * scale + shift),
+//   - area4(logits) from its own 16 results (row by row, x y z w, times 1/16),
+// and copies g16, area2(g8) and the hidden state, float4 groups dealt over the lanes, their loads requested BEFORE the first of their stores
+// (a store may alias a later load for all the compiler knows: one round trip per group otherwise).
+// The same bits as conv2d + xmem_hidden_update_gather + xmem_copy_channels; channels of g4d past c16 + c8 + c4 + 1 are not written.
+struct MaskTailArgs {
+    const float *g16, *g8, *g4, *w, *scale, *shift, *hidden;
+    float *logits, *g4d, *cat;
+    int c16, c8, c4, hd, ldg, ldcat, K, h, wd;
+};
+
+__global__ __launch_bounds__(64, 2) void conv_cout1_tail_kernel(MaskTailArgs p) {
+    const int lane = threadIdx.x;
+    const size_t pix = blockIdx.x;                                // (k * h + y) * w + x of the 1/16 map
+    const int x = (int)(pix % p.wd); const size_t ky = pix / p.wd;
+    const int y = (int)(ky % p.h);
+    const int W4 = 4 * p.wd;
+    const int c = lane * 4;
+    const bool act = c < p.c4;
+    // rows / columns 1..4 of the patch are the wave's own block: only the halo can fall outside the map
+    const bool okr0 = y > 0, okr5 = y < p.h - 1, okc0 = x > 0, okc5 = x < p.wd - 1;
+    f32x4 xv[6][6], wv[9];
+    const float sc = p.scale[0], sf = p.shift[0];                 // (read before the first store: after one they could not be scalar loads)
+    if (act) {
+        const float* base = p.g4 + ((4 * ky) * (size_t)W4 + 4 * x) * p.c4 + c;       // the block's first pixel
+        const long rowl = (long)W4 * p.c4;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            const long ro = (r == 0 ? (okr0 ? -1 : 0) : r == 5 ? (okr5 ? 4 : 3) : r - 1) * rowl;
+#pragma unroll
+            for (int cc = 0; cc < 6; ++cc) {
+                const long co = (long)(cc == 0 ? (okc0 ? -1 : 0) : cc == 5 ? (okc5 ? 4 : 3) : cc - 1) * p.c4;
+                xv[r][cc] = *reinterpret_cast<const f32x4*>(base + ro + co);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 9; ++t) wv[t] = *reinterpret_cast<const f32x4*>(p.w + (size_t)t * p.c4 + c);
+    }
+    // [ g16 | area2(g8) ] -> g4d, hidden -> cat: float4 groups dealt over the lanes.  The first 128 groups of g16 and the first 64 of g8 and of
+    // the hidden state (all there are at the served sizes) are straight-line code - every load requested here, the stores further down; a loop
+    // makes each pass wait for the one before it.  What is left over goes group by group at the end of the kernel.
+    const int n16 = p.c16 >> 2, n8 = p.c8 >> 2, nh = p.hd >> 2;
+    float* const o = p.g4d + pix * p.ldg;
+    float* const oh = p.cat + pix * p.ldcat;
+    const float* const s16 = p.g16 + pix * p.c16;
+    const float* const s8 = p.g8 + ((2 * ky) * (size_t)(2 * p.wd) + 2 * x) * p.c8;
+    const float* const sh = p.hidden + pix * p.hd;
+    const size_t row8 = (size_t)(2 * p.wd) * p.c8;
+    const bool a0 = lane < n16, a1 = lane + 64 < n16, b0 = lane < n8, h0 = lane < nh;
+    f32x4 va0, va1, vb[4], vh;
+    if (a0) va0 = *reinterpret_cast<const f32x4*>(s16 + 4 * lane);
+    if (a1) va1 = *reinterpret_cast<const f32x4*>(s16 + 4 * (lane + 64));
+    if (h0) vh = *reinterpret_cast<const f32x4*>(sh + 4 * lane);
+    if (b0) {
+        const float* src = s8 + 4 * lane;
+        vb[0] = *reinterpret_cast<const f32x4*>(src); vb[1] = *reinterpret_cast<const f32x4*>(src + p.c8);
+        vb[2] = *reinterpret_cast<const f32x4*>(src + row8); vb[3] = *reinterpret_cast<const f32x4*>(src + row8 + p.c8);
+    }
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    if (act) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) s += xv[1 + dy][1 + dx];
+        *reinterpret_cast<f32x4*>(p.g4d + pix * p.ldg + p.c16 + p.c8 + c) = s * 0.0625f;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 6; ++cc) {
+                f32x4& v = xv[r][cc];
+                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+            }
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int r = (j >> 2) + t / 3, cc = (j & 3) + t % 3;
+                if ((r == 0 && !okr0) || (r == 5 && !okr5) || (cc == 0 && !okc0) || (cc == 5 && !okc5)) continue;      // a padding tap
+                const f32x4 v = xv[r][cc];
+                acc[j] = fmaf(v.x, wv[t].x, acc[j]); acc[j] = fmaf(v.y, wv[t].y, acc[j]);
+                acc[j] = fmaf(v.z, wv[t].z, acc[j]); acc[j] = fmaf(v.w, wv[t].w, acc[j]);
+            }
+    }
+    // (the copies are stored after the arithmetic: nothing of it then waits for a store to land)
+    if (a0) *reinterpret_cast<f32x4*>(o + 4 * lane) = va0;
+    if (a1) *reinterpret_cast<f32x4*>(o + 4 * (lane + 64)) = va1;
+    if (b0) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        s += vb[0]; s += vb[1]; s += vb[2]; s += vb[3];
+        *reinterpret_cast<f32x4*>(o + p.c16 + 4 * lane) = s * 0.25f;
+    }
+    if (h0) *reinterpret_cast<f32x4*>(oh + 4 * lane) = vh;
+    float lsum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float a = wave_sum(acc[j]);                         // every lane holds the sum
+        acc[j] = a * sc + sf;
+        lsum += acc[j];
+    }
+    if (lane < 4) {                                               // lane dy stores row dy of the block (4 x is a multiple of 4 floats: aligned)
+        f32x4 v;
+        v.x = lane == 0 ? acc[0] : lane == 1 ? acc[4] : lane == 2 ? acc[8] : acc[12];
+        v.y = lane == 0 ? acc[1] : lane == 1 ? acc[5] : lane == 2 ? acc[9] : acc[13];
+        v.z = lane == 0 ? acc[2] : lane == 1 ? acc[6] : lane == 2 ? acc[10] : acc[14];
+        v.w = lane == 0 ? acc[3] : lane == 1 ? acc[7] : lane == 2 ? acc[11] : acc[15];
+        *reinterpret_cast<f32x4*>(p.logits + (4 * ky + lane) * (size_t)W4 + 4 * x) = v;
+    }
+    if (lane == 4) p.g4d[pix * p.ldg + p.c16 + p.c8 + p.c4] = lsum * 0.0625f;
+    // the left-over groups of wider tensors (none at the served sizes)
+    for (int g = lane + 128; g < n16; g += 64) *reinterpret_cast<f32x4*>(o + 4 * g) = *reinterpret_cast<const f32x4*>(s16 + 4 * g);
+    for (int g = lane + 64; g < n8; g += 64) {
+        const float* src = s8 + 4 * g;
+        const f32x4 q0 = *reinterpret_cast<const f32x4*>(src), q1 = *reinterpret_cast<const f32x4*>(src + p.c8);
+        const f32x4 q2 = *reinterpret_cast<const f32x4*>(src + row8), q3 = *reinterpret_cast<const f32x4*>(src + row8 + p.c8);
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        s += q0; s += q1; s += q2; s += q3;
+        *reinterpret_cast<f32x4*>(o + p.c16 + 4 * g) = s * 0.25f;
+    }
+    for (int g = lane + 64; g < nh; g += 64) *reinterpret_cast<f32x4*>(oh + 4 * g) = *reinterpret_cast<const f32x4*>(sh + 4 * g);
+}
+
 // ----------------------------------------------------------------------------------------------
 // Winograd F(2x2, 3x3) for the 3x3 / stride 1 / pad 1 convolutions (85 % of the network's FLOPs):
 //   Y = A^T [ (G g G^T) .* (B^T d B) ] A      (Lavin & Gray) - 16 multiplies per 2x2 outputs instead of 36.
@@ -1701,6 +1832,24 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
     }
 #endif
     return pl.splitk > 1 ? launch_splitk_reduce(a, half == 2, s) : rc;
+}
+
+extern "C" int xmem_mask_head_gather(const float* g16, int c16, const float* g8, int c8, const float* g4, int c4, const float* w,
+                                     const float* scale, const float* shift, const float* hidden, int hd, float* logits, float* g4d,
+                                     int ldg4d, float* cat, int ldcat, int K, int h, int wd, void* stream) {
+    if (!g16 || !g8 || !g4 || !w || !scale || !shift || !hidden || !logits || !g4d || !cat) return XMEM_ERR_BAD_ARG;
+    if (K <= 0 || h <= 0 || wd <= 0 || c16 <= 0 || c8 <= 0 || c4 <= 0 || hd <= 0) return XMEM_ERR_BAD_ARG;
+    if (c16 % 4 || c8 % 4 || c4 % 4 || hd % 4 || ldg4d % 4 || ldcat % 4 || c4 > 256) return XMEM_ERR_UNSUPPORTED;    // one float4 of g4 per lane
+    if (ldg4d < c16 + c8 + c4 + 1 || ldcat < hd) return XMEM_ERR_UNSUPPORTED;
+    if (((uintptr_t)g16 | (uintptr_t)g8 | (uintptr_t)g4 | (uintptr_t)w | (uintptr_t)hidden | (uintptr_t)logits | (uintptr_t)g4d | (uintptr_t)cat) & 15)
+        return XMEM_ERR_UNSUPPORTED;
+    if ((double)K * h * wd >= 2.0e9 / 16) return XMEM_ERR_UNSUPPORTED;            // one workgroup per 1/16 pixel; 16 logits each
+    MaskTailArgs a;
+    a.g16 = g16; a.g8 = g8; a.g4 = g4; a.w = w; a.scale = scale; a.shift = shift; a.hidden = hidden;
+    a.logits = logits; a.g4d = g4d; a.cat = cat;
+    a.c16 = c16; a.c8 = c8; a.c4 = c4; a.hd = hd; a.ldg = ldg4d; a.ldcat = ldcat; a.K = K; a.h = h; a.wd = wd;
+    hipLaunchKernelGGL(conv_cout1_tail_kernel, dim3(K * h * wd), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return xmem_check_launch();
 }
 
 // ----------------------------------------------------------------------------------------------

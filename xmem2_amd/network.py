@@ -28,6 +28,10 @@ def _pad4(n):
 
 # captured HIP-graph stages kept before the least recently replayed one is dropped
 MAX_STAGES = 160
+# 1/16-resolution pixels (objects x h x w) from which the decoder's tail runs as ops.mask_head_gather - one wave per such pixel: below,
+# too few waves to cover the latency of their loads, the mask head, hidden_update_gather and copy_channels stay three launches
+# (NOT MEASURED yet: placed between the 240p map, 405 pixels, and the 480p one, 1 620; profiles/r07_decoder_tail.txt)
+FUSED_TAIL_MIN_PIXELS = 512
 
 
 def _padc(n):
@@ -46,6 +50,11 @@ class XMem:
         self._cbam = {}
         # launch-bound stages (61 convolutions + ~40 small kernels per frame) are replayed as HIP graphs
         self.use_graphs = os.environ.get('XMEM_HIP_GRAPHS', '1') != '0'
+        # the decoder's tail: mask head + HiddenUpdater input + hidden copy in one launch (ops.mask_head_gather) and the fused hidden-update
+        # convolution's Cin padded to a multiple of 32 (the 1x1 operand loader).  XMEM_FUSED_TAIL=0 (or fused_tail = False BEFORE the
+        # weights are uploaded) keeps the separate launches and the unpadded filters: an A/B switch, bit-identical either way
+        self.fused_tail = os.environ.get('XMEM_FUSED_TAIL', '1') != '0'
+        self.fused_tail_min_pixels = FUSED_TAIL_MIN_PIXELS
         # 'fp32' (default: the parity contract) | 'fp16' (opt-in: the fp16 loop - half activations in HBM, half-operand convolutions
         # on the fp16 MFMA with fp32 accumulation: the counterpart of the reference's autocast loop, run_on_video.py:76; the
         # permanent-memory preload stays fp32 as in run_on_video.py:59-66) | 'fp16w' / 'fp32x' (experiments, ops.PRECISIONS)
@@ -225,7 +234,14 @@ class XMem:
             # split-K reductions (44 -> ~20 us per frame at 480p).  Same products; the sum runs over one chain instead of three.
             parts = [W['decoder.hidden_update.' + n] for n in ('g16_conv', 'g8_conv', 'g4_conv')]
             if all(float((p.scale - 1).abs().max()) == 0.0 for p in parts):
-                wk = torch.cat([p.w for p in parts], 3).contiguous()
+                wk = torch.cat([p.w for p in parts], 3)
+                if self.fused_tail and wk.shape[3] % 32:
+                    # zero filter columns up to a multiple of the 32-deep k-tile (1028 -> 1056): the convolution takes the 1x1 operand
+                    # loader instead of the general one (per-tile index arithmetic, masked loads).  As many k-tiles as before, and the
+                    # general loader's masked tail was a run of zero operands too: the same bits under the same plan.  The input buffer
+                    # (segment_nhwc: zero-initialised scratch as wide as this Cin) keeps zeros in the padding channels.
+                    wk = torch.nn.functional.pad(wk, (0, 32 - wk.shape[3] % 32))
+                wk = wk.contiguous()
                 W['decoder.hidden_update.g_fused'] = ConvWeights(wk, parts[0].scale, (parts[0].shift + parts[1].shift + parts[2].shift).contiguous(),
                                                                  1, 0, cin_true=sum(p.cin_true for p in parts))
         W['decoder.up_16_8.skip_conv'] = self._conv_w('decoder.up_16_8.skip_conv', None, 1, 1)
@@ -577,11 +593,21 @@ class XMem:
         g8 = self._group_res(ops.upsample2x_add(g16, skip8), 'decoder.up_16_8.out_conv')
         skip4 = skips[1] if skips is not None else ops.conv2d(f4, W['decoder.up_8_4.skip_conv'])
         g4 = self._group_res(ops.upsample2x_add(g8, skip4), 'decoder.up_8_4.out_conv')
+        gf = W.get('decoder.hidden_update.g_fused') if h_out and hd > 0 else None
+        if self.fused_tail and gf is not None and g4d is not None and g4d.shape[3] == gf.cin and K * h * w >= self.fused_tail_min_pixels \
+                and hidden.shape[3] == hd:
+            # mask head, HiddenUpdater input and the hidden half of `cat` in one launch that reads g4 once (the same bits as the calls below)
+            mid = gf.cout
+            cat = torch.empty((K, h, w, mid + hd), dtype=torch.float32, device=g4.device)
+            if ops.mask_head_gather_ok(g16, g8, g4, W['decoder.pred'], hidden, g4d, cat, mid):
+                logits = ops.mask_head_gather(g16, g8, g4, W['decoder.pred'], hidden, g4d, cat, mid)
+                ops.conv2d(g4d, gf, out=cat, out_ld=cat.shape[3])           # writes the disjoint [:mid]
+                values = ops.conv2d(cat, W['decoder.hidden_update.transform'])
+                return ops.gru_gate(values, hidden, out=hidden), logits
         logits = ops.conv2d(g4, W['decoder.pred'], relu_in=True, out_dtype=torch.float32)          # [K,4h,4w,1], fp32 in every mode
         new_hidden = None
         if h_out and hd > 0:
             c4 = g4.shape[3]
-            gf = W.get('decoder.hidden_update.g_fused')
             if g4d is None:
                 g4d = self._zero_scratch((K, h, w, _padc(c4 + 1)), g4.device, ops.act_dtype())
             if gf is not None and g4d.shape[3] == gf.cin and g4d.dtype == torch.float32:
@@ -596,7 +622,7 @@ class XMem:
                     ops.area_downsample(logits, 4, out=g4d, out_ld=ld, out_off=c16 + c8 + c4)
                 mid = gf.cout
                 cat = torch.empty((K, h, w, mid + hd), dtype=ops.act_dtype(), device=g4.device)
-                ops.conv2d(g4d, gf, out=cat, out_ld=cat.shape[3])
+                ops.conv2d(g4d, gf, out=cat, out_ld=cat.shape[3], plan=self._unpadded_g_fused_plan(gf, K, h, w, cat.shape[3]))
             else:
                 ops.area_downsample(g4, 4, out=g4d, out_ld=g4d.shape[3])
                 ops.area_downsample(logits, 4, out=g4d, out_ld=g4d.shape[3], out_off=c4)
@@ -610,6 +636,17 @@ class XMem:
             values = ops.conv2d(cat, W['decoder.hidden_update.transform'])
             new_hidden = ops.gru_gate(values, hidden, out=hidden)          # in place: the state tensor itself advances
         return new_hidden, logits
+
+    @staticmethod
+    def _unpadded_g_fused_plan(gf, K, h, w, out_ld):
+        """The plan table lists the fused hidden-update convolution under its padded Cin (fused_tail, the default).  With the padding
+        switched off the layer runs under that same entry - the same tile and split-K, so the same summation order: the switch
+        changes no bit, and both of its sides are measured under the tuned plan.  None: the usual choice (conv_plan.choose)."""
+        from . import conv_plan
+        if gf.cin % 32 == 0 or ops._PRECISION != 'fp32' or conv_plan.CONV_FORM or conv_plan.AUTOTUNE:
+            return None
+        cp = (gf.cin + 31) // 32 * 32
+        return conv_plan.FP32.get(f'{K}x{h}x{w}x{cp}/{cp}->{gf.cout}/{out_ld} k1s1p0 r000')
 
     # ---- reference-shaped wrappers (NCHW in / out) ----------------------------------------------
     @staticmethod

@@ -542,6 +542,45 @@ def hidden_update_gather(g16, g8, g4, logits, out):
     return out
 
 
+def mask_head_gather_ok(g16, g8, g4, cw, hidden, g4d, cat, cat_off):
+    """True when `mask_head_gather` takes these tensors: float32 mode, contiguous float32 NHWC tensors of one decoder pass, a 3x3 /
+    stride 1 / pad 1 mask head over at most 256 channels, 4-float channel counts and offsets."""
+    ts = (g16, g8, g4, hidden, g4d, cat)
+    if _PRECISION != 'fp32' or any(t is None or t.dtype != torch.float32 or not t.is_contiguous() for t in ts):
+        return False
+    K, h, w, c16 = g16.shape
+    c8, c4, hd = g8.shape[3], g4.shape[3], hidden.shape[3]
+    return (tuple(g8.shape[:3]) == (K, 2 * h, 2 * w) and tuple(g4.shape[:3]) == (K, 4 * h, 4 * w)
+            and tuple(hidden.shape[:3]) == (K, h, w) and tuple(g4d.shape[:3]) == (K, h, w) and tuple(cat.shape[:3]) == (K, h, w)
+            and (cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, cw.dilation, cw.cin) == (1, 3, 3, 1, 1, 1, c4) and c4 <= 256
+            and not (c16 % 4 or c8 % 4 or c4 % 4 or hd % 4 or cat_off % 4 or cat.shape[3] % 4 or g4d.shape[3] % 4)
+            and g4d.shape[3] >= c16 + c8 + c4 + 1 and cat_off + hd <= cat.shape[3])
+
+
+def mask_head_gather(g16, g8, g4, cw, hidden, g4d, cat, cat_off):
+    """The end of the decoder in one launch, g4 read once: logits = conv2d(g4, cw, relu_in=True) (the mask head `cw`: 3x3, Cout 1),
+    g4d[..., :c16+c8+c4+1] = [g16 | area2(g8) | area4(g4) | area4(logits)] and cat[..., cat_off:cat_off+hd] = hidden.  The same bits
+    as conv2d + hidden_update_gather + copy_channels.  Returns logits [K,4h,4w,1]."""
+    if not mask_head_gather_ok(g16, g8, g4, cw, hidden, g4d, cat, cat_off):
+        raise RuntimeError('mask_head_gather: float32 mode, contiguous float32 tensors of one decoder pass and a 3x3 mask head over <= 256 channels only')
+    K, h, w, c16 = g16.shape
+    c8, c4, hd = g8.shape[3], g4.shape[3], hidden.shape[3]
+    logits = torch.empty((K, 4 * h, 4 * w, 1), dtype=torch.float32, device=g4.device)
+    dst = C.c_void_p(cat.data_ptr() + 4 * cat_off)
+    launch = lambda: load().xmem_mask_head_gather(ptr(g16), c16, ptr(g8), c8, ptr(g4), c4, ptr(cw.w), ptr(cw.scale), ptr(cw.shift),
+                                                  ptr(hidden), hd, ptr(logits), ptr(g4d), g4d.shape[3], dst, cat.shape[3], K, h, w,
+                                                  stream_ptr())
+    check(launch())
+    if RECORD is not None:
+        # the mask head's own entry (key, FLOPs, plan) as conv2d writes it: the survey of the convolutions still counts the layer
+        H, W = 4 * h, 4 * w
+        key = f'{K}x{H}x{W}x{c4}/{c4}->1/1 k3s1p1 r010'
+        RECORD.append(('conv', key, 2.0 * K * H * W * 9 * cw.cin_true, launch,
+                       (g4, logits, None, cw, None, dict(relu_in=True, relu_out=False, in_ld=c4, cin=c4, out_ld=1, res_broadcast=False,
+                                                         plan=(conv_plan.HEURISTIC, 0), executed_mfma_flops=0.0))))
+    return logits
+
+
 def cbam_residual(g, p):
     """out = g + CBAM(g); p = dict(w1,b1,w2,b2,sw,sb) device tensors (float32); g float32 or float16."""
     lib = load()
