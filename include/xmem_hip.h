@@ -40,8 +40,8 @@ typedef enum {
 
 /* ABI version of this header.  2 (round 4): xmem_conv_desc grew (in_half / out_half / w_half), storage-typed `_t` entry points, plan
  * tiles 23..40.  3 (round 5): no layout change, but the MEANING of w_winograd4 / w_winograd4_split changed - the F(4x4) transforms use the
- * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
-#define XMEM_ABI_VERSION 4
+ * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
+#define XMEM_ABI_VERSION 5
 int xmem_version(void);
 const char* xmem_last_error_string(int code); /* static string for a status code */
 
@@ -342,6 +342,64 @@ int xmem_s2m_output(const float* logits, int K, int h4, int w4, int H, int W, in
 /* aggregate_wbg(prob, keep_bg, hard) of interaction.py:36-51 on its own: prob [K][H][W] -> out [K+1][H][W] (keep_bg) or [K][H][W]
  * (nullable), mask (nullable) = first-index argmax over the K + 1 softmax values; temperature 1 (hard=False) or 1000 (hard=True). */
 int xmem_aggregate_wbg(const float* prob, int K, int H, int W, int keep_bg, float temperature, float* out, uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Click-to-mask (the f-BRS click network with the NoBRS predictor: inference/interact/fbrs_controller.py, fbrs/model/
+ * is_deeplab_model.py, fbrs/inference/predictors/base.py, fbrs/inference/transforms/) around its convolutions.  All fp32.
+ * "align_corners" below is F.interpolate(mode='bilinear', align_corners=True): output index o of n_out reads the source
+ * coordinate o (n_in - 1) / (n_out - 1), 0 when n_out == 1; the cell index and the weight come from the integer quotient and
+ * remainder, so equal sizes copy bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+/* Network input of both samples of AddHorizontalFlip in one launch (transforms/flip.py:8-21, DistMaps in cpu mode: fbrs/model/ops.py:
+ * 46-53, 78 with utils/cython/_get_dist_maps.pyx, then rgb_conv: is_deeplab_model.py:36-41, 54).
+ *   image   [3][H][W] at the network's working size
+ *   clicks  [2][cap][2] (row, col) floats, positive clicks first; counts [2] int32 ON THE DEVICE (so that a captured graph serves any
+ *           number of clicks), each clamped to [0, cap]
+ *   out     [B][H][W][8] NHWC, B = with_flip ? 2 : 1, channels 3..7 zero; sample 1 is the horizontally mirrored image with the click
+ *           columns (W - 1) - col
+ *   features (nullable) [B][2][H][W]: the two distance features
+ * Per pixel and polarity d = min_i ((r - rint(r_i)) / radius)^2 + ((c - rint(c_i)) / radius)^2 (rint: half to even), feature =
+ * tanh(2 sqrt(d)), d = 1e6 (feature exactly 1) without a valid click.  A click whose rounded row is negative is ignored as in the
+ * reference (its padding is (-1, -1)); a click otherwise outside the map is ignored too (the reference writes out of bounds there).
+ * rgb_conv: 75 floats w1 [8][5], b1 [8], w2 [3][8], b2 [3] = Conv2d(5, 8, 1) -> LeakyReLU(0.2) -> Conv2d(8, 3, 1) with the BatchNorm
+ * between them folded into w2 / b2 by the caller. */
+int xmem_click_input(const float* image, const float* clicks, int cap, const int32_t* counts, float radius, const float* rgb_conv,
+                     int H, int W, int with_flip, float* out, float* features, void* stream);
+
+/* Depthwise 3x3, pad 1, stride 1, no bias (SeparableConv2d.body[0], fbrs/model/modeling/basic_blocks.py:63-64): in [B][H][W][ldin] ->
+ * out [B][H][W][ldout], first C channels of each; w [9][C] (tap-major).  The pointwise convolution that follows carries BatchNorm and
+ * ReLU in xmem_conv2d_nhwc's epilogue.  C, ldin, ldout multiples of 4, 16-byte aligned pointers. */
+int xmem_depthwise3x3_nhwc(const float* in, int ldin, const float* w, float* out, int ldout, int B, int H, int W, int C, void* stream);
+
+/* align_corners resize on NHWC into a channel slice (DeepLabV3Plus.forward, fbrs/model/modeling/deeplab_v3.py:77-78): shapes and
+ * constraints as xmem_resize_bilinear_nhwc. */
+int xmem_resize_bilinear_ac_nhwc(const float* in, int ldin, int B, int Hi, int Wi, int C, float* out, int ldout, int Ho, int Wo, void* stream);
+
+/* align_corners resize on planar maps with a source crop and a destination paste: rows [r0, r0 + Hc) x columns [c0, c0 + Wc) of
+ * in [C][Hi][Wi] resized to Hd x Wd and written at (pr0, pc0) of out [C][Ho][Wo]; zero_fill = 1 writes zeros to the rest of out, 0
+ * leaves it untouched.  get_roi_image_nd and ZoomIn.inv_transform (transforms/zoom_in.py:142-160, 65-83). */
+int xmem_resize_bilinear_ac(const float* in, int C, int Hi, int Wi, int r0, int c0, int Hc, int Wc,
+                            float* out, int Ho, int Wo, int pr0, int pc0, int Hd, int Wd, int zero_fill, void* stream);
+
+/* Network output: logits [B][h4][w4] (B = with_flip ? 2 : 1) -> prob [H][W] = sigmoid(mean of the align_corners upsample of sample 0
+ * and the mirrored upsample of sample 1).  The flip's inverse averages LOGITS: it is the last transform, so its inverse runs before
+ * SigmoidForPred's (predictors/base.py:21-26, 46-47; is_deeplab_model.py:63-64). */
+int xmem_click_prob(const float* logits, int h4, int w4, int H, int W, int with_flip, float* prob, void* stream);
+
+/* get_bbox_from_mask of prob > threshold (fbrs/utils/misc.py:19-25; prob [H][W]): out = {rmin, rmax, cmin, cmax, count} int32, the box
+ * {INT_MAX, -1, INT_MAX, -1} when nothing is set.  click_pixels (nullable) [n_clicks][2] int32 (row, col) join the box but not the
+ * count, as get_object_roi adds the positive clicks after its caller tested the mask's sum (transforms/zoom_in.py:41-44, 130-132).
+ * ZoomIn then moves 20 bytes to the host instead of the map.  Exact and order-independent. */
+int xmem_mask_bbox(const float* prob, int H, int W, float threshold, const int32_t* click_pixels, int n_clicks, int32_t* out, void* stream);
+
+/* out[i] = prob[i] > threshold ? 1 : 0, n floats: the mask FBRSController.interact returns (inference/interact/fbrs_controller.py:46) */
+int xmem_prob_threshold(const float* prob, size_t n, float threshold, float* out, void* stream);
+
+/* ClickInteraction.predict (inference/interact/interaction.py:247-254): prev_prob [K+1][H][W] clamped to <= 0.9, row tar_obj
+ * (1..K) replaced by obj_mask [H][W], then aggregate_wbg(.[1:], keep_bg=True) with `temperature` as xmem_aggregate_wbg ->
+ * out [K+1][H][W] (nullable, must not alias prev_prob) and mask [H][W] uint8 (nullable) = its first-index argmax. */
+int xmem_click_commit(const float* prev_prob, const float* obj_mask, int K, int H, int W, int tar_obj, float temperature,
+                      float* out, uint8_t* mask, void* stream);
 
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);

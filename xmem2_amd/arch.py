@@ -145,3 +145,46 @@ def s2m_state_dict_spec():
     _bn(spec, 'classifier.classifier.1', 256)
     _conv(spec, 'classifier.classifier.3', 1, 256, 1, True)
     return spec
+
+
+def _separable(spec, prefix, cin, cout):
+    """SeparableConv2d (fbrs/model/modeling/basic_blocks.py:57-71): depthwise 3x3, pointwise 1x1, BN (ReLU has no tensors)."""
+    spec[prefix + '.body.0.weight'] = (cin, 1, 3, 3)
+    _conv(spec, prefix + '.body.1', cout, cin, 1, False)
+    _bn(spec, prefix + '.body.2', cout)
+
+
+def click_state_dict_spec(deeplab_ch=128):
+    """The 413 tensors of the click network, get_deeplab_model(backbone='resnet50', deeplab_ch) (inference/interact/fbrs/model/
+    is_deeplab_model.py:9-48): rgb_conv, then DeepLabV3Plus (fbrs/model/modeling/deeplab_v3.py:36-46: backbone = ResNet-50-v1s with a
+    three-convolution stem, resnetv1b.py:121-146, 240-241; head, skip_project, aspp in that registration order), then the
+    SepConvHead (basic_blocks.py:27-54), in state_dict order.  The dilations of layer3 / layer4 add no tensors."""
+    ch = int(deeplab_ch)
+    spec = OrderedDict()
+    _conv(spec, 'rgb_conv.0', 8, 5, 1, True)
+    _bn(spec, 'rgb_conv.2', 8)
+    _conv(spec, 'rgb_conv.3', 3, 8, 1, True)
+    bb = 'feature_extractor.backbone.'
+    _conv(spec, bb + 'conv1.0', 64, 3, 3, False); _bn(spec, bb + 'conv1.1', 64)
+    _conv(spec, bb + 'conv1.3', 64, 64, 3, False); _bn(spec, bb + 'conv1.4', 64)
+    _conv(spec, bb + 'conv1.6', 128, 64, 3, False)
+    _bn(spec, bb + 'bn1', 128)
+    c = _bottleneck_layer(spec, bb + 'layer1', 128, 64, 3, 1)
+    c = _bottleneck_layer(spec, bb + 'layer2', c, 128, 4, 2)
+    c = _bottleneck_layer(spec, bb + 'layer3', c, 256, 6, 1)
+    c = _bottleneck_layer(spec, bb + 'layer4', c, 512, 3, 1)
+    fe = 'feature_extractor.'
+    _separable(spec, fe + 'head.block.0', ch + 32, ch)
+    _separable(spec, fe + 'head.block.1', ch, ch)
+    _conv(spec, fe + 'head.block.2', ch, ch, 1, True)
+    _conv(spec, fe + 'skip_project.skip_project.0', 32, 256, 1, False)
+    _bn(spec, fe + 'skip_project.skip_project.1', 32)
+    _conv(spec, fe + 'aspp.concurent.0.0', ch, c, 1, False); _bn(spec, fe + 'aspp.concurent.0.1', ch)
+    for i in (1, 2, 3):
+        _conv(spec, fe + f'aspp.concurent.{i}.0', ch, c, 3, False); _bn(spec, fe + f'aspp.concurent.{i}.1', ch)
+    _conv(spec, fe + 'aspp.concurent.4.gap.1', ch, c, 1, False); _bn(spec, fe + 'aspp.concurent.4.gap.2', ch)
+    _conv(spec, fe + 'aspp.project.0', ch, 5 * ch, 1, False); _bn(spec, fe + 'aspp.project.1', ch)
+    _separable(spec, 'head.layers.0', ch, ch // 2)
+    _separable(spec, 'head.layers.1', ch // 2, ch // 2)
+    _conv(spec, 'head.layers.2', 1, ch // 2, 1, True)
+    return spec

@@ -1004,24 +1004,29 @@ extern "C" int xmem_resize_bilinear_nhwc(const float* in, int ldin, int B, int H
 //   new = clamp(cat(prod_k (1 - p_k), p), 1e-7, 1 - 1e-7); l = log(new / (1 - new)) * temp; softmax over the K + 1 channels
 // written to out[c * ostride] for c = first .. K (first = 0: keep_bg; 1: without the background row, at out[(c - 1) * ostride]);
 // arg (nullable) = first index of the largest of the K + 1 softmax values, as torch.argmax
-__device__ __forceinline__ void wbg_pixel(const float* p, size_t stride, int K, float temp, int first, float* out, size_t ostride,
-                                          uint8_t* arg) {
+template <typename Load>
+__device__ __forceinline__ void wbg_pixel_of(Load p, int K, float temp, int first, float* out, size_t ostride, uint8_t* arg) {
     float bg = 1.f, mx;
-    for (int k = 0; k < K; ++k) bg *= (1.f - p[k * stride]);
+    for (int k = 0; k < K; ++k) bg *= (1.f - p(k));
     const float l0 = agg_logit(bg) * temp;
     mx = l0;
-    for (int k = 0; k < K; ++k) mx = fmaxf(mx, agg_logit(p[k * stride]) * temp);
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, agg_logit(p(k)) * temp);
     const float e0 = expf(l0 - mx);
     float den = e0;
-    for (int k = 0; k < K; ++k) den += expf(agg_logit(p[k * stride]) * temp - mx);
+    for (int k = 0; k < K; ++k) den += expf(agg_logit(p(k)) * temp - mx);
     float best = e0 / den; int bi = 0;
     if (first == 0 && out) out[0] = best;
     for (int k = 0; k < K; ++k) {
-        const float v = expf(agg_logit(p[k * stride]) * temp - mx) / den;
+        const float v = expf(agg_logit(p(k)) * temp - mx) / den;
         if (out) out[(size_t)(k + 1 - first) * ostride] = v;
         if (v > best) { best = v; bi = k + 1; }
     }
     if (arg) *arg = (uint8_t)bi;
+}
+
+__device__ __forceinline__ void wbg_pixel(const float* p, size_t stride, int K, float temp, int first, float* out, size_t ostride,
+                                          uint8_t* arg) {
+    wbg_pixel_of([=](int k) { return p[k * stride]; }, K, temp, first, out, ostride, arg);
 }
 
 // S2M output: logits [K][h4][w4] (the 1/4-resolution head) -> prob [K][H][W] = unpad(sigmoid(bilinear x4)) (s2m/utils.py:15-20,
@@ -1059,5 +1064,27 @@ extern "C" int xmem_aggregate_wbg(const float* prob, int K, int H, int W, int ke
     if (!prob || (!out && !mask) || K <= 0 || K > 254 || H <= 0 || W <= 0 || !(temperature > 0.f)) return XMEM_ERR_BAD_ARG;
     hipLaunchKernelGGL(aggregate_wbg_kernel, dim3(grid_for((size_t)H * W)), dim3(256), 0, (hipStream_t)stream,
                        prob, K, (size_t)H * W, temperature, keep_bg, out, mask);
+    return xmem_check_launch();
+}
+
+// ClickInteraction.predict (inference/interact/interaction.py:247-254): prev [K+1][H][W] clamped to <= 0.9, row tar_obj replaced by the
+// click mask obj [H][W], then aggregate_wbg(.[1:], keep_bg=True, hard) -> out [K+1][H][W] (nullable) and its argmax (nullable).
+// out may not alias prev: row 0 of out is written before the other rows of prev are read again.
+__global__ void click_commit_kernel(const float* __restrict__ prev, const float* __restrict__ obj, int K, size_t P, int tar, float temp,
+                                    float* __restrict__ out, uint8_t* __restrict__ arg) {
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (size_t)gridDim.x * blockDim.x) {
+        const float* p = prev + P + e;
+        const float o = obj[e];
+        wbg_pixel_of([=](int k) { return k + 1 == tar ? o : fminf(p[k * P], 0.9f); }, K, temp, 0, out ? out + e : nullptr, P,
+                     arg ? arg + e : nullptr);
+    }
+}
+
+extern "C" int xmem_click_commit(const float* prev_prob, const float* obj_mask, int K, int H, int W, int tar_obj, float temperature,
+                                 float* out, uint8_t* mask, void* stream) {
+    if (!prev_prob || !obj_mask || (!out && !mask) || K <= 0 || K > 254 || H <= 0 || W <= 0 || !(temperature > 0.f)) return XMEM_ERR_BAD_ARG;
+    if (tar_obj < 1 || tar_obj > K || out == prev_prob) return XMEM_ERR_BAD_ARG;
+    hipLaunchKernelGGL(click_commit_kernel, dim3(grid_for((size_t)H * W)), dim3(256), 0, (hipStream_t)stream,
+                       prev_prob, obj_mask, K, (size_t)H * W, tar_obj, temperature, out, mask);
     return xmem_check_launch();
 }

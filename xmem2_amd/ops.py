@@ -1008,3 +1008,123 @@ def aggregate_wbg(prob, keep_bg=False, temperature=1.0, want_mask=False):
     check(load().xmem_aggregate_wbg(ptr(prob.contiguous()), K, H, W, int(bool(keep_bg)), float(temperature), ptr(out), ptr(mask),
                                     stream_ptr()))
     return (out, mask) if want_mask else out
+
+
+# ---- click-to-mask (the f-BRS click network) --------------------------------------------------------------------
+
+def click_input(image, clicks, counts, rgb_conv, radius=260.0, with_flip=True, out=None, want_features=False):
+    """image [3,H,W] at the working size, clicks [2,cap,2] float (row, col; positives first), counts [2] int32 (device), rgb_conv
+    [75] (w1 [8,5], b1 [8], w2 [3,8], b2 [3], BatchNorm folded) -> the network input [B,H,W,8] NHWC, B = 2 with_flip (sample 1:
+    mirrored image and clicks); with want_features also the distance features [B,2,H,W]."""
+    _req(image, 'image'); _req(clicks, 'clicks'); _req(rgb_conv, 'rgb_conv')
+    if not counts.is_cuda or counts.dtype != torch.int32 or counts.numel() != 2:
+        raise RuntimeError('click_input: counts must be two int32 on the device')
+    if clicks.dim() != 3 or clicks.shape[0] != 2 or clicks.shape[2] != 2 or not clicks.is_contiguous():
+        raise RuntimeError(f'click_input: clicks must be a contiguous [2, cap, 2] tensor, got {tuple(clicks.shape)}')
+    if image.dim() != 3 or image.shape[0] != 3 or rgb_conv.numel() != 75:
+        raise RuntimeError('click_input: expected an image [3,H,W] and 75 rgb_conv parameters')
+    image = image.contiguous()
+    H, W = image.shape[-2:]
+    B = 2 if with_flip else 1
+    if out is None:
+        out = torch.empty((B, H, W, 8), dtype=torch.float32, device=image.device)
+    feat = torch.empty((B, 2, H, W), dtype=torch.float32, device=image.device) if want_features else None
+    check(load().xmem_click_input(ptr(image), ptr(clicks), clicks.shape[1], ptr(counts), float(radius), ptr(rgb_conv.contiguous()),
+                                  H, W, int(bool(with_flip)), ptr(out), ptr(feat), stream_ptr()))
+    return (out, feat) if want_features else out
+
+
+def depthwise3x3(x, w, out=None):
+    """Depthwise 3x3 (pad 1, stride 1, no bias) on NHWC x [B,H,W,C] (pixel stride x.stride(2)) with w [9,C] -> out [B,H,W,C]
+    (may be a channel slice of a wider buffer)."""
+    B, H, W, Cc = _req(x, 'depthwise3x3 input').shape
+    if tuple(_req(w, 'depthwise3x3 weight').shape) != (9, Cc) or not w.is_contiguous():
+        raise RuntimeError(f'depthwise3x3: weight must be a contiguous [9, {Cc}] tensor, got {tuple(w.shape)}')
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, H, W, Cc):
+        raise RuntimeError(f'depthwise3x3: out has shape {tuple(out.shape)}, expected {(B, H, W, Cc)}')
+    check(load().xmem_depthwise3x3_nhwc(ptr(x), x.stride(2), ptr(w), ptr(out), out.stride(2), B, H, W, Cc, stream_ptr()))
+    return out
+
+
+def resize_bilinear_ac_nhwc(x, shape, out=None):
+    """F.interpolate(x, size=shape, mode='bilinear', align_corners=True) on NHWC, otherwise as resize_bilinear_nhwc."""
+    B, Hi, Wi, Cc = _req(x, 'resize_bilinear_ac_nhwc input').shape
+    Ho, Wo = int(shape[0]), int(shape[1])
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cc), dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != (B, Ho, Wo, Cc):
+        raise RuntimeError(f'resize_bilinear_ac_nhwc: out has shape {tuple(out.shape)}, expected {(B, Ho, Wo, Cc)}')
+    check(load().xmem_resize_bilinear_ac_nhwc(ptr(x), x.stride(2), B, Hi, Wi, Cc, ptr(out), out.stride(2), Ho, Wo, stream_ptr()))
+    return out
+
+
+def resize_bilinear_ac(x, size, crop=None, out=None, paste=None, zero_fill=False):
+    """align_corners=True bilinear resize of planar x [C,Hi,Wi].  crop = (rmin, rmax, cmin, cmax), inclusive as the reference's ROIs: the
+    source rectangle (default: all of x).  Without `out` the result is [C, size]; with out [C,Ho,Wo] and paste = (rmin, rmax, cmin,
+    cmax) the crop is resized to the paste rectangle's size and written there, zeros elsewhere with zero_fill."""
+    Cc, Hi, Wi = _req(x, 'resize_bilinear_ac input').shape
+    x = x.contiguous()
+    r0, r1, c0, c1 = (0, Hi - 1, 0, Wi - 1) if crop is None else [int(v) for v in crop]
+    if out is None:
+        Hd, Wd = int(size[0]), int(size[1])
+        out = torch.empty((Cc, Hd, Wd), dtype=torch.float32, device=x.device)
+        pr0, pc0 = 0, 0
+    else:
+        if out.dim() != 3 or out.shape[0] != Cc or not out.is_contiguous() or paste is None:
+            raise RuntimeError('resize_bilinear_ac: out must be a contiguous [C,Ho,Wo] tensor given together with paste')
+        pr0, pr1, pc0, pc1 = [int(v) for v in paste]
+        Hd, Wd = pr1 - pr0 + 1, pc1 - pc0 + 1
+    check(load().xmem_resize_bilinear_ac(ptr(x), Cc, Hi, Wi, r0, c0, r1 - r0 + 1, c1 - c0 + 1, ptr(_req(out, 'out')), out.shape[1],
+                                         out.shape[2], pr0, pc0, Hd, Wd, int(bool(zero_fill)), stream_ptr()))
+    return out
+
+
+def click_prob(logits, H, W, out=None):
+    """logits [B,h4,w4] (B = 2: plain and mirrored sample) -> prob [H,W] = sigmoid of the (flip-averaged) align_corners upsample."""
+    B, h4, w4 = _req(logits, 'logits').shape
+    if B not in (1, 2) or not logits.is_contiguous():
+        raise RuntimeError(f'click_prob: expected contiguous logits [1 or 2, h4, w4], got {tuple(logits.shape)}')
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=logits.device)
+    check(load().xmem_click_prob(ptr(logits), h4, w4, int(H), int(W), int(B == 2), ptr(out), stream_ptr()))
+    return out
+
+
+def mask_bbox(prob, threshold=0.5, click_pixels=None, out=None):
+    """prob [H,W] -> int32 [5] on the device: (rmin, rmax, cmin, cmax) of prob > threshold joined with click_pixels (int32 [n,2]
+    row, col on the device), and the number of pixels above the threshold."""
+    H, W = _req(prob, 'prob').shape
+    n = 0
+    if click_pixels is not None:
+        if not click_pixels.is_cuda or click_pixels.dtype != torch.int32 or click_pixels.dim() != 2 or click_pixels.shape[1] != 2:
+            raise RuntimeError('mask_bbox: click_pixels must be an int32 [n, 2] tensor on the device')
+        click_pixels, n = click_pixels.contiguous(), click_pixels.shape[0]
+    if out is None:
+        out = torch.empty(5, dtype=torch.int32, device=prob.device)
+    check(load().xmem_mask_bbox(ptr(prob.contiguous()), H, W, float(threshold), ptr(click_pixels) if n else ptr(None), n, ptr(out),
+                                stream_ptr()))
+    return out
+
+
+def prob_threshold(prob, threshold=0.5):
+    """(prob > threshold).float() of a contiguous float tensor."""
+    if not _req(prob, 'prob').is_contiguous():
+        raise RuntimeError('prob_threshold: expected a contiguous tensor')
+    out = torch.empty_like(prob)
+    check(load().xmem_prob_threshold(ptr(prob), prob.numel(), float(threshold), ptr(out), stream_ptr()))
+    return out
+
+
+def click_commit(prev_prob, obj_mask, tar_obj, temperature=1000.0):
+    """ClickInteraction.predict: prev_prob [K+1,H,W], obj_mask [H,W], tar_obj in 1..K -> (aggregate_wbg of the clamped maps with row
+    tar_obj replaced [K+1,H,W], its argmax uint8 [H,W])."""
+    K1, H, W = _req(prev_prob, 'prev_prob').shape
+    if tuple(_req(obj_mask, 'obj_mask').shape[-2:]) != (H, W) or obj_mask.numel() != H * W:
+        raise RuntimeError(f'click_commit: prev_prob {tuple(prev_prob.shape)} and obj_mask {tuple(obj_mask.shape)} differ in size')
+    out = torch.empty((K1, H, W), dtype=torch.float32, device=prev_prob.device)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=prev_prob.device)
+    check(load().xmem_click_commit(ptr(prev_prob.contiguous()), ptr(obj_mask.contiguous()), K1 - 1, H, W, int(tar_obj), float(temperature),
+                                   ptr(out), ptr(mask), stream_ptr()))
+    return out, mask

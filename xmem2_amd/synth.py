@@ -218,3 +218,55 @@ def synthetic_s2m_state_dict(seed=0, as_torch=True):
         return {k: (torch.from_numpy(np.ascontiguousarray(v)) if v.ndim else torch.tensor(int(v), dtype=torch.int64))
                 for k, v in out.items()}
     return out
+
+
+def synthetic_click_state_dict(seed=0, as_torch=True):
+    """Conditioned synthetic checkpoint of the click network (the 413 names of arch.click_state_dict_spec), from the same integer hash.
+
+    Convolutions He-normal (backbone: fan-out; heads, depthwise and rgb_conv: fan-in), BatchNorm with non-trivial affine and running
+    statistics, the last BN of every residual branch damped (x0.35) as in synthetic_state_dict.  With plain He init the output is
+    nearly deaf to the clicks, so two conditionings keep it informative: the click channels (3: positive, 4: negative) of rgb_conv.0
+    x20 / x-20, so that the distance maps visibly move the mask, and the final 1x1 (head.layers.2) x1.5 with bias -2.7, which centres
+    the logits (its inputs are ReLU outputs, so the plain sum has mean 1.8 at std 1.5) and spreads the probabilities over (0, 1)
+    (tests/golden/make_click_goldens.py asserts both on the reference's outputs)."""
+    from .arch import click_state_dict_spec
+    spec = click_state_dict_spec()
+    out = {}
+    for ti, (name, shape) in enumerate(spec.items()):
+        stream = seed * 100003 + 70000 + ti
+        n = int(np.prod(shape)) if len(shape) else 1
+        if name.endswith('num_batches_tracked'):
+            arr = np.array(0, dtype=np.int64)
+        elif name.endswith('running_mean'):
+            arr = 0.05 * hash_normal(n, stream)
+        elif name.endswith('running_var'):
+            arr = hash_uniform(n, stream, 0.8, 1.25)
+        elif len(shape) == 1 and name.endswith('.weight'):      # BN gamma
+            arr = hash_uniform(n, stream, 0.85, 1.15)
+            if name.split('.')[-2] == 'bn3':
+                arr = arr * np.float32(0.35)
+        elif name == 'head.layers.2.bias':
+            arr = np.full(n, CLICK_HEAD_BIAS, np.float32)
+        elif len(shape) == 1:                                     # BN beta, convolution bias
+            arr = 0.02 * hash_normal(n, stream)
+        else:
+            cout, cin, kh, kw = shape
+            fan = kh * kw * (cout if 'backbone' in name else cin)
+            arr = hash_normal(n, stream) * np.float32(math.sqrt(2.0 / fan))
+            if name == 'rgb_conv.0.weight':
+                arr = arr.reshape(shape).copy()
+                arr[:, 3] *= np.float32(CLICK_INPUT_GAIN)
+                arr[:, 4] *= np.float32(-CLICK_INPUT_GAIN)
+            elif name == 'head.layers.2.weight':
+                arr = arr * np.float32(CLICK_HEAD_GAIN)
+        out[name] = np.asarray(arr).reshape(shape)
+    if as_torch:
+        import torch
+        return {k: (torch.from_numpy(np.ascontiguousarray(v)) if v.ndim else torch.tensor(int(v), dtype=torch.int64))
+                for k, v in out.items()}
+    return out
+
+
+CLICK_INPUT_GAIN = 20.0
+CLICK_HEAD_GAIN = 1.5
+CLICK_HEAD_BIAS = -2.7
