@@ -40,7 +40,7 @@ typedef enum {
 
 /* ABI version of this header.  2 (round 4): xmem_conv_desc grew (in_half / out_half / w_half), storage-typed `_t` entry points, plan
  * tiles 23..40.  3 (round 5): no layout change, but the MEANING of w_winograd4 / w_winograd4_split changed - the F(4x4) transforms use the
- * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
+ * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  Still 5: the f-BRS refinement entry points added (xmem_brs_affine_nhwc, xmem_brs_loss, xmem_relu_gate_nhwc, xmem_relu_gate_outer_nhwc, xmem_brs_param_grad and their workspace sizes): new symbols only, no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
 #define XMEM_ABI_VERSION 5
 int xmem_version(void);
 const char* xmem_last_error_string(int code); /* static string for a status code */
@@ -400,6 +400,46 @@ int xmem_prob_threshold(const float* prob, size_t n, float threshold, float* out
  * out [K+1][H][W] (nullable, must not alias prev_prob) and mask [H][W] uint8 (nullable) = its first-index argmax. */
 int xmem_click_commit(const float* prev_prob, const float* obj_mask, int K, int H, int W, int tar_obj, float temperature,
                       float* out, uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * f-BRS click refinement (inference/interact/fbrs/inference/predictors/brs.py:54-140, brs_functors.py, brs_losses.py): the parts of
+ * the objective and of its data gradient that are not convolutions.  Everything here is bit-reproducible: the same inputs give the
+ * same bits (no float atomics; fixed-order reductions), which L-BFGS and the strict `<` of the best prediction rely on.
+ *
+ * y = x (1 + s[c]) + b[c] on NHWC [B][h][w][C], scale_bias [2C] = the optimiser's vector (scale then bias, ScaleBiasOptimizer.
+ * unpack_opt_params), the same for every batch element.  C % 4 == 0, 16-byte aligned pointers. */
+int xmem_brs_affine_nhwc(const float* x, const float* scale_bias, float* y, int B, int h, int w, int C, void* stream);
+
+/* out[i] = y[i] > 0 ? g[i] : 0 over n floats (n % 4 == 0): the adjoint of a ReLU whose OUTPUT y was kept; out may alias g. */
+int xmem_relu_gate_nhwc(const float* y, const float* g, float* out, size_t n, void* stream);
+
+/* out[p][c] = y[p][c] > 0 ? g1[p] w[c] : 0: the adjoint of a Cout = 1 pointwise layer (an outer product of its output gradient g1
+ * [pixels] with its weights w [C]) followed by the ReLU gate of that layer's input y [pixels][C].  C % 4 == 0. */
+int xmem_relu_gate_outer_nhwc(const float* y, const float* g1, const float* w, float* out, size_t pixels, int C, void* stream);
+
+/* BRSMaskLoss on the align_corners upsample of logits [B][h4][w4] (B = 1 or 2: the plain and the mirrored sample, summed jointly) to
+ * H x W, with the bookkeeping of BaseOptimizer.__call__ in the same launch sequence.
+ *   rects     [B][cap][5] int32 per click: rows [r0, r1) x columns [c0, c1) of its square in the working image - what the numpy
+ *             slice of _get_clicks_maps_nd selects, so at most 3 x 3, clipped, and EMPTY for a click whose rounded row or column is 0 -
+ *             and the polarity (1 positive).  count [1] int32 ON THE DEVICE: clicks per sample, clamped to [0, cap].
+ *             A pixel covered by several squares of one polarity counts once.
+ *   last_mask [B][H][W] uint8 (read), mask [B][H][W] uint8 (written: upsampled logit > 0); must not alias.
+ *   record    8 floats: [0] sum((1-p) pos)^2 / (sum pos + 1e-5) + sum(p neg)^2 / (sum neg + 1e-5), [1] max |(1-p) pos|, [2] max |p neg|,
+ *             [3] zeroed (xmem_brs_param_grad writes the final f there), [4 + 2b], [5 + 2b] as int32: the number of pixels of sample b in
+ *             mask & last_mask and in mask | last_mask.
+ *   dlogit    [B][h4][w4]: d record[0] / d logits (every element written).
+ * workspace: xmem_brs_loss_workspace_bytes(B, cap), 16-byte aligned. */
+size_t xmem_brs_loss_workspace_bytes(int B, int cap);
+int xmem_brs_loss(const float* logits, int B, int h4, int w4, int H, int W, const int32_t* rects, const int32_t* count, int cap,
+                  const uint8_t* last_mask, uint8_t* mask, float* record, float* dlogit, void* workspace, size_t workspace_bytes,
+                  void* stream);
+
+/* grad[c] = sum over B h w of g x + 2 reg_weight s[c], grad[C + c] = sum g + 2 reg_weight reg_bias_weight b[c] for the feature
+ * gradient g and the un-scaled features x, both NHWC [B][h][w][C] (C % 4 == 0, C <= 1024), in two fixed-order stages; and
+ * record[3] = record[0] + reg_weight (sum s^2 + reg_bias_weight sum b^2).  workspace: xmem_brs_param_grad_workspace_bytes(C). */
+size_t xmem_brs_param_grad_workspace_bytes(int C);
+int xmem_brs_param_grad(const float* g, const float* x, int B, int h, int w, int C, const float* scale_bias, float reg_weight,
+                        float reg_bias_weight, float* record, float* grad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);

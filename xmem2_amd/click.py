@@ -1,7 +1,7 @@
 """Click-to-mask on MI355X: the reference's f-BRS click network and its NoBRS predictor over HIP kernels.
 
     python -m xmem2_amd.click --images DIR --clicks FILE.json --out DIR [--prev-masks DIR] [--model fbrs.pth | --synthetic-seed N]
-                              [--num-objects K]
+                              [--num-objects K] [--brs-mode NoBRS|f-BRS-B|f-BRS-C]
 
 ``ClickNet`` mirrors ``get_deeplab_model(backbone='resnet50', deeplab_ch)`` (inference/interact/fbrs/model/is_deeplab_model.py:9-66):
 click distance maps and the rgb_conv input MLP, a ResNet-50-v1s at output stride 8 (fbrs/model/modeling/resnetv1b.py), the
@@ -12,8 +12,8 @@ the forward is captured once per working geometry as a HIP graph and replayed.
 ``NoBRSPredictor`` is BasePredictor (fbrs/inference/predictors/base.py) with its transforms: ZoomIn and LimitLongestSide are ported
 as host state machines over device tensors; SigmoidForPred and AddHorizontalFlip live inside the input and output kernels
 (ops.click_input builds both samples, ops.click_prob averages the logits and applies the sigmoid).  ``FBRSController`` keeps the
-reference's surface (inference/interact/fbrs_controller.py).  The back-propagating refinement (f-BRS / RGB-BRS) is not built:
-``brs_mode`` other than 'NoBRS' raises NotImplementedError.
+reference's surface (inference/interact/fbrs_controller.py) with the NoBRS predictor: ``brs_mode`` other than 'NoBRS' raises
+NotImplementedError there.  The back-propagating refinement of 'f-BRS-B' / 'f-BRS-C' is click_brs.py (FeatureBRSController).
 
 The JSON of the command line maps a frame number to a list of {"object": k, "x": col, "y": row, "positive": bool}.  The objects of a
 frame are processed one after the other (a fresh anchor per object), each committed as ClickInteraction.predict does
@@ -66,6 +66,7 @@ class ClickNet:
         self._sd = None
         self._w = {}
         self._graphs = OrderedDict()   # (h, w, with_flip) -> (graph, static inputs, static output), least recently used first
+        self._brs = {}                 # insertion mode -> the f-BRS engine with its own captured graphs (click_brs.engine_for)
         self._cap = CLICK_CAPACITY
         self.captures = 0
         self._scope = ops.new_scope()
@@ -109,6 +110,7 @@ class ClickNet:
         self.deeplab_ch = ch
         self._sd = {k: v.detach().to('cpu') for k, v in sd.items() if k != 'aspp_dropout'}
         self._graphs.clear()
+        self._brs.clear()
         self._upload()
 
     def state_dict(self):
@@ -120,6 +122,7 @@ class ClickNet:
             self.device = torch.device('cuda', torch.cuda.current_device())
         if self._sd is not None:
             self._graphs.clear()
+            self._brs.clear()
             self._upload()
         return self
 
@@ -131,6 +134,17 @@ class ClickNet:
         dw = self._sd[prefix + '.body.0.weight'].float()
         W[key + '.dw'] = dw.reshape(dw.shape[0], 9).t().contiguous().to(self.device)
         W[key + '.pw'] = self._conv_w(prefix + '.body.1', prefix + '.body.2', 1, 0)
+        # the adjoints f-BRS back-propagates through (click_brs.py): the taps reversed, the BN-folded pointwise matrix transposed
+        W[key + '.dwT'] = W[key + '.dw'].flip(0).contiguous()
+        W[key + '.pwT'] = self._transposed(W[key + '.pw'])
+
+    @staticmethod
+    def _transposed(cw):
+        """The adjoint of a pointwise layer as a pointwise layer: (scale[o] w[o][i])^T with scale 1 and shift 0."""
+        wt = (cw.w[:, 0, 0, :cw.cin_true] * cw.scale[:, None]).t().contiguous()
+        dev = wt.device
+        return ops.ConvWeights(wt.reshape(cw.cin_true, 1, 1, cw.cout), torch.ones(cw.cin_true, device=dev),
+                               torch.zeros(cw.cin_true, device=dev), 1, 0)
 
     def _upload(self):
         if self.device.type != 'cuda':
@@ -171,9 +185,12 @@ class ClickNet:
         self._separable(W, 'dl.0', fe + 'head.block.0')
         self._separable(W, 'dl.1', fe + 'head.block.1')
         W['dl.2'] = self._conv_w(fe + 'head.block.2', None, 1, 0)
+        W['dl.2T'] = self._transposed(W['dl.2'])
         self._separable(W, 'head.0', 'head.layers.0')
         self._separable(W, 'head.1', 'head.layers.1')
         W['head.2'] = self._conv_w('head.layers.2', None, 1, 0)
+        h2 = W['head.2']
+        W['head.2T'] = (h2.w[0, 0, 0, :h2.cin_true] * h2.scale[0]).contiguous()       # one output channel: its adjoint is an outer product
         self._w = W
 
     def _need_weights(self):
@@ -212,15 +229,29 @@ class ClickNet:
 
     def head(self, head_input):
         """head_input [B,h4,w4,ch+32] -> logits [B,h4,w4,1]: _DeepLabHead (deeplab_v3.py:99-112), then SepConvHead."""
+        return self.sep_conv_head(self.deeplab_head(head_input))
+
+    def deeplab_head(self, head_input, kept=None):
+        """_DeepLabHead: head_input [B,h4,w4,ch+32] -> [B,h4,w4,ch], the tensor f-BRS-C's `after_deeplab` scale and bias act on.  `kept`
+        (a list) receives the two ReLU outputs the backward pass gates with."""
         self._need_weights()
         W = self._w
         x = head_input
         for key in ('dl.0', 'dl.1'):
             x = ops.conv2d(ops.depthwise3x3(x, W[key + '.dw']), W[key + '.pw'], relu_out=True)
-        x = ops.conv2d(x, W['dl.2'])
+            if kept is not None:
+                kept.append(x)
+        return ops.conv2d(x, W['dl.2'])
+
+    def sep_conv_head(self, x, kept=None, out=None):
+        """SepConvHead: [B,h4,w4,ch] -> logits [B,h4,w4,1] (into `out` when given); `kept` as in deeplab_head."""
+        self._need_weights()
+        W = self._w
         for key in ('head.0', 'head.1'):
             x = ops.conv2d(ops.depthwise3x3(x, W[key + '.dw']), W[key + '.pw'], relu_out=True)
-        return ops.conv2d(x, W['head.2'])
+            if kept is not None:
+                kept.append(x)
+        return ops.conv2d(x, W['head.2'], out=out, out_ld=None if out is None else 1)
 
     def _forward(self, image, clicks, counts, with_flip):
         x = ops.click_input(image, clicks, counts, self._w['rgb_conv'], NORM_RADIUS, with_flip)
@@ -483,15 +514,20 @@ class NoBRSPredictor:
         return image, clicks_list, changed
 
     def get_prediction(self, clicks_list):
-        image, clicks, _ = self.apply_transforms(self.original_image, list(clicks_list))
+        image, clicks, changed = self.apply_transforms(self.original_image, list(clicks_list))
         self.last_geometry = (tuple(image.shape[-2:]), [tuple(c.coords) for c in clicks])
-        points = get_points_nd([clicks], self.net_clicks_limit)[0]
-        prob = self.net.run(image, points, self.with_flip).clone()       # a copy: the static buffer is overwritten by the next click
+        prob = self._predict(image, clicks, changed)
         for t in reversed(self.transforms):
             prob = t.inv_transform(prob)
         if self.zoom_in is not None and self.zoom_in.check_possible_recalculation():
             return self.get_prediction(clicks_list)
         return prob
+
+    def _predict(self, image, clicks, image_changed):
+        """The probability map [h,w] of the working image for its (transformed) clicks: BasePredictor._get_prediction with the
+        flip-averaged sigmoid of the output transforms."""
+        points = get_points_nd([clicks], self.net_clicks_limit)[0]
+        return self.net.run(image, points, self.with_flip).clone()       # a copy: the static buffer is overwritten by the next click
 
     def get_states(self):
         return {'transform_states': [t.get_state() for t in self.transforms]}
@@ -505,19 +541,24 @@ class NoBRSPredictor:
 class FBRSController:
     """inference/interact/fbrs_controller.py with fbrs/controller.py's InteractiveController folded in: clicks on one anchored image ->
     the object's mask.  Defaults are the reference's (zoom-in skip_clicks=1, target_size=480, expansion_ratio=1.4; with_flip;
-    prob_thresh 0.5; max_size 800) except the predictor: brs_mode='NoBRS' (the back-propagating refinement of 'f-BRS-B', the
-    reference's default, is not built) with NoBRS's own net_clicks_limit=None.  With the reference controller's limit of 8, clicks
-    after the eighth would be ignored outright once no optimisation follows them.  The first click of every mode is identical to
-    NoBRS's (no optimisation runs before optimize_after_n_clicks=1); later clicks lack the refinement."""
+    prob_thresh 0.5; max_size 800) except the predictor: brs_mode='NoBRS' with NoBRS's own net_clicks_limit=None (with the reference
+    controller's limit of 8, clicks after the eighth would be ignored outright once no optimisation follows them).  This class
+    runs no back-propagating refinement: click_brs.FeatureBRSController is the controller with the reference's own defaults
+    ('f-BRS-B', net_clicks_limit=8).  The first click of every mode is identical to NoBRS's (no optimisation runs before
+    optimize_after_n_clicks=1); later clicks lack the refinement here."""
 
     def __init__(self, checkpoint_path_or_net, device='cuda:0', max_size=800, brs_mode='NoBRS', zoom_in_params=None, with_flip=True,
                  net_clicks_limit=None, prob_thresh=0.5):
         if brs_mode in BRS_MODES:
             raise NotImplementedError(f"FBRSController: brs_mode={brs_mode!r} needs the back-propagating refinement (backward kernels and "
-                                      "L-BFGS), which is not built.  Its first click is identical to brs_mode='NoBRS'; later clicks "
-                                      'lack the refinement.')
+                                      "L-BFGS), which this controller does not run.  Its first click is identical to brs_mode='NoBRS'; "
+                                      "later clicks lack the refinement.  xmem2_amd.click_brs.FeatureBRSController runs 'f-BRS-B' and "
+                                      "'f-BRS-C'.")
         if brs_mode != 'NoBRS':
             raise ValueError(f'FBRSController: unknown brs_mode {brs_mode!r}')
+        self._setup(checkpoint_path_or_net, device, max_size, zoom_in_params, with_flip, net_clicks_limit, prob_thresh)
+
+    def _setup(self, checkpoint_path_or_net, device, max_size, zoom_in_params, with_flip, net_clicks_limit, prob_thresh):
         self.device = torch.device(device)
         self.net = checkpoint_path_or_net if isinstance(checkpoint_path_or_net, ClickNet) \
             else ClickNet(checkpoint_path_or_net, device=self.device)
@@ -597,6 +638,8 @@ def parse_args(argv=None):
     src.add_argument('--model', default=None, help='click-network checkpoint (saves/fbrs.pth)')
     src.add_argument('--synthetic-seed', type=int, default=None, help='conditioned synthetic weights instead of a checkpoint')
     ap.add_argument('--num-objects', type=int, default=None, help='objects (default: the largest label in clicks / masks)')
+    ap.add_argument('--brs-mode', choices=('NoBRS', 'f-BRS-B', 'f-BRS-C'), default='NoBRS',
+                    help="click refinement: 'f-BRS-B' is the interactive demo's (default: NoBRS, no refinement)")
     args = ap.parse_args(argv)
     if args.model is None and args.synthetic_seed is None:
         ap.error('one of --model or --synthetic-seed is required')
@@ -665,13 +708,18 @@ def main(argv=None):
     if k_max > K:
         raise ValueError(f'--num-objects {K} is smaller than the largest label {k_max}')
     device = torch.device('cuda', torch.cuda.current_device())
-    net = ClickNet(device=device)
+    from . import click as pkg      # under `python -m` this module is __main__: take the classes click_brs subclasses from the package
+    net = pkg.ClickNet(device=device)
     if args.model:
         net.load_weights(args.model)
     else:
         from .synth import synthetic_click_state_dict
         net.load_state_dict(synthetic_click_state_dict(args.synthetic_seed))
-    ctl = FBRSController(net, device=device)
+    if args.brs_mode == 'NoBRS':
+        ctl = pkg.FBRSController(net, device=device)
+    else:
+        from .click_brs import FeatureBRSController
+        ctl = FeatureBRSController(net, device=device, brs_mode=args.brs_mode)
     os.makedirs(args.out, exist_ok=True)
     pal = _palette()
     for fi, img, prev, frame_clicks in loaded:

@@ -1128,3 +1128,97 @@ def click_commit(prev_prob, obj_mask, tar_obj, temperature=1000.0):
     check(load().xmem_click_commit(ptr(prev_prob.contiguous()), ptr(obj_mask.contiguous()), K1 - 1, H, W, int(tar_obj), float(temperature),
                                    ptr(out), ptr(mask), stream_ptr()))
     return out, mask
+
+
+# ---- f-BRS click refinement (csrc/brs.hip): every kernel bit-reproducible --------------------------------------------
+
+BRS_RECORD = 8          # floats of the evaluation record ahead of the gradient (include/xmem_hip.h, xmem_brs_loss)
+
+
+def brs_affine(x, scale_bias, out=None):
+    """y = x (1 + s[c]) + b[c] on contiguous NHWC x [B,h,w,C]; scale_bias [2C] float32 on the device (scale then bias)."""
+    B, h, w, Cc = _req(x, 'brs_affine input').shape
+    if not x.is_contiguous() or _req(scale_bias, 'scale_bias').numel() != 2 * Cc or not scale_bias.is_contiguous():
+        raise RuntimeError(f'brs_affine: expected a contiguous input and {2 * Cc} scale / bias values')
+    if out is None:
+        out = torch.empty_like(x)
+    if tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+        raise RuntimeError('brs_affine: out must be contiguous and shaped like the input')
+    check(load().xmem_brs_affine_nhwc(ptr(x), ptr(scale_bias), ptr(_req(out, 'out')), B, h, w, Cc, stream_ptr()))
+    return out
+
+
+def relu_gate(y, g, out=None):
+    """g where the kept ReLU output y is positive, else 0 (the ReLU's adjoint); out may be g."""
+    if tuple(_req(y, 'relu_gate y').shape) != tuple(_req(g, 'relu_gate g').shape) or not y.is_contiguous() or not g.is_contiguous():
+        raise RuntimeError('relu_gate: y and g must be contiguous tensors of one shape')
+    if out is None:
+        out = torch.empty_like(g)
+    if tuple(out.shape) != tuple(g.shape) or not out.is_contiguous():
+        raise RuntimeError('relu_gate: out must be contiguous and shaped like g')
+    check(load().xmem_relu_gate_nhwc(ptr(y), ptr(g), ptr(_req(out, 'out')), g.numel(), stream_ptr()))
+    return out
+
+
+def relu_gate_outer(y, g1, w, out=None):
+    """out[..., c] = y[..., c] > 0 ? g1[...] w[c] : 0 for y [B,h,w,C], g1 [B,h,w] (or [B,h,w,1]) and w [C]: the adjoint of a
+    single-output pointwise layer, gated by the ReLU that produced its input y."""
+    Cc = _req(y, 'relu_gate_outer y').shape[-1]
+    pixels = y.numel() // Cc
+    if _req(g1, 'g1').numel() != pixels or _req(w, 'w').numel() != Cc or not (y.is_contiguous() and g1.is_contiguous() and w.is_contiguous()):
+        raise RuntimeError('relu_gate_outer: expected contiguous y [..., C], g1 with one value per pixel and w [C]')
+    if out is None:
+        out = torch.empty_like(y)
+    if tuple(out.shape) != tuple(y.shape) or not out.is_contiguous():
+        raise RuntimeError('relu_gate_outer: out must be contiguous and shaped like y')
+    check(load().xmem_relu_gate_outer_nhwc(ptr(y), ptr(g1), ptr(w), ptr(_req(out, 'out')), pixels, Cc, stream_ptr()))
+    return out
+
+
+def brs_loss(logits, H, W, rects, count, last_mask, mask, record, dlogit=None):
+    """BRSMaskLoss on the align_corners upsample of logits [B,h4,w4] to H x W with the evaluation's bookkeeping.  rects [B,cap,5] int32
+    (r0, r1, c0, c1, positive) and count [1] int32 on the device; last_mask (read) and mask (written: upsampled logit > 0) uint8
+    [B,H,W]; record: at least BRS_RECORD floats, written as include/xmem_hip.h lays them out -> dlogit [B,h4,w4]."""
+    B, h4, w4 = _req(logits, 'logits').shape
+    if not logits.is_contiguous() or B not in (1, 2):
+        raise RuntimeError(f'brs_loss: expected contiguous logits [1 or 2, h4, w4], got {tuple(logits.shape)}')
+    if not rects.is_cuda or rects.dtype != torch.int32 or rects.dim() != 3 or rects.shape[0] != B or rects.shape[2] != 5 or not rects.is_contiguous():
+        raise RuntimeError(f'brs_loss: rects must be a contiguous int32 [{B}, cap, 5] tensor on the device')
+    if not count.is_cuda or count.dtype != torch.int32 or count.numel() != 1:
+        raise RuntimeError('brs_loss: count must be one int32 on the device')
+    for name, m in (('last_mask', last_mask), ('mask', mask)):
+        if not m.is_cuda or m.dtype != torch.uint8 or tuple(m.shape) != (B, int(H), int(W)) or not m.is_contiguous():
+            raise RuntimeError(f'brs_loss: {name} must be a contiguous uint8 [{B}, {H}, {W}] tensor on the device')
+    if mask.data_ptr() == last_mask.data_ptr():
+        raise RuntimeError('brs_loss: mask and last_mask must be different buffers')
+    if _req(record, 'record').numel() < BRS_RECORD or not record.is_contiguous():
+        raise RuntimeError(f'brs_loss: record needs {BRS_RECORD} contiguous floats')
+    if dlogit is None:
+        dlogit = torch.empty_like(logits)
+    if tuple(_req(dlogit, 'dlogit').shape) != (B, h4, w4) or not dlogit.is_contiguous():
+        raise RuntimeError('brs_loss: dlogit must be contiguous and shaped like the logits')
+    lib, cap = load(), rects.shape[1]
+    need = lib.xmem_brs_loss_workspace_bytes(B, cap)
+    ws = workspace(need, logits.device, 'brs_loss')
+    check(lib.xmem_brs_loss(ptr(logits), B, h4, w4, int(H), int(W), ptr(rects), ptr(count), cap, ptr(last_mask), ptr(mask), ptr(record),
+                            ptr(dlogit), ptr(ws), need, stream_ptr()))
+    return dlogit
+
+
+def brs_param_grad(g, x, scale_bias, record, grad, reg_weight=1e-3, reg_bias_weight=10.0):
+    """The feature gradient g and the un-scaled features x (contiguous NHWC [B,h,w,C]) -> grad [2C] (sum g x + 2 reg_weight s | sum g +
+    2 reg_weight reg_bias_weight b) and record[3] = record[0] + the regulariser: the objective's value."""
+    B, h, w, Cc = _req(g, 'brs_param_grad g').shape
+    if tuple(_req(x, 'x').shape) != (B, h, w, Cc) or not g.is_contiguous() or not x.is_contiguous():
+        raise RuntimeError('brs_param_grad: g and x must be contiguous tensors of one shape')
+    if _req(scale_bias, 'scale_bias').numel() != 2 * Cc or _req(grad, 'grad').numel() != 2 * Cc or not grad.is_contiguous() \
+            or not scale_bias.is_contiguous():
+        raise RuntimeError(f'brs_param_grad: scale_bias and grad hold {2 * Cc} contiguous floats')
+    if _req(record, 'record').numel() < BRS_RECORD or not record.is_contiguous():
+        raise RuntimeError(f'brs_param_grad: record needs {BRS_RECORD} contiguous floats')
+    lib = load()
+    need = lib.xmem_brs_param_grad_workspace_bytes(Cc)
+    ws = workspace(need, g.device, 'brs_param')
+    check(lib.xmem_brs_param_grad(ptr(g), ptr(x), B, h, w, Cc, ptr(scale_bias), float(reg_weight), float(reg_bias_weight), ptr(record),
+                                  ptr(grad), ptr(ws), need, stream_ptr()))
+    return grad
