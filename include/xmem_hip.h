@@ -441,6 +441,31 @@ size_t xmem_brs_param_grad_workspace_bytes(int C);
 int xmem_brs_param_grad(const float* g, const float* x, int B, int h, int w, int C, const float* scale_bias, float reg_weight,
                         float reg_bias_weight, float* record, float* grad, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Robot-click evaluation (inference/interact/fbrs/inference/clicker.py:32-59, utils.py:103-110) in integer arithmetic: the same inputs
+ * give the same bits.  H and W in [1, 16384] (else XMEM_ERR_UNSUPPORTED), which keeps every squared distance in int32.
+ *
+ * Error planes of a prediction against gt [H][W] uint8 (1 object, 255 ignore, anything else background).  The prediction is
+ * prob [H][W] > threshold, or mask [H][W] != 0: exactly one of prob / mask is non-NULL.  planes [2][H][W] uint8: fn = gt & ~pred,
+ * fp = ~gt & pred & not_ignore.  counts [2] int32 (zeroed on the stream first): pixels of pred & gt and of (pred | gt) & not_ignore,
+ * the numerator and denominator of get_iou. */
+int xmem_click_errors(const float* prob, float threshold, const uint8_t* mask, const uint8_t* gt, int H, int W, uint8_t* planes,
+                      int32_t* counts, void* stream);
+
+/* Exact squared Euclidean distance transform of planes [B][H][W] uint8 (non-zero = inside) surrounded by one ring of zeros:
+ * d2 [B][H][W] int32 = min over the zero pixels of the plane and the ring pixels of dy^2 + dx^2, 0 where the plane is 0 - the square
+ * of scipy's distance_transform_edt on the plane padded by one, cropped again.  A column pass and a row pass; the row pass searches
+ * outwards from each pixel while dx^2 < the best so far (exact), so its cost grows with the largest distance.  B * H < 2^31. */
+int xmem_edt_sq(const uint8_t* planes, int B, int H, int W, int32_t* d2, void* stream);
+
+/* The next click of Clicker._get_click from d2 [2][H][W] (fn, fp) and not_clicked [H][W] uint8: per plane the maximum of
+ * d2 * (not_clicked != 0) at its smallest linear index; is_positive = fn_max > fp_max (strict: a tie is a negative click).
+ * record [8] int32 = {is_positive, row, col, fn_max_d2, fp_max_d2, counts[0], counts[1], 0} (counts nullable: zeros);
+ * not_clicked[row][col] is cleared.  Two stages through workspace (xmem_next_click_workspace_bytes(H, W), 8-byte aligned). */
+size_t xmem_next_click_workspace_bytes(int H, int W);
+int xmem_next_click(const int32_t* d2, uint8_t* not_clicked, const int32_t* counts, int H, int W, int32_t* record, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

@@ -1130,6 +1130,76 @@ def click_commit(prev_prob, obj_mask, tar_obj, temperature=1000.0):
     return out, mask
 
 
+# ---- robot-click evaluation (csrc/edt.hip): integer arithmetic, bit-reproducible -------------------------------------
+
+CLICK_RECORD = 8        # int32 values of xmem_next_click's record (include/xmem_hip.h)
+
+
+def _req_u8(t, name, shape=None):
+    if not t.is_cuda or t.dtype != torch.uint8 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor' + (f' of shape {tuple(shape)}' if shape is not None else '')
+                           + ' - xmem2_amd has no CPU path')
+    return t.contiguous()
+
+
+def edt_sq(mask, out=None):
+    """Exact squared Euclidean distance transform of uint8 planes `mask` [H,W] or [B,H,W] (non-zero = inside) within one ring of
+    zeros -> int32 of the same shape: rint(distance_transform_edt(np.pad(mask, 1))[1:-1, 1:-1] ** 2), exactly."""
+    if mask.dim() not in (2, 3):
+        raise RuntimeError(f'edt_sq: expected [H,W] or [B,H,W], got {tuple(mask.shape)}')
+    mask = _req_u8(mask, 'mask')
+    B, H, W = (1,) + tuple(mask.shape) if mask.dim() == 2 else tuple(mask.shape)
+    if out is None:
+        out = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    elif not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != tuple(mask.shape) or not out.is_contiguous():
+        raise RuntimeError(f'edt_sq: out must be a contiguous int32 CUDA (HIP) tensor of shape {tuple(mask.shape)}')
+    check(load().xmem_edt_sq(ptr(mask), B, H, W, ptr(out), stream_ptr()))
+    return out
+
+
+def click_errors(pred, gt, threshold=None, planes=None, counts=None):
+    """The robot's error planes: gt uint8 [H,W] (1 object, 255 ignore, else background) against `pred`, a float32 probability map
+    with `threshold` (pred > threshold) or a uint8 mask (non-zero) -> (planes uint8 [2,H,W] = (fn, fp), counts int32 [2] =
+    (intersection, union) under the ignore mask), both on the device."""
+    if gt.dim() != 2:
+        raise RuntimeError(f'click_errors: gt must be [H,W], got {tuple(gt.shape)}')
+    gt = _req_u8(gt, 'gt')
+    H, W = gt.shape
+    if pred.dtype == torch.float32:
+        if threshold is None:
+            raise RuntimeError('click_errors: a probability map needs its threshold')
+        if tuple(_req(pred, 'pred').shape) != (H, W):
+            raise RuntimeError(f'click_errors: pred {tuple(pred.shape)} and gt {(H, W)} differ in shape')
+        prob, mask = pred.contiguous(), None
+    else:
+        prob, mask = None, _req_u8(pred, 'pred', (H, W))
+    if planes is None:
+        planes = torch.empty((2, H, W), dtype=torch.uint8, device=gt.device)
+    else:
+        planes = _req_u8(planes, 'planes', (2, H, W))
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int32, device=gt.device)
+    check(load().xmem_click_errors(ptr(prob), float(threshold or 0.0), ptr(mask), ptr(gt), H, W, ptr(planes), ptr(counts), stream_ptr()))
+    return planes, counts
+
+
+def next_click(d2, not_clicked, counts=None, record=None):
+    """d2 int32 [2,H,W] (fn, fp), not_clicked uint8 [H,W] -> record int32 [CLICK_RECORD] on the device: (is_positive, row, col,
+    fn_max_d2, fp_max_d2, counts[0], counts[1], 0); not_clicked[row, col] is cleared in place."""
+    if not d2.is_cuda or d2.dtype != torch.int32 or d2.dim() != 3 or d2.shape[0] != 2 or not d2.is_contiguous():
+        raise RuntimeError('next_click: d2 must be a contiguous int32 CUDA (HIP) tensor [2,H,W]')
+    H, W = int(d2.shape[1]), int(d2.shape[2])
+    if not not_clicked.is_cuda or not_clicked.dtype != torch.uint8 or tuple(not_clicked.shape) != (H, W) or not not_clicked.is_contiguous():
+        raise RuntimeError(f'next_click: not_clicked must be a contiguous uint8 CUDA (HIP) tensor of shape {(H, W)} (it is written)')
+    if record is None:
+        record = torch.empty(CLICK_RECORD, dtype=torch.int32, device=d2.device)
+    lib = load()
+    nbytes = lib.xmem_next_click_workspace_bytes(H, W)
+    ws = workspace(max(nbytes, 8), d2.device, 'next_click')
+    check(lib.xmem_next_click(ptr(d2), ptr(not_clicked), ptr(counts), H, W, ptr(record), ptr(ws), ws.numel(), stream_ptr()))
+    return record
+
+
 # ---- f-BRS click refinement (csrc/brs.hip): every kernel bit-reproducible --------------------------------------------
 
 BRS_RECORD = 8          # floats of the evaluation record ahead of the gradient (include/xmem_hip.h, xmem_brs_loss)
