@@ -466,6 +466,22 @@ size_t xmem_next_click_workspace_bytes(int H, int W);
 int xmem_next_click(const int32_t* d2, uint8_t* not_clicked, const int32_t* counts, int H, int W, int32_t* record, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame ingest: the working-size resize of a decoded frame (inference/data/video_reader.py:61-65, torchvision Resize on a PIL image =
+ * Image.resize(size, BILINEAR), antialiased) in the host library's own integer arithmetic, so the result is the same bytes.
+ *   src uint8 [Hs][Ws][3] -> dst uint8 [Hd][Wd][3] (contiguous, not aliasing src); flip != 0 writes the output columns mirrored.
+ *   Per axis a tap table computed on the host (xmem2_amd/pil_resize.py: taps): bounds int32 [out][2] = (first source index, tap
+ *   count), coeffs int32 [out][ksize] with 22 fractional bits, unused taps 0; any ksize >= 1.  One pass is
+ *   clamp((2^21 + sum_k src[first + k] * coeffs[k]) >> 22, 0, 255) per channel in int32; the horizontal pass runs first and is rounded
+ *   to uint8 into `workspace` ([Hs][Wd][3], xmem_resize_u8_workspace_bytes), the vertical pass runs on that.  A pass whose sizes are
+ *   equal is skipped (its tables may be NULL); when neither axis changes one copy (or mirror) kernel runs.  Windows are clamped to the
+ *   source, so a wrong table cannot read out of bounds.  Integer arithmetic only, no atomics: bit-reproducible.
+ * Every side in [1, 16384] (else XMEM_ERR_UNSUPPORTED, before any GPU work; the workspace query returns 0). */
+size_t xmem_resize_u8_workspace_bytes(int Hs, int Ws, int Hd, int Wd);
+int xmem_resize_u8_bilinear_aa(const uint8_t* src, int Hs, int Ws, uint8_t* dst, int Hd, int Wd, int flip, const int32_t* xbounds,
+                               const int32_t* xcoeffs, int xksize, const int32_t* ybounds, const int32_t* ycoeffs, int yksize,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

@@ -45,10 +45,17 @@ def extract_keys(dataloder, processor, print_progress=False, flatten=True, **kwa
     device, key_sum, ti = None, None, -1
     dev = processor.network.device
     for ti, data in enumerate(dataloder):
-        rgb = _rgb_of(data)
-        if rgb.dim() == 4:                       # a DataLoader adds a batch dimension
-            rgb = rgb[0]
-        key, shrinkage, selection = processor.encode_frame_key(rgb.to(dev, non_blocking=True))
+        if getattr(data, 'rgb_u8', 0) is None and getattr(data, 'src_u8', None) is not None:
+            # a reader made with resize_on_device=True: the source-size frame, resized to the working size on the device
+            rgb = data.src_u8.to(dev, non_blocking=True)
+            if tuple(rgb.shape[:2]) != tuple(data.target_hw):
+                rgb = ops.resize_u8(rgb, data.target_hw)
+        else:
+            rgb = _rgb_of(data)
+            if rgb.dim() == 4:                   # a DataLoader adds a batch dimension
+                rgb = rgb[0]
+            rgb = rgb.to(dev, non_blocking=True)
+        key, shrinkage, selection = processor.encode_frame_key(rgb)
         if key_sum is None:
             device = key.device
             key_sum = torch.zeros(key.shape, device=device, dtype=torch.float64)

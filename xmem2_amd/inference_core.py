@@ -162,8 +162,49 @@ class InferenceCore:
         the next `step()`."""
         return self.prefetch_keys([image], inputs_complete=inputs_complete)[0]
 
+    def _pipelined(self):
+        net = self.network
+        return getattr(net, 'use_graphs', False) and net.device.type == 'cuda' and not ops.eager_only()
+
+    def _side_stream(self):
+        if self._side is None:
+            self._side = _net_stream(self.network, 'side', lambda: ops.side_stream(self.network.device))
+        return self._side
+
     @_on_network_device
-    def prefetch_keys(self, images, inputs_complete=False):
+    def upload_frames(self, images):
+        """Host (pinned) frames -> device tensors, copied on the stream `prefetch_keys` works on (the side stream; the caller's
+        current stream when the core runs eagerly).  For a caller that makes several working-size variants of one uploaded frame -
+        the ensemble hands the result to `prefetch_keys(..., working_size=..., inputs_complete=True)` of each of its cores: the
+        copies are already ordered in front of those passes.
+        ONLY for that use: the tensors are written on the side stream, so until it has caught up they are complete for nothing but a
+        `prefetch_keys` of a core on the SAME network (cores of one network share the side stream); anything on another stream - a
+        `step()` without a hint, `ops.resize_u8` on the caller's stream - must first wait for that stream."""
+        dev = self.network.device
+        if not self._pipelined():
+            return [im.to(dev) if not im.is_cuda else im for im in images]
+        with torch.cuda.stream(self._side_stream()):
+            return [im.to(dev, non_blocking=True) if not im.is_cuda else im for im in images]
+
+    def _resize_inputs(self, srcs, working_size, flip, reader_stream=None):
+        """Source-size uint8 device frames -> the working-size (mirrored if asked) frames, on the current stream.  A frame that needs
+        neither is passed through.  `reader_stream`: the stream this runs on when it is not the one the sources were made on - their
+        memory must not be reused before the resize has read it."""
+        th, tw = int(working_size[0]), int(working_size[1])
+        out = []
+        for s in srcs:
+            if s.dtype != torch.uint8 or s.dim() != 3 or s.shape[2] != 3:
+                raise ValueError('prefetch_keys: working_size needs decoded H x W x 3 uint8 frames')
+            if (s.shape[0], s.shape[1]) == (th, tw) and not flip:
+                out.append(s)
+                continue
+            out.append(ops.resize_u8(s.contiguous(), (th, tw), flip=flip))
+            if reader_stream is not None:
+                s.record_stream(reader_stream)
+        return out
+
+    @_on_network_device
+    def prefetch_keys(self, images, inputs_complete=False, working_size=None, flip=False):
         """Enqueue ONE batched key-encoder pass for the next `len(images)` frames on a side stream.
 
         The key encoder depends on nothing but the image, so a streaming caller that already holds the coming frames
@@ -178,18 +219,26 @@ class InferenceCore:
         CALLER's current stream, so a tensor the caller has just produced there (a `.clone()`, a resize, an H2D copy) is complete when
         the pass reads it.  `inputs_complete=True` skips that wait for callers whose inputs were finished long ago (resident clips):
         the pass may then start under the frame that is still being decoded.  (Round 6: bench.py's parity leg handed over clones that
-        were still being written on the main stream - the 'unexplained wrong stream' of round 5)"""
+        were still being written on the main stream - the 'unexplained wrong stream' of round 5)
+
+        `working_size=(th, tw)` (and `flip`): frame ingest on the device.  `images` are then the decoded SOURCE-size H x W x 3 uint8
+        frames; the copy and the resize to the working size (`ops.resize_u8`: the host library's antialiased bilinear resize byte for
+        byte, columns mirrored when `flip`) are enqueued on the same side stream in front of the pack kernel, never on the caller's
+        stream, and the call returns the working-size device tensors.  The source-size device buffers are released right after the
+        resize (a caller's device tensors are marked as read by the side stream, `record_stream`)."""
         net = self.network
         images = list(images)
         if not images:
             return []
-        if not (getattr(net, 'use_graphs', False) and net.device.type == 'cuda') or ops.eager_only():
-            return [im.to(net.device) if not im.is_cuda else im for im in images]
+        if (working_size is None and flip) or (working_size is not None and len(working_size) != 2):
+            raise ValueError('prefetch_keys: flip needs working_size=(th, tw)')
+        if not self._pipelined():
+            devs = [im.to(net.device) if not im.is_cuda else im for im in images]
+            return devs if working_size is None else self._resize_inputs(devs, working_size, flip)
         if any(tuple(im.shape) != tuple(images[0].shape) for im in images):
             raise ValueError('prefetch_keys: all frames of a batch must have the same shape')
         main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = _net_stream(net, 'side', lambda: ops.side_stream(net.device))
+        self._side_stream()
         if not inputs_complete and any(im.is_cuda for im in images):
             self._side.wait_stream(main)                         # producers of the inputs on the caller's stream
         B = len(images)
@@ -205,6 +254,8 @@ class InferenceCore:
         saved_pad = getattr(self, 'pad', None)
         with torch.cuda.stream(self._side):
             devs = [im.to(net.device, non_blocking=True) if not im.is_cuda else im for im in images]
+            if working_size is not None:
+                devs = self._resize_inputs(devs, working_size, flip, reader_stream=self._side)
             u8 = devs[0].dtype == torch.uint8
             H0, W0 = (devs[0].shape[0], devs[0].shape[1]) if u8 else devs[0].shape[-2:]
             lw_, uw_, lh_, uh_ = pad_amounts(H0, W0, 16)

@@ -363,7 +363,9 @@ def main(argv=None):
     ap.add_argument('--masks', default=None)
     ap.add_argument('--out', required=True)
     ap.add_argument('--frames-with-masks', default='0', help='comma-separated frame indices whose annotation is given')
-    ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG (overwrite_config)')
+    ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG (overwrite_config); opt-in switches '
+                                                     'are read from it too, e.g. \'{"resize_on_device": true}\' resizes the decoded frames '
+                                                     'to the working size on the GPU (same masks, byte for byte)')
     ap.add_argument('--compute-iou', action='store_true')
     ap.add_argument('--compute-jf', action='store_true', help='score every frame that has a ground truth: DAVIS J, F and J&F per video '
                                                                'and their dataset means in summary.json')

@@ -13,6 +13,7 @@ import threading
 import torch
 
 from . import _lib, conv_plan
+from .pil_resize import MAX_SIDE, taps
 from ._lib import AffinityHint, ConvDesc, KeySegment, ValueSegment, check, load, ptr, stream_ptr
 
 _workspaces = {}
@@ -627,6 +628,49 @@ def pack_image_u8(img, Hp, Wp, lh, lw, mean=IM_MEAN, std=IM_STD, out=None):
         out = torch.empty((1, Hp, Wp, 4), dtype=torch.float32, device=img.device)
     m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     check(load().xmem_pack_image_u8(ptr(img), ptr(out), img.shape[0], img.shape[1], Hp, Wp, lh, lw, m3, s3, stream_ptr()))
+    return out
+
+
+_resize_taps = {}       # (device, in, out) -> (bounds, coeffs, ksize) on the device: uploaded once per geometry
+
+
+def _device_taps(device, in_size, out_size):
+    key = (str(device), int(in_size), int(out_size))
+    t = _resize_taps.get(key)
+    if t is None:
+        bounds, coeffs = taps(in_size, out_size)
+        # a blocking copy: the tables are complete before any stream reads them, whichever stream is current now
+        t = (torch.from_numpy(bounds.copy()).to(device), torch.from_numpy(coeffs.copy()).to(device), int(coeffs.shape[1]))
+        _resize_taps[key] = t
+    return t
+
+
+def resize_u8(src, size, flip=False, out=None):
+    """decoded frame uint8 [H,W,3] -> uint8 [th,tw,3]: `Image.resize((tw, th), Image.BILINEAR)` of the host library byte for byte
+    (xmem2_amd/pil_resize.py states the arithmetic), columns mirrored when `flip`.  `out`: a contiguous uint8 [th,tw,3] tensor, e.g.
+    one frame of a batched buffer.  Launched on the current stream; the intermediate of the horizontal pass comes from the stream's
+    own allocator pool, so calls on different streams share no scratch."""
+    if not src.is_cuda or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or not src.is_contiguous():
+        raise RuntimeError('resize_u8: expected a contiguous CUDA (HIP) uint8 tensor of shape [H, W, 3]')
+    th, tw = int(size[0]), int(size[1])
+    if th < 1 or tw < 1:
+        raise RuntimeError(f'resize_u8: target size {(th, tw)} must be positive')
+    Hs, Ws = int(src.shape[0]), int(src.shape[1])
+    if max(Hs, Ws, th, tw) > MAX_SIDE:                 # what the C entry point answers, before any table is built or uploaded
+        check(_lib.UNSUPPORTED)
+    if out is None:
+        out = torch.empty((th, tw, 3), dtype=torch.uint8, device=src.device)
+    elif not out.is_cuda or out.device != src.device or out.dtype != torch.uint8 or tuple(out.shape) != (th, tw, 3) \
+            or not out.is_contiguous() or (out.data_ptr() < src.data_ptr() + src.numel() and src.data_ptr() < out.data_ptr() + out.numel()):
+        raise RuntimeError(f'resize_u8: out must be a contiguous uint8 CUDA (HIP) tensor of shape {(th, tw, 3)} that does not overlap '
+                           'the input')
+    lib = load()
+    xb, xc, xk = _device_taps(src.device, Ws, tw) if Ws != tw else (None, None, 0)
+    yb, yc, yk = _device_taps(src.device, Hs, th) if Hs != th else (None, None, 0)
+    nbytes = lib.xmem_resize_u8_workspace_bytes(Hs, Ws, th, tw)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if nbytes else None
+    check(lib.xmem_resize_u8_bilinear_aa(ptr(src), Hs, Ws, ptr(out), th, tw, int(bool(flip)), ptr(xb), ptr(xc), xk, ptr(yb), ptr(yc), yk,
+                                         ptr(ws), nbytes, stream_ptr()))
     return out
 
 

@@ -40,8 +40,10 @@ IM_STD = np.array([0.229, 0.224, 0.225], np.float32)
 class Sample:
     """inference/data/video_reader.py:20-28.  `rgb_u8` is the decoded (and, if asked, resized) H x W x 3 uint8 frame;
     `rgb` - the reference's normalised 3 x H x W float tensor - is derived from it on first use (the harness itself
-    hands `rgb_u8` to the device, where ToTensor + Normalize + padding are one kernel)."""
-    rgb_u8: torch.Tensor
+    hands `rgb_u8` to the device, where ToTensor + Normalize + padding are one kernel).
+    A reader made with `resize_on_device=True` does not resize: `rgb_u8` is None, `src_u8` is the decoded SOURCE-size frame and
+    `target_hw` the working size the device resizes it to (`ops.resize_u8`, the same bytes as the host resize)."""
+    rgb_u8: Optional[torch.Tensor]
     raw_image_pil: object
     frame: str
     save: bool
@@ -49,11 +51,18 @@ class Sample:
     need_resize: bool
     mask: Optional[np.ndarray] = None
     _rgb: Optional[torch.Tensor] = None
+    src_u8: Optional[torch.Tensor] = None
+    target_hw: Optional[tuple] = None
 
     @property
     def rgb(self):
         if self._rgb is None:
-            arr = (self.rgb_u8.numpy().astype(np.float32) / 255.0 - IM_MEAN) / IM_STD
+            if self.rgb_u8 is None:                      # resize_on_device: the host restatement of the same resize
+                from .pil_resize import resize_u8_host
+                u8 = resize_u8_host(self.src_u8.numpy(), *self.target_hw)
+            else:
+                u8 = self.rgb_u8.numpy()
+            arr = (u8.astype(np.float32) / 255.0 - IM_MEAN) / IM_STD
             self._rgb = torch.from_numpy(np.ascontiguousarray(arr.transpose(2, 0, 1)))
         return self._rgb
 
@@ -61,8 +70,9 @@ class Sample:
 class VideoReader:
     """Directory-of-frames reader (inference/data/video_reader.py:31-118 without cv2 / torchvision)."""
 
-    def __init__(self, vid_name, video_path, mask_dir, size=-1, use_all_masks=False):
+    def __init__(self, vid_name, video_path, mask_dir, size=-1, use_all_masks=False, resize_on_device=False):
         from PIL import Image
+        self.resize_on_device = bool(resize_on_device)
         self._Image = Image
         if os.path.isfile(video_path):
             raise NotImplementedError('video files need cv2 for frame extraction; pass a directory of frames')
@@ -92,12 +102,21 @@ class VideoReader:
         work = img if (th, tw) == shape else img.resize((tw, th), Image.BILINEAR)
         return torch.from_numpy(np.array(work, dtype=np.uint8))                   # owns its memory
 
+    def frame_src_u8(self, img):
+        """PIL RGB image -> (the decoded source-size H x W x 3 uint8 tensor, the working size (th, tw) it is resized to on the
+        device): `frame_u8` without the resize."""
+        return torch.from_numpy(np.array(img, dtype=np.uint8)), self._target_hw(img.size[1], img.size[0])
+
     def __getitem__(self, idx) -> Sample:
         Image = self._Image
         name = self.frames[idx]
         img = Image.open(os.path.join(self.image_dir, name)).convert('RGB')
         shape = (img.size[1], img.size[0])
-        rgb_u8 = self.frame_u8(img)
+        rgb_u8 = src_u8 = target_hw = None
+        if self.resize_on_device:
+            src_u8, target_hw = self.frame_src_u8(img)
+        else:
+            rgb_u8 = self.frame_u8(img)
         gt_path = os.path.join(self.mask_dir, name[:-4] + '.png')
         if not os.path.exists(gt_path):
             gt_path = os.path.join(self.mask_dir, name[:-4] + '.PNG')
@@ -105,7 +124,7 @@ class VideoReader:
         if (self.use_all_masks or gt_path == self.first_gt_path) and os.path.exists(gt_path):
             mask = np.array(Image.open(gt_path).convert('P'), dtype=np.uint8)
         return Sample(rgb_u8=rgb_u8, raw_image_pil=img, frame=name, save=True, shape=shape,
-                      need_resize=not (self.size < 0), mask=mask)
+                      need_resize=not (self.size < 0), mask=mask, src_u8=src_u8, target_hw=target_hw)
 
     def resize_mask(self, onehot):
         """nearest resize of a [K,H,W] one-hot mask to the working size (video_reader.py:148-153)."""
@@ -174,7 +193,10 @@ class FramePrefetcher:
 
     def _load(self, idx):
         smp = self.reader[idx]
-        smp.rgb_u8 = smp.rgb_u8.pin_memory()
+        if smp.rgb_u8 is None:                                   # resize_on_device: the source-size frame travels
+            smp.src_u8 = smp.src_u8.pin_memory()
+        else:
+            smp.rgb_u8 = smp.rgb_u8.pin_memory()
         return smp
 
     def _top_up(self):
@@ -257,12 +279,22 @@ def _post_process(sample, prob):
     return ops.argmax_u8(prob).cpu().numpy()
 
 
+def _working_u8(src_u8, target_hw, device, flip=False):
+    """resize_on_device outside the frame loop (preloads, key extraction): upload a source-size frame (or take a device one) and
+    resize it on the current stream."""
+    dev = src_u8.to(device)
+    if tuple(dev.shape[:2]) == tuple(target_hw) and not flip:
+        return dev
+    return ops.resize_u8(dev, target_hw, flip=flip)
+
+
 def _load_main_objects(imgs_in_path, masks_in_path, config, device):
     model_path = config['model']
     network = XMem(config, model_path, pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
     if model_path is None:
         warn('No model weights were loaded, as config["model"] was not specified.')
-    vid_reader = VideoReader('', imgs_in_path, masks_in_path, size=config['size'], use_all_masks=True)
+    vid_reader = VideoReader('', imgs_in_path, masks_in_path, size=config['size'], use_all_masks=True,
+                             resize_on_device=config.get('resize_on_device', False))
     vid_length = len(vid_reader)
     config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196
         config['enable_long_term'] and
@@ -303,6 +335,9 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         if sample.need_resize:
             msk = vid_reader.resize_mask(msk)
         processor.set_all_labels(list(mapper.remappings.values()))
+        # Opt-in (config['resize_on_device'] = True; default False): the reader hands over source-size frames and the working-size resize
+        # runs on the device, in the host library's integer arithmetic - the same bytes, hence the same masks.
+        dev_resize = sample.rgb_u8 is None
         a = perf_counter()
         # Opt-in (config['augment_on_device'] = True; default False): the device path is pinned to this repo's host restatement only
         # to float ties (blur within 1 LSB, < 2e-4 of the pixels of the nearest-sampling transforms, batched conv plans ~2e-4), and the
@@ -313,20 +348,25 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
             # batched key + value pass (the reference runs 12 sequential passes over host-side PIL transforms, :231-242).
             # With a working-size resize the reference augments BEFORE resizing: that case keeps the host path below.
             from .augmentations import augment_on_device
-            rgb_dev, msk_dev = sample.rgb_u8.to(device), msk.to(device)
+            rgb_dev = _working_u8(sample.src_u8, sample.target_hw, device) if dev_resize else sample.rgb_u8.to(device)
+            msk_dev = msk.to(device)
             aug_rgb, aug_msk = augment_on_device(rgb_dev, msk_dev, subset='best_all')
             processor.put_many_to_permanent_memory([rgb_dev] + [aug_rgb[i] for i in range(aug_rgb.shape[0])], [msk_dev] + aug_msk)
         else:
-            processor.put_to_permanent_memory(sample.rgb_u8.to(device), msk.to(device))
+            rgb_dev = _working_u8(sample.src_u8, sample.target_hw, device) if dev_resize else sample.rgb_u8.to(device)
+            processor.put_to_permanent_memory(rgb_dev, msk.to(device))
         torch.cuda.synchronize()
         preload_time += perf_counter() - a
         loaded = True
         if augment_images_with_masks and not on_device:              # run_on_video.py:231-242, subset 'best_all' (host path)
             from .augmentations import get_determenistic_augmentations
-            h, w = sample.rgb_u8.shape[:2]
+            h, w = sample.target_hw if dev_resize else sample.rgb_u8.shape[:2]
             for img_aug, mask_aug in get_determenistic_augmentations((3, h, w), msk, subset='best_all'):
-                rgb_aug = vid_reader.frame_u8(img_aug(sample.raw_image_pil))
-                processor.put_to_permanent_memory(rgb_aug.to(device), mask_aug(msk).to(device))
+                if dev_resize:                                       # augmented at the source size on the host, resized on the device
+                    rgb_aug = _working_u8(*vid_reader.frame_src_u8(img_aug(sample.raw_image_pil)), device)
+                else:
+                    rgb_aug = vid_reader.frame_u8(img_aug(sample.raw_image_pil)).to(device)
+                processor.put_to_permanent_memory(rgb_aug, mask_aug(msk).to(device))
     if not loaded:
         raise ValueError('No valid masks provided!')
 
@@ -363,7 +403,10 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
             return
         n = key_batch if remaining >= key_batch else 1               # the tail goes frame by frame (no new graph shapes)
         samples = decoder.get(n)
-        devs = processor.prefetch_keys([smp.rgb_u8 for smp in samples])   # uint8 H2D + normalise + key encoder, side stream
+        if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
+            devs = processor.prefetch_keys([smp.src_u8 for smp in samples], working_size=samples[0].target_hw)
+        else:
+            devs = processor.prefetch_keys([smp.rgb_u8 for smp in samples])   # uint8 H2D + normalise + key encoder, side stream
         pending.extend(zip(samples, devs))
         next_idx += n
 
@@ -463,13 +506,16 @@ def _mirror(a):
 @dataclass
 class EnsembleSample:
     """One decoded frame and its per-pass inputs: `rgb_u8[p]` is pass p's working-size (mirrored if asked) uint8 frame, `mask` the
-    annotation's raw index array at the ORIGINAL resolution (each pass mirrors it before its own convert / resize)."""
-    rgb_u8: list
+    annotation's raw index array at the ORIGINAL resolution (each pass mirrors it before its own convert / resize).  With
+    `resize_on_device` readers `rgb_u8` is None and `src_u8` the one decoded source-size frame every variant is made from on the
+    device."""
+    rgb_u8: Optional[list]
     raw_image_pil: object
     frame: str
     save: bool
     shape: tuple
     mask: Optional[np.ndarray] = None
+    src_u8: Optional[torch.Tensor] = None
 
 
 class EnsembleFramePrefetcher(FramePrefetcher):
@@ -486,6 +532,9 @@ class EnsembleFramePrefetcher(FramePrefetcher):
 
     def _load(self, idx):
         base = self.reader[idx]                                   # decode + the first pass's size (+ the raw annotation)
+        if base.rgb_u8 is None:                                   # resize_on_device: one source frame, the variants are made on the device
+            return EnsembleSample(rgb_u8=None, raw_image_pil=base.raw_image_pil, frame=base.frame, save=base.save, shape=base.shape,
+                                  mask=base.mask, src_u8=base.src_u8)
         by_size = {self.passes[0][0]: base.rgb_u8}
         variants = {}
         for s, f in self.passes:
@@ -500,6 +549,9 @@ class EnsembleFramePrefetcher(FramePrefetcher):
     def get(self, n):
         out = super().get(n)
         for smp in out:
+            if smp.rgb_u8 is None:
+                smp.src_u8 = smp.src_u8.pin_memory()
+                continue
             pinned = {}
             for t in smp.rgb_u8:
                 if id(t) not in pinned:
@@ -544,10 +596,11 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     network = XMem(config, model_path, pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
     if model_path is None:
         warn('No model weights were loaded, as config["model"] was not specified.')
+    dev_resize = bool(config.get('resize_on_device', False))        # opt-in: one decode, one upload, every (size, flip) variant by kernel
     readers = {}
     for s, _ in passes:
         if s not in readers:
-            readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True)
+            readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True, resize_on_device=dev_resize)
     vid_reader = readers[passes[0][0]]
     vid_length = len(vid_reader)
     config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196, once for all passes
@@ -576,10 +629,16 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             continue
         by_size = {passes[0][0]: sample.rgb_u8}
         a = perf_counter()
+        src_dev, variants = (sample.src_u8.to(device), {}) if dev_resize else (None, None)
         for p, (s, f) in enumerate(passes):
-            if s not in by_size:
-                by_size[s] = readers[s].frame_u8(sample.raw_image_pil)
-            rgb = torch.from_numpy(_mirror(by_size[s].numpy())) if f else by_size[s]
+            if dev_resize:
+                if (s, f) not in variants:
+                    variants[(s, f)] = _working_u8(src_dev, readers[s]._target_hw(*sample.shape), device, flip=f)
+                rgb = variants[(s, f)]
+            else:
+                if s not in by_size:
+                    by_size[s] = readers[s].frame_u8(sample.raw_image_pil)
+                rgb = torch.from_numpy(_mirror(by_size[s].numpy())) if f else by_size[s]
             cores[p].set_all_labels(list(mappers[p].remappings.values()))
             cores[p].put_to_permanent_memory(rgb.to(device), per_pass[p][0].to(device))
         torch.cuda.synchronize()
@@ -623,7 +682,20 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             return
         n = key_batch if remaining >= key_batch else 1
         samples = decoder.get(n)
-        devs = [cores[p].prefetch_keys([smp.rgb_u8[p] for smp in samples]) for p in range(P)]   # each core hints its own variants
+        if dev_resize:
+            # one upload per frame; the first pass of each (size, flip) makes that variant on the side stream (copy, resize / mirror and
+            # key pass are stream-ordered there: inputs_complete), later passes with the same variant hint the same tensors
+            srcs = cores[0].upload_frames([smp.src_u8 for smp in samples])
+            made, devs = {}, []
+            for p, (s, f) in enumerate(passes):
+                if (s, f) not in made:
+                    made[(s, f)] = cores[p].prefetch_keys(srcs, inputs_complete=True, flip=f,
+                                                          working_size=readers[s]._target_hw(*samples[0].shape))
+                else:
+                    cores[p].prefetch_keys(made[(s, f)], inputs_complete=True)
+                devs.append(made[(s, f)])
+        else:
+            devs = [cores[p].prefetch_keys([smp.rgb_u8[p] for smp in samples]) for p in range(P)]   # each core hints its own variants
         pending.extend((smp, [devs[p][i] for p in range(P)]) for i, smp in enumerate(samples))
         next_idx += n
 
@@ -716,7 +788,7 @@ def select_k_next_best_annotation_candidates(imgs_in_path, masks_in_path, masks_
     device = torch.device('cuda', torch.cuda.current_device())
     config = dict(VIDEO_INFERENCE_CONFIG)
     config.update(kwargs.get('overwrite_config') or {})     # the reference extracts keys with the default config
-    _, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device)
+    _, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device)   # honours config['resize_on_device']
     frame_keys, shrinkages, selections, *_ = extract_keys(vid_reader, processor, print_progress=print_progress,
                                                           flatten=False, keep_on_device=True)
     tmp = None
