@@ -623,6 +623,14 @@ int xmem_selector_prepare(const float* key, const float* sel, const float* mask,
                           int h, int w, int Ck, float alpha, float one_minus_alpha, float eps,
                           float* Mexp, float* Qexp, float* bsq, int32_t* presence, void* stream);
 
+/* xmem_selector_prepare for a mask held as a uint8 label plane [H][W] and a 256-entry table: the mask value of a pixel is
+ * lut[label] (the max over channels of the float mask the table stands for), read at the same nearest-neighbour source pixel;
+ * presence receives #{pixels of the full plane with lut[label] > eps}.  Every output is bit-identical to xmem_selector_prepare
+ * on that float mask.  mask and lut must not be NULL. */
+int xmem_selector_prepare_u8(const float* key, const float* sel, const uint8_t* mask, const float* lut, int H, int W,
+                             int h, int w, int Ck, float alpha, float one_minus_alpha, float eps,
+                             float* Mexp, float* Qexp, float* bsq, int32_t* presence, void* stream);
+
 /* Cycle dissimilarity of every frame f against frame `chosen` (frame_selection.py:218-226):
  *   out[f] = sum_{i,j} relu( S(mem=c_chosen[i], ms=s_chosen[i]; q=c_f[j], qe=e_f[j])
  *                          - S(mem=c_f[i],      ms=s_f[i];      q=c_chosen[j], qe=e_chosen[j]) ) / HW^2

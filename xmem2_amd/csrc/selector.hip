@@ -18,6 +18,27 @@
 // ---------------------------------------------------------------------------------------------
 // prepare: composite key + expanded operands + mask presence count for one frame
 // ---------------------------------------------------------------------------------------------
+// One key-map pixel p on one wave, given its mask weight m (shared by the float-mask and the label-plane kernels: same
+// operations in the same order, hence the same bits).
+__device__ __forceinline__ void selector_prepare_pixel(const float* __restrict__ key, const float* __restrict__ sel, bool has_mask,
+                                                       float m, int p, int lane, int Ck, float alpha, float one_minus_alpha,
+                                                       float* __restrict__ Mexp, float* __restrict__ Qexp, float* __restrict__ bsq) {
+    float bs = 0.f;
+    for (int c = lane; c < Ck; c += 64) {
+        const float k = key[(size_t)p * Ck + c];
+        float ck = k;
+        if (has_mask) ck = __fadd_rn(__fmul_rn(__fmul_rn(k, m), alpha), __fmul_rn(k, one_minus_alpha));
+        const float e = sel[(size_t)p * Ck + c];
+        Mexp[(size_t)p * 2 * Ck + c] = ck * ck;
+        Mexp[(size_t)p * 2 * Ck + Ck + c] = ck;
+        Qexp[(size_t)p * 2 * Ck + c] = -e;
+        Qexp[(size_t)p * 2 * Ck + Ck + c] = 2.f * (ck * e);
+        bs += e * (ck * ck);
+    }
+    bs = wave_sum(bs);
+    if (lane == 0) bsq[p] = bs;
+}
+
 // key/sel: [HW][Ck] rows; mask: [C][H][W] float (or NULL => composite = key); nearest resize to h x w as
 // torch.nn.functional.interpolate(mode='nearest') (src = min(floor(dst * (in/out)), in-1), scale in fp32);
 // composite = (key * m) * alpha + key * (1 - alpha) with separately rounded products (frame_selection.py:183-184).
@@ -37,20 +58,24 @@ __global__ void selector_prepare_kernel(const float* __restrict__ key, const flo
         m = mask[(size_t)yy * W + xx];
         for (int c = 1; c < C; ++c) m = fmaxf(m, mask[((size_t)c * H + yy) * W + xx]);
     }
-    float bs = 0.f;
-    for (int c = lane; c < Ck; c += 64) {
-        const float k = key[(size_t)p * Ck + c];
-        float ck = k;
-        if (mask) ck = __fadd_rn(__fmul_rn(__fmul_rn(k, m), alpha), __fmul_rn(k, one_minus_alpha));
-        const float e = sel[(size_t)p * Ck + c];
-        Mexp[(size_t)p * 2 * Ck + c] = ck * ck;
-        Mexp[(size_t)p * 2 * Ck + Ck + c] = ck;
-        Qexp[(size_t)p * 2 * Ck + c] = -e;
-        Qexp[(size_t)p * 2 * Ck + Ck + c] = 2.f * (ck * e);
-        bs += e * (ck * ck);
-    }
-    bs = wave_sum(bs);
-    if (lane == 0) bsq[p] = bs;
+    selector_prepare_pixel(key, sel, mask != nullptr, m, p, lane, Ck, alpha, one_minus_alpha, Mexp, Qexp, bsq);
+}
+
+// The same for a mask that arrives as a uint8 label plane [H][W] and a 256-entry table: m = lut[label] (the float mask the table stands
+// for, max over channels already folded in); the source pixel is the one the float kernel reads.
+__global__ void selector_prepare_u8_kernel(const float* __restrict__ key, const float* __restrict__ sel,
+                                           const uint8_t* __restrict__ mask, const float* __restrict__ lut, int H, int W, int h, int w,
+                                           int Ck, float alpha, float one_minus_alpha,
+                                           float* __restrict__ Mexp, float* __restrict__ Qexp, float* __restrict__ bsq) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int p = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (p >= h * w) return;
+    const int y = p / w, x = p % w;
+    const float sy = (float)H / (float)h, sx = (float)W / (float)w;
+    const int yy = min((int)floorf((float)y * sy), H - 1);
+    const int xx = min((int)floorf((float)x * sx), W - 1);
+    const float m = lut[mask[(size_t)yy * W + xx]];
+    selector_prepare_pixel(key, sel, true, m, p, lane, Ck, alpha, one_minus_alpha, Mexp, Qexp, bsq);
 }
 
 // count of pixels whose max-over-channels mask value exceeds eps (frame_selection.py:161-163)
@@ -80,6 +105,48 @@ extern "C" int xmem_selector_prepare(const float* key, const float* sel, const f
         }
     }
     hipLaunchKernelGGL(selector_prepare_kernel, dim3(cdiv(h * w, 4)), dim3(256), 0, st, key, sel, mask, C, H, W, h, w, Ck,
+                       alpha, one_minus_alpha, Mexp, Qexp, bsq);
+    return xmem_check_launch();
+}
+
+// count of labels v of the full plane with lut[v] > eps.  `vec`: the plane starts on a 4-byte boundary - four labels per load, the
+// last HW % 4 one by one.
+__global__ void mask_presence_u8_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ lut, int HW, float eps, int vec,
+                                        int* __restrict__ count) {
+    __shared__ uint8_t on[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) on[i] = (lut[i] > eps) ? 1 : 0;
+    __syncthreads();
+    int local = 0;
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+    int done = 0;
+    if (vec) {
+        const int n4 = HW >> 2;
+        const uint32_t* m4 = reinterpret_cast<const uint32_t*>(mask);
+        for (int i = tid; i < n4; i += nth) {
+            const uint32_t v = m4[i];
+            local += on[v & 255u] + on[(v >> 8) & 255u] + on[(v >> 16) & 255u] + on[v >> 24];
+        }
+        done = n4 << 2;
+    }
+    for (int i = done + tid; i < HW; i += nth) local += on[mask[i]];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, 64);
+    if ((threadIdx.x & 63) == 0 && local) atomicAdd(count, local);
+}
+
+extern "C" int xmem_selector_prepare_u8(const float* key, const float* sel, const uint8_t* mask, const float* lut, int H, int W,
+                                        int h, int w, int Ck, float alpha, float one_minus_alpha, float eps,
+                                        float* Mexp, float* Qexp, float* bsq, int32_t* presence, void* stream) {
+    if (!key || !sel || !mask || !lut || !Mexp || !Qexp || !bsq || h <= 0 || w <= 0 || Ck <= 0 || H <= 0 || W <= 0) return XMEM_ERR_BAD_ARG;
+    if ((long long)H * W > 0x7fffffffLL || (long long)h * w > 0x7fffffffLL) return XMEM_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (presence) {
+        if (hipMemsetAsync(presence, 0, sizeof(int32_t), st) != hipSuccess) return XMEM_ERR_LAUNCH;
+        const int HWf = H * W;
+        const int vec = (((uintptr_t)mask & 3u) == 0) ? 1 : 0;
+        hipLaunchKernelGGL(mask_presence_u8_kernel, dim3(min(cdiv(HWf, 1024), 1024)), dim3(256), 0, st, mask, lut, HWf, eps, vec, presence);
+    }
+    hipLaunchKernelGGL(selector_prepare_u8_kernel, dim3(cdiv(h * w, 4)), dim3(256), 0, st, key, sel, mask, lut, H, W, h, w, Ck,
                        alpha, one_minus_alpha, Mexp, Qexp, bsq);
     return xmem_check_launch();
 }

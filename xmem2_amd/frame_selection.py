@@ -100,6 +100,28 @@ class SelectorState:
             ops.selector_prepare(key_rows[i], sel_rows[i], m, h, w, alpha, epsilon,
                                  self.Mexp[i], self.Qexp[i], self.bsq[i], self.presence[i:i + 1])
 
+    @classmethod
+    def from_label_planes(cls, key_rows, shr_rows, sel_rows, grid_hw, masks_u8, lut, alpha, epsilon):
+        """The same operands from device-resident state, without a host copy or a float mask: key_rows / sel_rows [F, h*w, C_k] and
+        shr_rows [F, h*w] (contiguous float32, as the key encoder wrote them), masks_u8 [F, H, W] uint8 label planes and the
+        256-entry float table that gives a label its mask value (`ops.selector_prepare_u8`: bit-identical to `__init__` on the float
+        masks `lut[masks_u8]`).  The arrays are used in place."""
+        self = cls.__new__(cls)
+        F_, hw, ck = key_rows.shape
+        h, w = grid_hw
+        device = key_rows.device
+        self.n, self.h, self.w, self.ck = F_, h, w, ck
+        self.shr = shr_rows
+        self.Mexp = torch.empty((F_, hw, 2 * ck), dtype=torch.float32, device=device)
+        self.Qexp = torch.empty_like(self.Mexp)
+        self.bsq = torch.empty((F_, hw), dtype=torch.float32, device=device)
+        self.presence = torch.zeros((F_,), dtype=torch.int32, device=device)
+        self.mask_numel = [masks_u8.shape[1] * masks_u8.shape[2]] * F_
+        for i in range(F_):
+            ops.selector_prepare_u8(key_rows[i], sel_rows[i], masks_u8[i], lut, h, w, alpha, epsilon,
+                                    self.Mexp[i], self.Qexp[i], self.bsq[i], self.presence[i:i + 1])
+        return self
+
     def scores_against(self, chosen, valid_dev=None):
         """float32 [F] on the device: cycle dissimilarity of every frame vs frame `chosen`."""
         return ops.cycle_dissimilarity(self.Mexp, self.Qexp, self.bsq, self.shr, chosen, valid_dev).to(torch.float32)
@@ -126,33 +148,39 @@ def select_next_candidates(keys: torch.Tensor, shrinkages, selections, masks: Li
         raise RuntimeError('select_next_candidates: xmem2_amd has no CPU path (device must be a HIP device)')
     with torch.no_grad(), torch.cuda.device(device):
         state = SelectorState(keys, shrinkages, selections, masks, alpha, epsilon, device)
-        n = state.n
-        # mask presence test (frame_selection.py:161-176): the percentage is formed in fp32 as in the reference
-        counts = state.presence.cpu()
-        numel = torch.tensor(state.mask_numel, dtype=torch.int64)
-        percent = counts.to(torch.int64) / numel * 100
-        valid = (percent >= min_mask_presence_percent).numpy().copy()
-        for i in previously_chosen_candidates:
-            valid[i] = True
-        print(f"Frames with invalid (empty or too small) masks: {int((~valid).sum())} / {len(masks)}")
-        valid_dev = torch.from_numpy(valid.astype(np.uint8)).to(device)
+        return greedy_selection(state, num_next_candidates, previously_chosen_candidates, min_mask_presence_percent, device,
+                                progress_callback=progress_callback, only_new_candidates=only_new_candidates)
 
-        chosen = list(previously_chosen_candidates)
-        running = None
-        trace = []
-        for m in chosen:
-            d = state.scores_against(m, valid_dev)
-            running = d if running is None else torch.minimum(running, d)
-        for i in range(num_next_candidates):
-            scores = running.cpu()               # invalid frames are already 0 (frame_selection.py:201-203)
-            trace.append(scores.numpy().copy())
-            new = int(torch.argmax(scores))      # host argmax on the fp32 scores: same tie rule as the reference
-            chosen.append(new)
-            if i + 1 < num_next_candidates:
-                running = torch.minimum(running, state.scores_against(new, valid_dev))
-            if progress_callback is not None:
-                progress_callback.emit(i + 1)
-        select_next_candidates.last_scores = trace   # per-iteration candidate scores (diagnostics / tests)
-        if only_new_candidates:
-            chosen = chosen[len(previously_chosen_candidates):]
-        return chosen
+
+def greedy_selection(state, num_next_candidates, previously_chosen_candidates, min_mask_presence_percent, device,
+                     progress_callback=None, only_new_candidates=True):
+    """The selection itself (frame_selection.py:156-244) on prepared operands; leaves `select_next_candidates.last_scores`."""
+    # mask presence test (frame_selection.py:161-176): the percentage is formed in fp32 as in the reference
+    counts = state.presence.cpu()
+    numel = torch.tensor(state.mask_numel, dtype=torch.int64)
+    percent = counts.to(torch.int64) / numel * 100
+    valid = (percent >= min_mask_presence_percent).numpy().copy()
+    for i in previously_chosen_candidates:
+        valid[i] = True
+    print(f"Frames with invalid (empty or too small) masks: {int((~valid).sum())} / {state.n}")
+    valid_dev = torch.from_numpy(valid.astype(np.uint8)).to(device)
+
+    chosen = list(previously_chosen_candidates)
+    running = None
+    trace = []
+    for m in chosen:
+        d = state.scores_against(m, valid_dev)
+        running = d if running is None else torch.minimum(running, d)
+    for i in range(num_next_candidates):
+        scores = running.cpu()               # invalid frames are already 0 (frame_selection.py:201-203)
+        trace.append(scores.numpy().copy())
+        new = int(torch.argmax(scores))      # host argmax on the fp32 scores: same tie rule as the reference
+        chosen.append(new)
+        if i + 1 < num_next_candidates:
+            running = torch.minimum(running, state.scores_against(new, valid_dev))
+        if progress_callback is not None:
+            progress_callback.emit(i + 1)
+    select_next_candidates.last_scores = trace   # per-iteration candidate scores (diagnostics / tests)
+    if only_new_candidates:
+        chosen = chosen[len(previously_chosen_candidates):]
+    return chosen

@@ -33,10 +33,12 @@ def _on_network_device(fn):
     return wrapper
 
 
-def _release_core(network, uid, inflight):
+def _release_core(network, uid, inflight, group_free=None):
     """Finalizer of an InferenceCore: work it enqueued on the side / readout streams (a batched key pass into the network's shared
-    key-stage buffers, a readout into a decoder stage's static input) must be over before its owner token is recycled."""
-    for ev in inflight.values():
+    key-stage buffers, a readout into a decoder stage's static input) must be over before its owner token is recycled - and so must
+    the main-stream readers of its key-stage buffers (`_group_free`): the next owner of the token starts with no such events and, with
+    pinned host inputs, its first `prefetch_keys` does not wait for the main stream either."""
+    for ev in list(inflight.values()) + list((group_free or {}).values()):
         if ev is not None:
             try:
                 ev.synchronize()
@@ -84,7 +86,7 @@ class InferenceCore:
         # owner token of this core's captured decoder stages (they update ITS hidden state in place); recycled when the core dies
         if hasattr(network, 'acquire_owner'):
             self._uid = network.acquire_owner()
-            weakref.finalize(self, _release_core, network, self._uid, self._inflight)
+            weakref.finalize(self, _release_core, network, self._uid, self._inflight, self._group_free)
         else:
             self._uid = id(self)
         # warm-up on the network's own device (the reference hard-codes cuda:0, inference_core.py:26)
@@ -383,6 +385,9 @@ class InferenceCore:
                 mem.set_hidden(hidden)
                 self.last_deep_update_ti = self.curr_ti
 
+        extras = None
+        if return_key_and_stuff:                      # caller-owned copies, made BEFORE the group is declared free: they read its buffers
+            extras = tuple(v.clone() if v is not None else None for v in self._key_views(key, shrinkage, selection, h, w))
         if pf is not None:
             done = torch.cuda.Event()
             done.record()
@@ -391,8 +396,7 @@ class InferenceCore:
             # (a memory frame's value encoder and insertion are enqueued by now: the next readout must see them)
             self._enqueue_early_readout(ro_done if (ro_done is not None and not is_mem_frame) else None)
         if return_key_and_stuff:
-            views = self._key_views(key, shrinkage, selection, h, w)
-            return (prob,) + tuple(v.clone() if v is not None else None for v in views)   # caller-owned copies
+            return (prob,) + extras
         return prob
 
     # ---- early readout -----------------------------------------------------------------------------

@@ -276,10 +276,13 @@ def worker(args):
     runner = _resolve(args.runner)
     over = json.loads(args.config) if args.config else {}
     fm = [int(x) for x in args.frames_with_masks.split(',') if x != '']
+    shared = rank_network(args, runner, over)
     results = []
     for v in mine:
         t0 = time.perf_counter()
         extra = dict(compute_jf=True) if args.compute_jf else {}
+        if shared is not None:
+            extra['network'] = shared
         stats = runner(v['frames'], v['masks'], os.path.join(args.out, v['name']), frames_with_masks=fm,
                        compute_iou=args.compute_iou, print_progress=False, overwrite_config=dict(over), **extra)
         dt = time.perf_counter() - t0
@@ -295,6 +298,28 @@ def worker(args):
         json.dump(dict(rank=rank, world=world, nonce=run_nonce(), videos=results), f)
     os.replace(tmp, mine_path)
     return 0
+
+
+def rank_network(args, runner, over):
+    """The one network of a rank, handed to every video it runs (the reference builds its network once per dataset, eval.py:134-163):
+    the weights are uploaded and transformed once and a video of a geometry seen before replays the captured stages.  None - every
+    video builds its own, as before - on the cpu device (launcher tests), for a runner that takes no `network`, and with
+    --fresh-network-per-video."""
+    import inspect
+    if args.device == 'cpu' or getattr(args, 'fresh_network_per_video', False):
+        return None
+    try:
+        if 'network' not in inspect.signature(runner).parameters:
+            return None
+    except (TypeError, ValueError):
+        return None
+    import torch
+    from .configuration import VIDEO_INFERENCE_CONFIG
+    from .network import XMem
+    config = dict(VIDEO_INFERENCE_CONFIG)
+    config.update(over)
+    device = torch.device('cuda', torch.cuda.current_device())
+    return XMem(config, config['model'], pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
 
 
 def jf_means(stats):
@@ -374,6 +399,8 @@ def main(argv=None):
     ap.add_argument('--merge-timeout', type=float, default=86400.0, help='under torchrun: how long rank 0 waits for the other ranks\' results')
     ap.add_argument('--threads-per-rank', type=int, default=8, help='torch intra-op threads per rank (ranks are pinned to the cores next to their GPU)')
     ap.add_argument('--no-isolate', action='store_true', help='keep every GPU visible in every rank (default: a rank sees only its own)')
+    ap.add_argument('--fresh-network-per-video', action='store_true', help='build (upload, transform, capture) a new network for every '
+                                                                           'video instead of one per rank')
     ap.add_argument('--as-worker', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
     under_torchrun = (not args.as_worker) and int(os.environ.get('WORLD_SIZE', '1')) > 1 and 'RANK' in os.environ

@@ -44,6 +44,7 @@ class XMem:
         """Same signature as model/network.py:18.  `pretrained_*` are accepted for compatibility; torchvision
         ImageNet weights cannot be fetched offline, so a checkpoint (or load_weights) is the only weight source."""
         self.single_object = config.get('single_object', False)
+        self.model_path = model_path                 # what a caller's config['model'] is compared with when the network is handed over
         self.device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
         self._sd = None
         self._w = {}
@@ -292,7 +293,7 @@ class XMem:
                 fn(*[(t.clone() if (i in mutates and t is not None) else t) for i, t in enumerate(static_in)])
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
+                with ops.CAPTURE_LOCK, torch.cuda.graph(graph):   # no decode thread pins host memory meanwhile
                     static_out = fn(*static_in)
             st = (graph, static_in, static_out)
             while len(self._stages) >= MAX_STAGES:
@@ -329,6 +330,9 @@ class XMem:
         video) takes over the dead core's captured stages - its fresh hidden state is copied into the stage's state buffer
         once and the core then continues on that buffer - instead of re-capturing every decoder graph per video."""
         if self._owner_free:
+            # the smallest free token: the cores a caller builds in a fixed order (an ensemble's passes) get the same tokens call after
+            # call, whatever order the previous call's cores died in, and so find their own captured stages again
+            self._owner_free.sort(reverse=True)
             return self._owner_free.pop()
         self._owner_next += 1
         return self._owner_next

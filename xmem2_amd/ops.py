@@ -141,6 +141,10 @@ def _h(t):
 # counterpart of the reference's autocast loop, inference/run_on_video.py:76).  Set per call tree by XMem (`precision`).
 _PRECISION = 'fp32'
 _DRIVER = threading.RLock()          # held while a thread is inside `precision` (a network stage): see precision.__enter__
+# held while a stage is being captured into a HIP graph, and by helper threads around calls the runtime forbids while ANY thread captures
+# (torch captures in the 'global' error mode): pinning host memory makes the pinned allocator query its events, which invalidates a capture
+# in progress on another thread (hipErrorStreamCaptureInvalidated).  Captures are rare (once per stage and shape), so nobody waits long.
+CAPTURE_LOCK = threading.Lock()
 PRECISIONS = ('fp32', 'fp16', 'fp16w', 'fp32x')
 # 'fp16' (opt-in): THE FP16 LOOP - the counterpart of the reference's GPU mode (torch.cuda.amp.autocast around the frame loop,
 # inference/run_on_video.py:76; fp32 preload :59-66): activations are IEEE halfs in HBM, every convolution contracts half
@@ -909,6 +913,22 @@ def selector_prepare(key_rows, sel_rows, mask, h, w, alpha, eps, Mexp, Qexp, bsq
     check(load().xmem_selector_prepare(ptr(_req(key_rows, 'key')), ptr(_req(sel_rows, 'selection')), ptr(mask), Cm, H, W,
                                        h, w, ck, float(alpha), float(1 - alpha), float(eps),
                                        ptr(Mexp), ptr(Qexp), ptr(bsq), ptr(presence), stream_ptr()))
+
+
+def selector_prepare_u8(key_rows, sel_rows, mask_u8, lut, h, w, alpha, eps, Mexp, Qexp, bsq, presence):
+    """`selector_prepare` for a mask held as a uint8 label plane [H,W] and a float32 table lut[256]: the mask value of a pixel is
+    lut[label].  Bit-identical to `selector_prepare` on the float mask `lut[mask_u8][None]`."""
+    hw, ck = key_rows.shape
+    if hw != h * w:
+        raise ValueError('key rows do not match h*w')
+    if mask_u8.dim() != 2:
+        raise ValueError('mask must be a uint8 [H, W] label plane')
+    if lut.dtype != torch.float32 or lut.numel() != 256:
+        raise ValueError('lut must hold 256 float32 entries')
+    H, W = mask_u8.shape
+    check(load().xmem_selector_prepare_u8(ptr(_req(key_rows, 'key')), ptr(_req(sel_rows, 'selection')), ptr(_req_u8(mask_u8, 'mask')),
+                                          ptr(_req(lut, 'lut')), H, W, h, w, ck, float(alpha), float(1 - alpha), float(eps),
+                                          ptr(Mexp), ptr(Qexp), ptr(bsq), ptr(presence), stream_ptr()))
 
 
 def cycle_dissimilarity(Mexp, Qexp, bsq, shrinkage, chosen, valid=None):

@@ -193,10 +193,11 @@ class FramePrefetcher:
 
     def _load(self, idx):
         smp = self.reader[idx]
-        if smp.rgb_u8 is None:                                   # resize_on_device: the source-size frame travels
-            smp.src_u8 = smp.src_u8.pin_memory()
-        else:
-            smp.rgb_u8 = smp.rgb_u8.pin_memory()
+        with ops.CAPTURE_LOCK:                                   # not while the main thread captures a stage (see ops.CAPTURE_LOCK)
+            if smp.rgb_u8 is None:                               # resize_on_device: the source-size frame travels
+                smp.src_u8 = smp.src_u8.pin_memory()
+            else:
+                smp.rgb_u8 = smp.rgb_u8.pin_memory()
         return smp
 
     def _top_up(self):
@@ -288,11 +289,35 @@ def _working_u8(src_u8, target_hw, device, flip=False):
     return ops.resize_u8(dev, target_hw, flip=flip)
 
 
-def _load_main_objects(imgs_in_path, masks_in_path, config, device):
+def _adopt_network(network, config, device):
+    """A network that outlives the call (one per dataset, as eval.py:134-163 builds it): checked against the call's config, which then
+    receives the dimensions `XMem.__init__` would have written into it.  The cores of successive calls take over each other's owner
+    token and with it the captured stages (XMem.acquire_owner), so a second video of the same geometry replays instead of capturing."""
+    if config.get('model') != network.model_path:
+        raise ValueError(f"config['model'] = {config.get('model')!r}, but the given network was built from {network.model_path!r}")
+    want = config.get('precision', os.environ.get('XMEM_PRECISION', 'fp32'))
+    if want != network.precision:
+        raise ValueError(f"config['precision'] = {want!r}, but the given network runs in {network.precision!r}")
+    if network.device != device:
+        raise ValueError(f'the given network lives on {network.device}, the call runs on {device}')
+    config['key_dim'], config['value_dim'], config['hidden_dim'] = network.key_dim, network.value_dim, network.hidden_dim
+    if config.get('model') is None:                                  # as a call that builds its own network says
+        warn('No model weights were loaded, as config["model"] was not specified.')
+    return network
+
+
+def _make_network(config, device, network=None):
+    if network is not None:
+        return _adopt_network(network, config, device)
     model_path = config['model']
     network = XMem(config, model_path, pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
     if model_path is None:
         warn('No model weights were loaded, as config["model"] was not specified.')
+    return network
+
+
+def _load_main_objects(imgs_in_path, masks_in_path, config, device, network=None):
+    network = _make_network(config, device, network)
     vid_reader = VideoReader('', imgs_in_path, masks_in_path, size=config['size'], use_all_masks=True,
                              resize_on_device=config.get('resize_on_device', False))
     vid_length = len(vid_reader)
@@ -307,7 +332,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
                         compute_iou=False, manually_curated_masks=False, print_progress=True,
                         augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
                         object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
-                        compute_jf=False):
+                        compute_jf=False, network=None):
     import pandas as pd
     from PIL import Image
     if not torch.cuda.is_available():
@@ -319,7 +344,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     overwrite_config = {} if overwrite_config is None else overwrite_config
     overwrite_config['masks_out_path'] = masks_out_path
     config.update(overwrite_config)
-    mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device)
+    mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
     to_permanent = [0] if original_memory_mechanism else sorted(frames_with_masks)
@@ -463,12 +488,14 @@ def _with_jf(df, scorer):
 
 
 def run_on_video(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
-                 compute_iou=False, print_progress=True, **kwargs):
+                 compute_iou=False, print_progress=True, network=None, **kwargs):
     """Same signature / return as inference/run_on_video.py:247-282: per-frame stats DataFrame
     (frame, mask_provided[, iou]); predicted masks are written under ``masks_out_path/masks``.
     ``compute_jf=True`` adds DAVIS J and F columns, scored on the device against every frame's ground truth
-    (xmem2_amd.metrics; frames without one get NaN)."""
-    return _inference_on_video(imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
+    (xmem2_amd.metrics; frames without one get NaN).
+    ``network``: an `XMem` to run on instead of building one from ``config['model']`` (which, like ``config['precision']``, must
+    agree with it): its weights stay uploaded and its captured stages are replayed by the next call of the same geometry."""
+    return _inference_on_video(network=network, imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
                                frames_with_masks=frames_with_masks, compute_iou=compute_iou,
                                print_progress=print_progress, **kwargs)
 
@@ -573,7 +600,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                        compute_iou=False, manually_curated_masks=False, print_progress=True,
                        augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
                        object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
-                       compute_jf=False):
+                       compute_jf=False, network=None):
     import pandas as pd
     from PIL import Image
     config = VIDEO_INFERENCE_CONFIG.copy()
@@ -592,10 +619,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     P = len(passes)
 
     # one network (weights uploaded and transformed once), one InferenceCore + MaskMapper per pass
-    model_path = config['model']
-    network = XMem(config, model_path, pretrained_key_encoder=False, pretrained_value_encoder=False).to(device).eval()
-    if model_path is None:
-        warn('No model weights were loaded, as config["model"] was not specified.')
+    network = _make_network(config, device, network)
     dev_resize = bool(config.get('resize_on_device', False))        # opt-in: one decode, one upload, every (size, flip) variant by kernel
     readers = {}
     for s, _ in passes:
@@ -750,12 +774,13 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
-                          compute_iou=False, print_progress=True, **kwargs):
+                          compute_iou=False, print_progress=True, network=None, **kwargs):
     """The test-time ensemble of eval.py (--size S [--flip] --save_scores, one run per pass) + merge_multi_scale.py, in one process on
     one network: `overwrite_config['ensemble']` lists the [size, flip] passes (default: [[size, False], [size, True]]).  Every pass
     runs its own InferenceCore; per frame, each pass's probabilities are resized to the original size, un-flipped, quantised to
-    uint8 and summed on the device, and the argmax of the sum is the written mask.  Same signature and return as run_on_video."""
-    return _ensemble_on_video(imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
+    uint8 and summed on the device, and the argmax of the sum is the written mask.  Same signature and return as run_on_video
+    (``network`` included)."""
+    return _ensemble_on_video(network=network, imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=masks_out_path,
                               frames_with_masks=frames_with_masks, compute_iou=compute_iou,
                               print_progress=print_progress, **kwargs)
 
@@ -776,8 +801,8 @@ def _pil_to_tensor01(pic):
 def select_k_next_best_annotation_candidates(imgs_in_path, masks_in_path, masks_out_path=None, k: int = 5,
                                              print_progress=True, previously_chosen_candidates=[0],
                                              use_previously_predicted_masks=True, alpha=0.5,
-                                             min_mask_presence_percent=0.25, **kwargs):
-    """inference/run_on_video.py:285-370, same arguments and return (list of new frame indices)."""
+                                             min_mask_presence_percent=0.25, network=None, **kwargs):
+    """inference/run_on_video.py:285-370, same arguments and return (list of new frame indices).  ``network``: as in run_on_video."""
     import tempfile
     from pathlib import Path
     from PIL import Image
@@ -788,7 +813,7 @@ def select_k_next_best_annotation_candidates(imgs_in_path, masks_in_path, masks_
     device = torch.device('cuda', torch.cuda.current_device())
     config = dict(VIDEO_INFERENCE_CONFIG)
     config.update(kwargs.get('overwrite_config') or {})     # the reference extracts keys with the default config
-    _, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device)   # honours config['resize_on_device']
+    _, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)   # honours config['resize_on_device']
     frame_keys, shrinkages, selections, *_ = extract_keys(vid_reader, processor, print_progress=print_progress,
                                                           flatten=False, keep_on_device=True)
     tmp = None
@@ -802,7 +827,7 @@ def select_k_next_best_annotation_candidates(imgs_in_path, masks_in_path, masks_
             p_masks_out = Path(tmp.name)
         run_on_video(imgs_in_path=imgs_in_path, masks_in_path=masks_in_path, masks_out_path=p_masks_out,
                      frames_with_masks=previously_chosen_candidates, compute_iou=False, print_progress=print_progress,
-                     **kwargs)
+                     network=network, **kwargs)
     try:
         masks = [_pil_to_tensor01(Image.open(p)) for p in sorted((p_masks_out / 'masks').iterdir())]
     except Exception:

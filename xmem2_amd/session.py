@@ -1,0 +1,500 @@
+"""VideoSession: the annotate -> propagate -> select loop of XMem++ on one video, with everything that does not change between
+iterations kept on the device.
+
+The reference's interactive backend (inference/interact/gui.py:719-884 with resource_manager.py) is a tensor program behind a GUI:
+it stores each propagated frame's key, shrinkage, selection and mask, hands exactly those to `select_next_candidates`, edits the
+permanent memory in place when a reference is saved or removed and propagates forward or backward from any frame.  This module is
+that program without the GUI, on the file conventions of `run_on_video`:
+
+    s = VideoSession(imgs_in_path, masks_in_path, overwrite_config={...}, network=net)
+    s.save_reference(0)                     # the annotation of frame 0 from masks_in_path
+    s.full_propagation()                    # == run_on_video(frames_with_masks=s.references), masks stay on the device
+    new = s.candidates(k=3)                 # no second encoder pass, no mask file read back
+    s.save_reference(new[0], mask)          # an index array, a device tensor (S2M / click output) or a palette PNG
+    s.full_propagation(); s.save(out_dir)
+
+Paid once per video: decode, resize and upload of every frame (working-size uint8, on the device up to
+`config['session_device_frame_bytes']`, in pinned host memory beyond it).  Paid once per network: upload, filter transforms and the
+captured stages.  Recomputed per propagation: the key encoder, readout and decoder of every visited frame (caching the key
+encoder's feature pyramid is a follow-up).  Never recomputed: keys for the selector - every visited frame's key, shrinkage and
+selection come from its own `step` (the copies `return_key_and_stuff=True` makes of the buffers the step used, taken before the
+step releases them to the next key pass) and are stored in a per-video arena.
+"""
+import argparse
+import collections
+import contextlib
+import json
+import os
+import sys
+from warnings import warn
+
+import numpy as np
+import torch
+
+from . import ops
+from .configuration import VIDEO_INFERENCE_CONFIG
+from .inference_core import InferenceCore
+from .mask_mapper import MaskMapper
+
+DEFAULT_DEVICE_FRAME_BYTES = 16 << 30          # config['session_device_frame_bytes']: frames beyond it stay in pinned host memory
+MASK_FORMS = ('objects', 'files')
+
+
+# ---- pure helpers (host) ---------------------------------------------------------------------------------------------
+def visit_order(n_frames, start=0, direction='forward', stop=None):
+    """Frame indices `propagate` visits: start, start +- 1, ..., stop (both included).  `stop` defaults to the end of the clip in the
+    direction of travel."""
+    if direction not in ('forward', 'backward'):
+        raise ValueError(f"direction must be 'forward' or 'backward', got {direction!r}")
+    if n_frames <= 0:
+        raise ValueError('the video has no frames')
+    step = 1 if direction == 'forward' else -1
+    if stop is None:
+        stop = n_frames - 1 if step > 0 else 0
+    for name, v in (('start', start), ('stop', stop)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (0 <= v < n_frames):
+            raise ValueError(f'{name} = {v!r} is not a frame of this video (0..{n_frames - 1})')
+    if (stop - start) * step < 0:
+        raise ValueError(f'stop = {stop} lies behind start = {start} when going {direction}')
+    return list(range(int(start), int(stop) + step, step))
+
+
+def hinted(order, key_batch, prefetch):
+    """Yield (frame index, what `prefetch` returned for it) over `order`, hinting the key encoder as the frame loop of run_on_video
+    does: whenever fewer than `key_batch` hinted frames are pending, the next `key_batch` frames IN THE DIRECTION OF TRAVEL go to
+    `prefetch(list of indices) -> list` as one batch; a tail shorter than a batch goes frame by frame (no new graph shapes)."""
+    key_batch = max(1, int(key_batch))
+    pending, nxt = collections.deque(), 0
+    for _ in order:
+        if len(pending) < key_batch and nxt < len(order):
+            remaining = len(order) - nxt
+            n = key_batch if remaining >= key_batch else 1
+            batch = list(order[nxt:nxt + n])
+            pending.extend(zip(batch, prefetch(batch)))
+            nxt += n
+        yield pending.popleft()
+
+
+def files_table(pic):
+    """float32[256]: the mask value `_pil_to_tensor01` gives each pixel of `pic`, a PIL image of 256 pixels (pixel v stands for label
+    v, any mode the harness reads), with the selector's max over channels folded in.  Computed by that function itself, so the
+    arithmetic - float32(v) / 255 in IEEE division, a palette image contributing its raw INDEX plane - is the file path's."""
+    from .run_on_video import _pil_to_tensor01
+    t = _pil_to_tensor01(pic)
+    if t.numel() != 256 * t.shape[0]:
+        raise ValueError('files_table: expected an image of 256 pixels, one per label')
+    return t.reshape(t.shape[0], 256).max(dim=0).values.contiguous()
+
+
+def objects_table():
+    """float32[256] of the GUI's meaning of a mask: any object -> 1.0, background -> 0.0."""
+    t = torch.ones(256, dtype=torch.float32)
+    t[0] = 0.0
+    return t
+
+
+def _remove_permanent_frame(core, t, pos):
+    """Take the elements of frame t, the pos-th frame of the permanent store, out of it.  Not through
+    `InferenceCore.remove_from_permanent_memory`, which keeps two quirks of the reference: the frame position `add` reports
+    (kv_memory_store.py: (n_total + 1e-9) // (n + 1e-9) - 1) is one too small for every frame but the first (96.000000001 //
+    48.000000001 is 1), and memory_manager.py:204-210 passes that POSITION as an ELEMENT offset.  The session knows the true position
+    (its store is in frame order) and removes the frame's own h*w elements."""
+    core._retire_early()
+    mem = core.memory
+    mem.frame_id_to_permanent_mem_idx.pop(t, None)
+    mem.version += 1
+    mem.permanent_work_mem.remove_at(pos * mem.HW, mem.HW)
+
+
+class _Frame:
+    """What `_post_process_gpu` and the writers need of a decoded frame (the fields of run_on_video.Sample they read)."""
+    __slots__ = ('frame', 'shape', 'need_resize', 'raw_image_pil', 'mask')
+
+    def __init__(self, smp):
+        # the decoded original-size image is NOT kept (several GB for a long 1080p clip): only overlays need it, `save` reads it again
+        self.frame, self.shape, self.need_resize, self.raw_image_pil, self.mask = smp.frame, smp.shape, smp.need_resize, None, smp.mask
+
+
+class VideoSession:
+    def __init__(self, imgs_in_path, masks_in_path=None, overwrite_config=None, network=None):
+        from .run_on_video import _make_network, _working_u8
+        if not os.path.isdir(imgs_in_path):
+            raise NotADirectoryError(f'imgs_in_path: {imgs_in_path!r} is not a directory of frames')
+        if masks_in_path is not None and not os.path.isdir(masks_in_path):
+            raise NotADirectoryError(f'masks_in_path: {masks_in_path!r} is not a directory')
+        if overwrite_config is not None and not isinstance(overwrite_config, dict):
+            raise TypeError('overwrite_config must be a dict (or None)')
+        if not torch.cuda.is_available():
+            raise RuntimeError('xmem2_amd.session needs an MI355X (HIP) device - there is no CPU path')
+        torch.autograd.set_grad_enabled(False)
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        config = VIDEO_INFERENCE_CONFIG.copy()
+        config.update(overwrite_config or {})
+        self.config = config
+        self.network = _make_network(config, self.device, network)
+        self.imgs_in_path, self.masks_in_path = imgs_in_path, masks_in_path
+        reader = _session_reader(imgs_in_path, masks_in_path, size=config['size'], resize_on_device=config.get('resize_on_device', False))
+        self.reader = reader
+        n = len(reader)
+        if n == 0:
+            raise ValueError(f'no frames in {imgs_in_path!r}')
+        config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196
+            config['enable_long_term'] and
+            (n / (config['max_mid_term_frames'] - config['min_mid_term_frames']) * config['num_prototypes'])
+            >= config['max_long_term_elements'])
+        self.mapper = MaskMapper()
+        self.core = InferenceCore(self.network, config=config)
+        self.key_batch = max(1, int(config.get('key_batch', 4)))
+
+        # every frame decoded ONCE: working-size uint8, on the device up to the byte cap, in pinned host memory beyond it
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, int(config.get('decode_workers', 8))), thread_name_prefix='xmem-decode') as pool:
+            samples = list(pool.map(reader.__getitem__, range(n)))
+        self.frames = [_Frame(s) for s in samples]
+        if any(s.shape != samples[0].shape for s in samples):
+            raise ValueError('the frames of a video must have one size')
+        self.shape = samples[0].shape                                    # (H, W) of the original frames and of the masks
+        dev_resize = samples[0].rgb_u8 is None
+        th, tw = samples[0].target_hw if dev_resize else samples[0].rgb_u8.shape[:2]
+        cap = int(config.get('session_device_frame_bytes', DEFAULT_DEVICE_FRAME_BYTES))
+        per_frame = th * tw * 3
+        self.n_device_frames = n if cap < 0 else min(n, cap // per_frame)
+        self._dev_frames = torch.empty((self.n_device_frames, th, tw, 3), dtype=torch.uint8, device=self.device)
+        self._host_frames = torch.empty((n - self.n_device_frames, th, tw, 3), dtype=torch.uint8, pin_memory=True) \
+            if n > self.n_device_frames else None
+        for i, s in enumerate(samples):
+            if i < self.n_device_frames:
+                self._dev_frames[i].copy_(_working_u8(s.src_u8, s.target_hw, self.device) if dev_resize else s.rgb_u8)
+            elif dev_resize:
+                from .pil_resize import resize_u8_host                   # the host restatement of the device resize: the same bytes
+                self._host_frames[i - self.n_device_frames].copy_(torch.from_numpy(resize_u8_host(s.src_u8.numpy(), th, tw)))
+            else:
+                self._host_frames[i - self.n_device_frames].copy_(s.rgb_u8)
+        del samples
+
+        # arenas: one row block per frame, written by the propagation that visits the frame
+        gh, gw = -(-th // 16), -(-tw // 16)                              # the stride-16 grid of the padded frame
+        ck = self.network.key_dim
+        self.grid_hw = (gh, gw)
+        self.key = torch.empty((n, gh * gw, ck), dtype=torch.float32, device=self.device)
+        self.shrinkage = torch.empty((n, gh * gw), dtype=torch.float32, device=self.device)
+        self.selection = torch.empty((n, gh * gw, ck), dtype=torch.float32, device=self.device)
+        self.masks = torch.zeros((n,) + tuple(self.shape), dtype=torch.uint8, device=self.device)   # dense ids (MaskMapper)
+        self._present = [False] * n
+        self._refs = {}                                                  # frame index -> the annotation's raw H x W index array
+        torch.cuda.synchronize()                                         # the frames are complete for every stream from here on
+
+    # ---- bookkeeping ---------------------------------------------------------------------------------------------------
+    def __len__(self):
+        return len(self.frames)
+
+    @property
+    def references(self):
+        """Sorted frame indices in the permanent memory."""
+        return sorted(self._refs)
+
+    def _check_frame(self, t):
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not (0 <= t < len(self)):
+            raise IndexError(f'frame {t!r} is not a frame of this video (0..{len(self) - 1})')
+        return int(t)
+
+    def frame_u8(self, t):
+        """The working-size uint8 frame t as `step` / `prefetch_keys` take it (a device tensor, or pinned host memory beyond the cap)."""
+        t = self._check_frame(t)
+        return self._dev_frames[t] if t < self.n_device_frames else self._host_frames[t - self.n_device_frames]
+
+    def all_masks_present(self):
+        return all(self._present)
+
+    def _label_lut(self):
+        """dense id -> original label value, as a host uint8[256] (identity while the annotation's ids are 1, 2, 3, ...)."""
+        lut = np.arange(256, dtype=np.uint8)
+        if not self.mapper.coherent:
+            lut[:] = 0
+            for original, dense in self.mapper.remappings.items():
+                lut[dense] = original
+        return lut
+
+    def mask(self, t):
+        """Device uint8 [H, W] with the original label values, or None when no propagation has visited frame t."""
+        t = self._check_frame(t)
+        if not self._present[t]:
+            return None
+        if self.mapper.coherent:
+            return self.masks[t].clone()                                  # a copy: the arena is the session's state
+        key = tuple(sorted(self.mapper.remappings.items()))
+        if getattr(self, '_lut_dev', (None, None))[0] != key:            # changes only when an annotation brings a new label
+            self._lut_dev = (key, torch.from_numpy(self._label_lut()).to(self.device))
+        return self._lut_dev[1][self.masks[t].long()]
+
+    # ---- references ----------------------------------------------------------------------------------------------------
+    def _raw_mask(self, t, mask):
+        """The annotation as the reader would have read it: an H x W uint8 index array at the original size."""
+        from PIL import Image
+        if mask is None:
+            raw = self.frames[t].mask
+            if raw is None:
+                raise FileNotFoundError(f"Couldn't find mask {t}! Check that the filename is the same as for frame {t}.")
+        elif isinstance(mask, (str, os.PathLike)):
+            raw = np.array(Image.open(mask).convert('P'), dtype=np.uint8)
+        elif torch.is_tensor(mask):
+            m = mask
+            if m.dim() == 3:                                             # [K+1, H, W] probabilities (aggregate_wbg output)
+                m = ops.argmax_u8(m.to(self.device, torch.float32).contiguous()) if m.shape[0] > 1 else m[0]
+            raw = m.to(torch.uint8).cpu().numpy()
+        else:
+            raw = np.asarray(mask).astype(np.uint8)
+        if raw.ndim != 2 or tuple(raw.shape) != tuple(self.shape):
+            raise ValueError(f'mask of frame {t}: expected an index mask of shape {tuple(self.shape)}, got {tuple(raw.shape)}')
+        return np.ascontiguousarray(raw)
+
+    def _put(self, t, raw):
+        msk, _ = self.mapper.convert_mask(raw, exhaustive=True)
+        if min(msk.shape) == 0:
+            return None
+        if self.frames[t].need_resize:
+            msk = self.reader.resize_mask(msk)
+        self.core.set_all_labels(list(self.mapper.remappings.values()))
+        rgb = self.frame_u8(t)
+        return self.core.put_to_permanent_memory(rgb.to(self.device), msk.to(self.device), t)
+
+    def save_reference(self, t, mask=None):
+        """gui.on_save_reference: put_to_permanent_memory(image, mask, t).  True if frame t was a reference already (its entry is
+        replaced).  `mask`: None (the file of frame t in masks_in_path) | H x W index array | device tensor (an index mask,
+        or [K+1, H, W] probabilities) | path to a palette PNG.
+        The permanent memory is kept in frame order - a reference in front of existing ones makes those be put again behind it - so
+        that the memory, and with it every result, is a function of the SET of references: what run_on_video builds for that set."""
+        t = self._check_frame(t)
+        raw = self._raw_mask(t, mask)
+        if not self.mapper.labels and not raw.any():                     # no object known, none given (run_on_video.py:213-216)
+            warn(f'Skipping adding frame {t} to permanent memory, as the mask is empty')
+            return False
+        # frame t itself (when it is replaced) and the references behind it are taken out and put again in frame order.  A replacement
+        # does not go through update_permanent_memory: the position it would write to is the reference's, one frame too early.
+        replaced = t in self._refs
+        again = [r for r in self.references if r > t or r == t]
+        if again:
+            self._require_one_object_group('save_reference of a frame that is, or lies in front of, an existing reference')
+        for r in reversed(again):
+            _remove_permanent_frame(self.core, r, self.references.index(r))
+        self._put(t, raw)
+        self._refs[t] = raw
+        for r in again:
+            if r != t:
+                self._put(r, self._refs[r])
+        self._sync_positions()
+        return replaced
+
+    def remove_reference(self, t):
+        """gui.on_remove_reference.  The labels the mask mapper has seen stay known."""
+        t = self._check_frame(t)
+        if t not in self._refs:
+            raise KeyError(f'frame {t} is not a reference (references: {self.references})')
+        self._require_one_object_group('remove_reference')
+        _remove_permanent_frame(self.core, t, self.references.index(t))
+        del self._refs[t]
+        self._sync_positions()
+
+    def _require_one_object_group(self, what):
+        """Taking a frame out of the permanent store is defined for ONE object group only.  An object that first appears in a later
+        reference opens a second group whose value arena starts at that frame and is shorter than the key arena; the store sieves
+        every arena by the same element range, which would hit the wrong elements there (as for eviction, kv_memory_store.py:160-181,
+        the store does not support it).  Nothing has been changed when this raises."""
+        perm = getattr(self.core.memory, 'permanent_work_mem', None)
+        if perm is not None and perm.num_groups > 1:
+            raise NotImplementedError(f'{what}: the permanent memory holds {perm.num_groups} object groups (an object first appeared '
+                                      'in a later reference); frames can only be appended to it - start a new VideoSession to '
+                                      'annotate this set of references')
+
+    def _sync_positions(self):
+        """The memory's frame -> position table restated with the true positions (the store is in frame order)."""
+        table = getattr(self.core.memory, 'frame_id_to_permanent_mem_idx', None)
+        if table is not None:
+            table.clear()
+            table.update({r: i for i, r in enumerate(self.references)})
+
+    # ---- propagation ---------------------------------------------------------------------------------------------------
+    def propagate(self, start=0, direction='forward', stop=None, manually_curated_masks=False):
+        """gui.on_propagation: step over start..stop in `direction` on the memory as it stands; per visited frame the call
+        run_on_video's frame loop makes.  Returns the visited frame indices."""
+        from .run_on_video import _post_process_gpu
+        order = visit_order(len(self), start, direction, stop)
+        if not self._refs:
+            raise ValueError('No valid masks provided!')
+        core, device = self.core, self.device
+        on_device = all(t < self.n_device_frames for t in order)
+
+        def prefetch(batch):
+            # resident frames were complete long ago (synchronised at construction): the pass may start under the current frame
+            return core.prefetch_keys([self.frame_u8(t) for t in batch], inputs_complete=on_device)
+
+        for i, (t, rgb) in enumerate(hinted(order, self.key_batch, prefetch)):
+            fr = self.frames[t]
+            msk = labels = None
+            if t in self._refs:
+                msk, labels = self.mapper.convert_mask(self._refs[t], exhaustive=True)
+                if fr.need_resize:
+                    msk = self.reader.resize_mask(msk)
+                msk = msk.to(device)
+                core.set_all_labels(list(self.mapper.remappings.values()))
+            prob, key, shr, sel = core.step(rgb, msk, labels, end=(i == len(order) - 1), manually_curated_masks=manually_curated_masks,
+                                            do_not_add_mask_to_memory=(msk is not None), return_key_and_stuff=True)
+            gh, gw = self.grid_hw
+            self.key[t].view(gh, gw, -1).copy_(key[0].permute(1, 2, 0))
+            self.shrinkage[t].view(gh, gw).copy_(shr[0, 0])
+            self.selection[t].view(gh, gw, -1).copy_(sel[0].permute(1, 2, 0))
+            self.masks[t].copy_(_post_process_gpu(fr, prob))
+            self._present[t] = True
+        return order
+
+    def full_propagation(self):
+        """gui.on_full_propagation: clear_memory(keep_permanent=True), then forward from frame 0."""
+        if not self._refs:
+            raise ValueError('No valid masks provided!')
+        self.core.clear_memory(keep_permanent=True)
+        return self.propagate(0, 'forward')
+
+    # ---- candidates ----------------------------------------------------------------------------------------------------
+    def mask_table(self, mask_form='objects'):
+        """float32[256] on the host: the selector's mask value of a DENSE id.  'objects': any object 1.0 (the GUI's masks);
+        'files': what reading the PNG `save` writes back through `_pil_to_tensor01` gives (max over channels)."""
+        if mask_form not in MASK_FORMS:
+            raise ValueError(f'mask_form must be one of {MASK_FORMS}, got {mask_form!r}')
+        if mask_form == 'objects':
+            return objects_table()
+        from PIL import Image
+        labels = Image.fromarray(np.arange(256, dtype=np.uint8)[None])          # pixel v = original label v, as `save` hands it over
+        by_label = files_table(self.reader.map_the_colors_back(labels))
+        return by_label[torch.from_numpy(self._label_lut()).long()].contiguous()
+
+    def candidates(self, k=5, alpha=0.5, min_mask_presence_percent=0.25, mask_form='objects', epsilon=0.5):
+        """gui.on_compute_candidates: `select_next_candidates` on what the propagation left on the device, with `references` as the
+        previously chosen frames.  Every frame must have a mask (gui.confirm_ready_for_candidates_selection)."""
+        from .frame_selection import SelectorState, greedy_selection
+        if not self.all_masks_present():
+            missing = [t for t, p in enumerate(self._present) if not p]
+            raise RuntimeError(f'Run propagation on all frames first! ({len(missing)} frame(s) without a mask, first: {missing[0]})')
+        if not self._refs:
+            raise RuntimeError('candidates need at least one reference')
+        if k <= 0 or not (0.0 <= alpha <= 1.0) or min_mask_presence_percent < 0:
+            raise ValueError('candidates: k > 0, 0 <= alpha <= 1 and min_mask_presence_percent >= 0 are required')
+        if len(self._refs) >= len(self):
+            raise ValueError('every frame is a reference already')
+        lut = self.mask_table(mask_form).to(self.device)
+        with torch.cuda.device(self.device):
+            state = SelectorState.from_label_planes(self.key, self.shrinkage, self.selection, self.grid_hw, self.masks, lut, alpha, epsilon)
+            return greedy_selection(state, k, self.references, min_mask_presence_percent, self.device)
+
+    # ---- output --------------------------------------------------------------------------------------------------------
+    def _host_masks(self):
+        return self.masks.cpu().numpy()
+
+    def save(self, masks_out_path, save_overlay=True):
+        """Exactly the files run_on_video writes: <out>/masks/<frame>.png (+ overlay/<frame>.jpg) for every frame that has a mask."""
+        from PIL import Image
+        from .run_on_video import _AsyncSaver, _overlay
+        host = self._host_masks()
+        saver = _AsyncSaver(str(masks_out_path), '')
+        try:
+            for t, fr in enumerate(self.frames):
+                if not self._present[t]:
+                    continue
+                ids = self.mapper.remap_index_mask(host[t])
+
+                def job(ids=ids, fr=fr):
+                    out_img = self.reader.map_the_colors_back(Image.fromarray(ids))
+                    yield out_img, 'masks', fr.frame[:-4] + '.png'
+                    if save_overlay:
+                        img = Image.open(os.path.join(self.reader.image_dir, fr.frame)).convert('RGB')
+                        yield _overlay(img, out_img), 'overlay', fr.frame[:-4] + '.jpg'
+                saver.submit(job)
+        finally:
+            saver.close()
+
+    def stats(self, compute_iou=False, compute_jf=False):
+        """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
+        import pandas as pd
+        from .metrics import InLoopScorer
+        from .run_on_video import _with_jf
+        from .tensor_util import compute_array_iou
+        host = self._host_masks() if compute_iou else None
+        if compute_jf and not self.all_masks_present():
+            raise RuntimeError('compute_jf scores the whole video: run propagation on all frames first')
+        scorer = InLoopScorer(len(self), self.device) if compute_jf else None
+        rows = []
+        for t, fr in enumerate(self.frames):
+            if not self._present[t]:
+                continue
+            had_mask = t in self._refs
+            stat = {'frame': fr.frame, 'mask_provided': had_mask}
+            if compute_iou:
+                stat['iou'] = float(compute_array_iou(host[t], fr.mask)) if (fr.mask is not None and not had_mask) else -1
+            if scorer is not None and fr.mask is not None:
+                scorer.add(t, fr.mask, self.masks[t], self.mapper)
+            rows.append(stat)
+        return _with_jf(pd.DataFrame(rows), scorer)
+
+
+def _session_reader(imgs_in_path, masks_in_path, size, resize_on_device):
+    """run_on_video.VideoReader (use_all_masks=True); without annotation files the reader is set up by hand - it reads no masks and
+    the written masks are mapped to a grey ramp instead of the first annotation's palette."""
+    from PIL import Image
+    from .run_on_video import VideoReader
+    if masks_in_path is not None and len(os.listdir(masks_in_path)) > 0:
+        return VideoReader('', imgs_in_path, masks_in_path, size=size, use_all_masks=True, resize_on_device=resize_on_device)
+    r = VideoReader.__new__(VideoReader)
+    r.resize_on_device, r._Image = bool(resize_on_device), Image
+    r.vid_name, r.image_dir, r.mask_dir = '', imgs_in_path, (masks_in_path or imgs_in_path)
+    r.size, r.use_all_masks = size, False
+    r.frames = sorted(os.listdir(imgs_in_path))
+    r.first_gt_path = None
+    ramp = Image.new('P', (1, 1))
+    ramp.putpalette([v for i in range(256) for v in (i, i, i)])
+    r.reference_mask = ramp
+    return r
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m xmem2_amd.session',
+                                 description='The XMem++ loop on one video with a simulated annotator: every round propagates with the '
+                                             'references so far, lets the selector propose the next frames and takes their annotations '
+                                             'from --masks (run_experiments.py).')
+    ap.add_argument('--images', required=True, help='directory of frames')
+    ap.add_argument('--masks', required=True, help='directory of annotations (palette PNGs named like the frames)')
+    ap.add_argument('--out', required=True, help='the masks of the last round are written to <out>/masks')
+    ap.add_argument('--rounds', type=int, default=1)
+    ap.add_argument('--k', type=int, default=5, help='frames the selector proposes per round')
+    ap.add_argument('--first', default='0', help='comma-separated frames annotated before the first round')
+    ap.add_argument('--alpha', type=float, default=0.5)
+    ap.add_argument('--min-mask-presence-percent', type=float, default=0.25)
+    ap.add_argument('--mask-form', default='objects', choices=MASK_FORMS)
+    ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG')
+    ap.add_argument('--overlay', action='store_true', help='write overlays next to the masks')
+    args = ap.parse_args(argv)
+    if args.rounds < 1 or args.k < 1:
+        ap.error('--rounds and --k must be at least 1')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    s = VideoSession(args.images, args.masks, overwrite_config=json.loads(args.config) if args.config else None)
+    for t in sorted(int(x) for x in args.first.split(',') if x != ''):
+        s.save_reference(t)
+    chosen = []
+    for r in range(args.rounds):
+        for t in sorted(chosen):                                         # the simulated annotator: the ground truth, where there is one
+            if s.frames[t].mask is not None:
+                s.save_reference(t)
+        s.full_propagation()
+        with contextlib.redirect_stdout(sys.stderr):                     # the selector's progress line: stdout carries the JSON only
+            chosen = s.candidates(k=args.k, alpha=args.alpha, min_mask_presence_percent=args.min_mask_presence_percent,
+                                  mask_form=args.mask_form) if len(s.references) < len(s) else []
+        print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
+    s.save(args.out, save_overlay=args.overlay)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
