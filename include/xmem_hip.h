@@ -482,6 +482,17 @@ int xmem_resize_u8_bilinear_aa(const uint8_t* src, int Hs, int Ws, uint8_t* dst,
                                const int32_t* xcoeffs, int xksize, const int32_t* ybounds, const int32_t* ycoeffs, int yksize,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * n device-to-device copies, src[i] -> dst[i] of bytes[i] bytes, in one launch per XMEM_COPY_MAX_SEGMENTS of them (the session's
+ * feature cache: one frame's key-encoder outputs <-> its cache entry).  src / dst / bytes are HOST arrays; the triples travel by
+ * value in the kernel arguments, so the call needs no device-side table and its addresses may change from call to call.
+ * Byte-exact for every length (0: nothing is touched) and every alignment: 16-byte stores on the destination's aligned body, loads as
+ * wide as the source's alignment relative to it allows (16, 4, 2 or 1 bytes), single bytes in front of and behind the body.
+ * The ranges of one pair must not overlap (XMEM_ERR_BAD_ARG); a destination that overlaps ANOTHER pair's ranges is the caller's
+ * fault.  Segments that are all empty launch nothing. */
+#define XMEM_COPY_MAX_SEGMENTS 16
+int xmem_copy_segments(const void* const* src, void* const* dst, const size_t* bytes, int n, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

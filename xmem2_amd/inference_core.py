@@ -56,6 +56,19 @@ def _net_stream(net, name, make):
     return d[name]
 
 
+def _frame_slices(outs, i, batch):
+    """Frame i's contiguous slice of every tensor of a batched key pass that a cache entry holds: key, shrinkage, selection, f16 and the
+    extras (the skip convolutions and the decoder fuser's f16 half).  f8 and f4 (outs[4:6]) are not among them: with the extras made in
+    the pass, no later kernel reads them."""
+    key, shr, sel, f16 = outs[:4]
+    n = key.shape[0] // batch
+    return [key[i * n:(i + 1) * n], shr[i * n:(i + 1) * n], sel[i * n:(i + 1) * n], f16[i:i + 1]] + [t[i:i + 1] for t in outs[6]]
+
+
+def _entry_layout(outs, batch):
+    return tuple((tuple(t.shape), t.dtype) for t in _frame_slices(outs, 0, batch))
+
+
 class InferenceCore:
     def __init__(self, network, config):
         self.config = config
@@ -206,7 +219,7 @@ class InferenceCore:
         return out
 
     @_on_network_device
-    def prefetch_keys(self, images, inputs_complete=False, working_size=None, flip=False):
+    def prefetch_keys(self, images, inputs_complete=False, working_size=None, flip=False, save_to=None):
         """Enqueue ONE batched key-encoder pass for the next `len(images)` frames on a side stream.
 
         The key encoder depends on nothing but the image, so a streaming caller that already holds the coming frames
@@ -227,7 +240,57 @@ class InferenceCore:
         frames; the copy and the resize to the working size (`ops.resize_u8`: the host library's antialiased bilinear resize byte for
         byte, columns mirrored when `flip`) are enqueued on the same side stream in front of the pack kernel, never on the caller's
         stream, and the call returns the working-size device tensors.  The source-size device buffers are released right after the
-        resize (a caller's device tensors are marked as read by the side stream, `record_stream`)."""
+        resize (a caller's device tensors are marked as read by the side stream, `record_stream`).
+
+        `save_to`: a feature cache's side of the pass (xmem2_amd.session.FeatureCache).  A list with one cache entry (or None) per
+        frame, or a callable that is given the entry layout of this pass - (shape, dtype) of one frame's slice of key, shrinkage,
+        selection, f16 and every extra - and returns that list.  Right behind the key stage, on the side stream, ONE `ops.copy_segments`
+        launch per frame with an entry copies the frame's slices into the entry's tensors; `prefetch_cached` is the way back.  The
+        callable runs with the side stream current: what it allocates there belongs to that stream.  Ignored when the core does not
+        pipeline (no key pass runs here then)."""
+        net = self.network
+
+        def produce(image4, gid):
+            outs = net.encode_key_nhwc(image4, need_sk=True, need_ek=True, with_skips=True, slot=gid, inline_skips=True)
+            if save_to is not None:
+                B = image4.shape[0]
+                entries = save_to(_entry_layout(outs, B)) if callable(save_to) else save_to
+                if len(entries) != B:
+                    raise ValueError('prefetch_keys: save_to needs one entry (or None) per frame')
+                for i, entry in enumerate(entries):
+                    if entry is not None:
+                        ops.copy_segments(list(zip(_frame_slices(outs, i, B), entry)))
+            return outs
+        return self._prefetch(images, inputs_complete, working_size, flip, 'g', produce)
+
+    @_on_network_device
+    def prefetch_cached(self, images, entries, inputs_complete=False):
+        """The counterpart of `prefetch_keys` for frames whose key pass was saved (`save_to`): NO key stage runs.  On the side stream
+        the frames are packed as `prefetch_keys` packs them and ONE `ops.copy_segments` launch per frame restores its entry into the
+        network's restored-key slot (`XMem.restored_key_slot`: static buffers shaped and laid out like the key stage's outputs, two
+        groups per batch size as there); the hints are queued exactly as `prefetch_keys` queues them, so `step()`, the early readout and
+        `return_key_and_stuff` do not know the difference.  `entries`: one per frame, as `save_to` received them, all saved by a pass of
+        `len(images)` frames.  Returns the device tensors to pass to the following `step()` calls in order."""
+        net = self.network
+        images, entries = list(images), list(entries)
+        if len(entries) != len(images) or any(e is None for e in entries):
+            raise ValueError('prefetch_cached: one cache entry per frame')
+        if images and not self._pipelined():
+            raise RuntimeError('prefetch_cached: the core does not pipeline (HIP graphs are off), so nothing can have been saved')
+        layout = tuple((tuple(t.shape), t.dtype) for t in entries[0]) if entries else ()
+
+        def produce(image4, gid):
+            B = image4.shape[0]
+            outs = net.restored_key_slot(gid, layout, B)
+            for i, entry in enumerate(entries):
+                ops.copy_segments(list(zip(entry, _frame_slices(outs, i, B))))
+            return outs
+        return self._prefetch(images, inputs_complete, None, False, 'r', produce)
+
+    def _prefetch(self, images, inputs_complete, working_size, flip, kind, produce):
+        """The stream discipline of a hinted batch, shared by `prefetch_keys` (kind 'g': `produce` replays the key stage) and
+        `prefetch_cached` (kind 'r': `produce` restores saved outputs).  `produce(image4, gid)` runs with the side stream current and
+        returns (key, shrinkage, selection, f16, f8, f4, extras) in static buffers that belong to the group `gid`."""
         net = self.network
         images = list(images)
         if not images:
@@ -244,13 +307,15 @@ class InferenceCore:
         if not inputs_complete and any(im.is_cuda for im in images):
             self._side.wait_stream(main)                         # producers of the inputs on the caller's stream
         B = len(images)
-        par = self._group_parity.get(B, 1) ^ 1                   # two buffer groups per batch size, used alternately
-        # (the group - a key-stage graph and its static buffers - belongs to THIS core's owner token: two live cores hinting on one
-        # network never overwrite each other's unconsumed frames; a recycled token takes over the dead core's captured stages)
-        gid = ('g', B, par, self._uid)
+        pkey = B if kind == 'g' else (kind, B)
+        par = self._group_parity.get(pkey, 1) ^ 1                # two buffer groups per batch size (and kind), used alternately
+        # (the group - a key-stage graph and its static buffers, or a restored-key slot - belongs to THIS core's owner token: two live
+        # cores hinting on one network never overwrite each other's unconsumed frames; a recycled token takes over the dead core's
+        # captured stages)
+        gid = (kind, B, par, self._uid)
         if any(e['gid'] == gid for e in self._pfq):              # unconsumed frames still live there: give them up
             self._drop_prefetch()
-        self._group_parity[B] = par
+        self._group_parity[pkey] = par
         if self._group_free.get(gid) is not None:                # main-stream readers of the group's buffers are done
             self._side.wait_event(self._group_free[gid])
         saved_pad = getattr(self, 'pad', None)
@@ -264,7 +329,7 @@ class InferenceCore:
             image4 = torch.empty((B, H0 + lh_ + uh_, W0 + lw_ + uw_, 4), dtype=torch.float32, device=net.device)
             packed = [self._pack(d, out=image4[i:i + 1]) for i, d in enumerate(devs)]     # straight into the batched buffer
             pad = self.pad
-            outs = net.encode_key_nhwc(image4, need_sk=True, need_ek=True, with_skips=True, slot=gid, inline_skips=True)
+            outs = produce(image4, gid)
             ev = torch.cuda.Event()
             ev.record(self._side)
         self._inflight['side'] = ev

@@ -34,6 +34,24 @@ MAX_STAGES = 160
 FUSED_TAIL_MIN_PIXELS = 512
 
 
+# stages whose static outputs other stages read in place: the key encoder, and the slot a cached key pass is restored into
+_KEY_PRODUCERS = ('key', 'keyr')
+
+
+def _flat_outputs(outs):
+    for o in outs:
+        if isinstance(o, torch.Tensor):
+            yield o
+        elif isinstance(o, tuple):
+            yield from (t for t in o if isinstance(t, torch.Tensor))
+
+
+def _span(t):
+    """[first, last) address of a static buffer; a placeholder (stride 0, `restored_key_slot`) owns its one element only"""
+    n = 1 if (t.dim() and t.stride(-1) == 0) else t.numel()
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
 def _padc(n):
     """channel padding of a buffer the network allocates: 4 floats or (fp16 loop) 8 halfs = one 16-byte operand chunk"""
     return (n + 7) // 8 * 8 if ops.act_dtype() == torch.float16 else _pad4(n)
@@ -312,16 +330,16 @@ class XMem:
         """Bound the cache (every resolution / object count / slot / owner adds graphs with private pools): drop the least
         recently replayed stage.  Decoder and value stages read a key-encoder stage's outputs in place; when a key stage goes,
         the stages aliasing its buffers go with it (they would otherwise pay a copy per frame into buffers nobody produces
-        into any more) and are re-captured on demand against the new key stage."""
+        into any more) and are re-captured on demand against the new key stage.  A restored-key slot (`restored_key_slot`) is
+        such a producer too and is dropped the same way."""
         key, st = self._stages.popitem(last=False)
-        if key[0] != 'key':
+        if key[0] not in _KEY_PRODUCERS:
             return
-        spans = [(o.data_ptr(), o.data_ptr() + o.numel() * o.element_size()) for o in st[2] if isinstance(o, torch.Tensor)]
-        for o in st[2]:
-            if isinstance(o, tuple):
-                spans += [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in o if isinstance(t, torch.Tensor)]
+        if key[0] == 'keyr':
+            torch.cuda.synchronize()          # plain allocations, not a graph's pool: every stream is done with them before they are freed
+        spans = [_span(t) for t in _flat_outputs(st[2])]
         inside = lambda t: isinstance(t, torch.Tensor) and any(a <= t.data_ptr() < b for a, b in spans)
-        for k in [k for k, v in self._stages.items() if k[0] != 'key' and any(inside(t) for t in v[1])]:
+        for k in [k for k, v in self._stages.items() if k[0] not in _KEY_PRODUCERS and any(inside(t) for t in v[1])]:
             del self._stages[k]
 
     def acquire_owner(self):
@@ -341,16 +359,49 @@ class XMem:
         self._owner_free.append(token)
 
     def _is_stage_output(self, t):
-        """True when `t` lives inside a static output buffer of a key-encoder stage (a whole output, or the slice of one
-        frame of a batched pass): such tensors keep their address, so later stages may capture them in place."""
+        """True when `t` lives inside a static output buffer of a key-encoder stage or of a restored-key slot (a whole output, or
+        the slice of one frame of a batched pass): such tensors keep their address, so later stages may capture them in place."""
         a = t.data_ptr()
         for k, st in self._stages.items():
-            if k[0] != 'key':
+            if k[0] not in _KEY_PRODUCERS:
                 continue
             for o in st[2]:
-                if isinstance(o, torch.Tensor) and o.data_ptr() <= a < o.data_ptr() + o.numel() * o.element_size():
-                    return True
+                if isinstance(o, torch.Tensor):
+                    lo, hi = _span(o)
+                    if lo <= a < hi:
+                        return True
         return False
+
+    def restored_key_slot(self, slot, frame_layout, batch):
+        """Static buffers with the shapes, dtypes and batched layout of the outputs of the key stage `encode_key_nhwc(image4 of `batch`
+        frames, with_skips=True, inline_skips=True, slot=...)`, for a caller that RESTORES those outputs from a cache instead of running
+        the stage (InferenceCore.prefetch_cached).  `frame_layout`: (shape, dtype) of ONE frame's slice of key, shrinkage, selection,
+        f16 and of every extra, in that order (what a cache entry holds).  Returns (key, shrinkage, selection, f16, f8, f4, extras) like
+        the stage.  f8 and f4 are NOT stored: with the inlined skip convolutions no kernel reads them, so they are placeholders of the
+        right shape without memory behind them (one element, stride 0).
+        The buffers are stable (`_is_stage_output`): decoder and value stages captured for `slot` read them in place.  One slot per
+        (slot, precision, geometry); it counts as a stage for MAX_STAGES and the LRU order, and takes its dependants with it."""
+        self._need_weights()
+        prec = self._call_precision or self.precision
+        frame_layout = tuple((tuple(int(v) for v in shape), dtype) for shape, dtype in frame_layout)
+        if len(frame_layout) < 6 or batch < 1:
+            raise ValueError('restored_key_slot: the layout of key, shrinkage, selection, f16, skip8 and skip4 is required')
+        full_key = ('keyr', slot, prec, int(batch), frame_layout)
+        st = self._stages.get(full_key)
+        if st is not None:
+            self._stages.move_to_end(full_key)
+            return st[2]
+        while len(self._stages) >= MAX_STAGES:
+            self._evict_lru()
+        dev = self.device
+        bufs = [torch.empty((shape[0] * batch,) + shape[1:], dtype=dtype, device=dev) for shape, dtype in frame_layout]
+        f16, skip8, skip4 = bufs[3], bufs[4], bufs[5]
+        hole = torch.empty(1, dtype=f16.dtype, device=dev)
+        f8 = hole.expand(batch, skip8.shape[1], skip8.shape[2], self._w['decoder.up_16_8.skip_conv'].cin)
+        f4 = hole.expand(batch, skip4.shape[1], skip4.shape[2], self._w['decoder.up_8_4.skip_conv'].cin)
+        out = (bufs[0], bufs[1], bufs[2], f16, f8, f4, tuple(bufs[4:]))
+        self._stages[full_key] = (None, [], out)
+        return out
 
     # ---- building blocks (NHWC) -----------------------------------------------------------------
     def _bottleneck(self, x, p):

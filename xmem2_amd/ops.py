@@ -678,6 +678,34 @@ def resize_u8(src, size, flip=False, out=None):
     return out
 
 
+def copy_segments(pairs):
+    """Every (src, dst) pair of `pairs` copied byte for byte, dst <- src, in ONE launch per `_lib.COPY_MAX_SEGMENTS` pairs on the
+    current stream (the feature cache of a session: one frame's key-encoder outputs <-> its cache entry).  The addresses travel in the
+    kernel arguments: nothing is uploaded, nothing is captured, so they may differ from call to call.  Both sides of a pair are
+    contiguous tensors on one HIP device with the same number of BYTES (the dtypes and shapes may differ); empty pairs are allowed."""
+    pairs = list(pairs)
+    n = len(pairs)
+    if n == 0:
+        return
+    device = None
+    for i, (src, dst) in enumerate(pairs):
+        if not (torch.is_tensor(src) and torch.is_tensor(dst)) or not src.is_cuda or not dst.is_cuda:
+            raise RuntimeError(f'copy_segments: pair {i}: expected CUDA (HIP) tensors - xmem2_amd has no CPU path')
+        if src.device != dst.device or (device is not None and src.device != device):
+            raise RuntimeError(f'copy_segments: pair {i}: every tensor of a call must live on one device')
+        device = src.device
+        if not src.is_contiguous() or not dst.is_contiguous():
+            raise RuntimeError(f'copy_segments: pair {i}: both sides must be contiguous')
+        if src.numel() * src.element_size() != dst.numel() * dst.element_size():
+            raise RuntimeError(f'copy_segments: pair {i}: {src.numel() * src.element_size()} source bytes for '
+                               f'{dst.numel() * dst.element_size()} destination bytes')
+    srcs = (C.c_void_p * n)(*[s.data_ptr() for s, _ in pairs])
+    dsts = (C.c_void_p * n)(*[d.data_ptr() for _, d in pairs])
+    sizes = (C.c_size_t * n)(*[s.numel() * s.element_size() for s, _ in pairs])
+    with torch.cuda.device(device):
+        check(load().xmem_copy_segments(srcs, dsts, sizes, n, stream_ptr()))
+
+
 def pack_value_input(image4, masks):
     """image4 [1,Hp,Wp,4], masks [K,Hp,Wp] -> [K,Hp,Wp,8]."""
     K, Hp, Wp = masks.shape

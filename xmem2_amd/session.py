@@ -15,10 +15,16 @@ that program without the GUI, on the file conventions of `run_on_video`:
 
 Paid once per video: decode, resize and upload of every frame (working-size uint8, on the device up to
 `config['session_device_frame_bytes']`, in pinned host memory beyond it).  Paid once per network: upload, filter transforms and the
-captured stages.  Recomputed per propagation: the key encoder, readout and decoder of every visited frame (caching the key
-encoder's feature pyramid is a follow-up).  Never recomputed: keys for the selector - every visited frame's key, shrinkage and
-selection come from its own `step` (the copies `return_key_and_stuff=True` makes of the buffers the step used, taken before the
-step releases them to the next key pass) and are stored in a per-video arena.
+captured stages.  Recomputed per propagation: the key encoder, readout and decoder of every visited frame.  Never recomputed: keys
+for the selector - every visited frame's key, shrinkage and selection come from its own `step` (the copies
+`return_key_and_stuff=True` makes of the buffers the step used, taken before the step releases them to the next key pass) and are
+stored in a per-video arena.
+
+Opt-in, `config['session_feature_cache_bytes']` > 0 (`FeatureCache`): the key encoder is paid once per frame too.  Everything the
+decoder and the value encoder take from a hinted key pass depends on the frame alone - key, shrinkage, selection, f16, the decoder's
+two skip convolutions and the fuser's f16 half - and is saved per frame in one device arena; a later propagation restores a batch
+with one copy launch per frame on the side stream instead of running the encoder (`InferenceCore.prefetch_cached`).  Bit-identical
+to the cache being off; profiles/r07_session_cache.txt has the measurement.
 """
 import argparse
 import collections
@@ -38,6 +44,7 @@ from .mask_mapper import MaskMapper
 
 DEFAULT_DEVICE_FRAME_BYTES = 16 << 30          # config['session_device_frame_bytes']: frames beyond it stay in pinned host memory
 MASK_FORMS = ('objects', 'files')
+ENTRY_ALIGN = 256                              # every tensor of a cache entry starts on a multiple of it: whole 16-byte chunks both ways
 
 
 # ---- pure helpers (host) ---------------------------------------------------------------------------------------------
@@ -104,6 +111,71 @@ def _remove_permanent_frame(core, t, pos):
     mem.frame_id_to_permanent_mem_idx.pop(t, None)
     mem.version += 1
     mem.permanent_work_mem.remove_at(pos * mem.HW, mem.HW)
+
+
+class FeatureCache:
+    """Per-frame outputs of the hinted key pass in one device arena (see the module docstring), and the policy of using them.
+
+    * The entry layout - (shape, dtype) of one frame's key, shrinkage, selection, f16 and extras - is that of the first key pass after
+      construction, so it follows the network's precision mode; the arena, min(budget, n_frames * entry_bytes) bytes, is allocated then.
+    * Frames get an entry in the order they are first visited until the arena is full.  Nothing is ever evicted.
+    * An entry is TAGGED with the batch size of the key pass that filled it.  `lookup(batch)` serves a batch only when every frame of it
+      has an entry tagged len(batch); otherwise the batch runs the key pass, which overwrites and re-tags the entries of its frames
+      (`claim`).  The tag is what keeps "cache on" equal to "cache off" byte for byte: convolution plans are chosen per batch size, so
+      a frame encoded alone need not have the bits of the same frame encoded in a batch of four."""
+
+    def __init__(self, n_frames, budget_bytes, device):
+        self.n_frames, self.budget, self.device = int(n_frames), int(budget_bytes), device
+        self.layout = None
+        self.entry_bytes = 0
+        self.arena = None
+        self._slot = {}                        # frame -> index of its entry in the arena
+        self._tag = {}                         # frame -> batch size of the pass that filled the entry
+        self.capacity = 0
+        self.hits = self.misses = 0
+
+    def _entry(self, slot):
+        base, views = slot * self.entry_bytes, []
+        for shape, dtype in self.layout:
+            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+            views.append(self.arena[base:base + nbytes].view(dtype).view(shape))
+            base += -(-nbytes // ENTRY_ALIGN) * ENTRY_ALIGN
+        return tuple(views)
+
+    def lookup(self, batch):
+        """The entries of `batch` (frame indices) when all of them were filled by a pass of len(batch) frames, else None; counted."""
+        if all(self._tag.get(t) == len(batch) for t in batch):
+            self.hits += len(batch)
+            return [self._entry(self._slot[t]) for t in batch]
+        self.misses += len(batch)
+        return None
+
+    def claim(self, batch, layout):
+        """Called by the key pass of `batch` with its entry layout: the entry (or None: the arena is full) each frame is to be saved
+        to, now tagged len(batch)."""
+        layout = tuple((tuple(int(v) for v in shape), dtype) for shape, dtype in layout)
+        if self.layout is None:
+            self.layout = layout
+            self.entry_bytes = sum(-(-int(np.prod(sh)) * torch.empty((), dtype=dt).element_size() // ENTRY_ALIGN) * ENTRY_ALIGN
+                                   for sh, dt in layout)
+            self.capacity = min(self.n_frames, self.budget // self.entry_bytes)
+            self.arena = torch.empty(self.capacity * self.entry_bytes, dtype=torch.uint8, device=self.device)
+        elif layout != self.layout:
+            raise RuntimeError('FeatureCache: the key pass changed its output layout (one cache serves one geometry and precision)')
+        out = []
+        for t in batch:
+            if t not in self._slot and len(self._slot) < self.capacity:
+                self._slot[t] = len(self._slot)
+            if t in self._slot:
+                self._tag[t] = len(batch)
+                out.append(self._entry(self._slot[t]))
+            else:
+                out.append(None)
+        return out
+
+    def info(self):
+        return dict(entry_bytes=self.entry_bytes, frames=len(self._slot), bytes=self.arena.numel() if self.arena is not None else 0,
+                    hits=self.hits, misses=self.misses)
 
 
 class _Frame:
@@ -182,6 +254,8 @@ class VideoSession:
         self.masks = torch.zeros((n,) + tuple(self.shape), dtype=torch.uint8, device=self.device)   # dense ids (MaskMapper)
         self._present = [False] * n
         self._refs = {}                                                  # frame index -> the annotation's raw H x W index array
+        budget = int(config.get('session_feature_cache_bytes', 0))      # opt-in: the key pass of every frame kept on the device
+        self._fcache = FeatureCache(n, budget, self.device) if budget > 0 else None
         torch.cuda.synchronize()                                         # the frames are complete for every stream from here on
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
@@ -205,6 +279,13 @@ class VideoSession:
 
     def all_masks_present(self):
         return all(self._present)
+
+    def cache_info(self):
+        """dict(entry_bytes, frames, bytes, hits, misses) of the feature cache (`config['session_feature_cache_bytes']`): bytes of one
+        entry and of the arena, frames that own an entry, and frames served from it / sent to the key pass so far.  All zero while the
+        cache is off or no key pass has run."""
+        fc = getattr(self, '_fcache', None)
+        return fc.info() if fc is not None else dict(entry_bytes=0, frames=0, bytes=0, hits=0, misses=0)
 
     def _label_lut(self):
         """dense id -> original label value, as a host uint8[256] (identity while the annotation's ids are 1, 2, 3, ...)."""
@@ -324,9 +405,17 @@ class VideoSession:
         core, device = self.core, self.device
         on_device = all(t < self.n_device_frames for t in order)
 
+        fcache = getattr(self, '_fcache', None)
+
         def prefetch(batch):
             # resident frames were complete long ago (synchronised at construction): the pass may start under the current frame
-            return core.prefetch_keys([self.frame_u8(t) for t in batch], inputs_complete=on_device)
+            frames = [self.frame_u8(t) for t in batch]
+            if fcache is None:
+                return core.prefetch_keys(frames, inputs_complete=on_device)
+            entries = fcache.lookup(batch)
+            if entries is not None:                                      # every frame saved by a pass of this batch size: no key stage
+                return core.prefetch_cached(frames, entries, inputs_complete=on_device)
+            return core.prefetch_keys(frames, inputs_complete=on_device, save_to=lambda layout: fcache.claim(batch, layout))
 
         for i, (t, rgb) in enumerate(hinted(order, self.key_batch, prefetch)):
             fr = self.frames[t]
@@ -471,15 +560,22 @@ def parse_args(argv=None):
     ap.add_argument('--mask-form', default='objects', choices=MASK_FORMS)
     ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG')
     ap.add_argument('--overlay', action='store_true', help='write overlays next to the masks')
+    ap.add_argument('--feature-cache-gb', type=float, default=0.0,
+                    help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
     if args.rounds < 1 or args.k < 1:
         ap.error('--rounds and --k must be at least 1')
+    if args.feature_cache_gb < 0:
+        ap.error('--feature-cache-gb must not be negative')
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
-    s = VideoSession(args.images, args.masks, overwrite_config=json.loads(args.config) if args.config else None)
+    config = json.loads(args.config) if args.config else {}
+    if args.feature_cache_gb > 0:
+        config['session_feature_cache_bytes'] = int(args.feature_cache_gb * (1 << 30))
+    s = VideoSession(args.images, args.masks, overwrite_config=config or None)
     for t in sorted(int(x) for x in args.first.split(',') if x != ''):
         s.save_reference(t)
     chosen = []
