@@ -493,6 +493,25 @@ int xmem_resize_u8_bilinear_aa(const uint8_t* src, int Hs, int Ws, uint8_t* dst,
 #define XMEM_COPY_MAX_SEGMENTS 16
 int xmem_copy_segments(const void* const* src, void* const* dst, const size_t* bytes, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Run-length track export: the run boundaries, areas and boxes of uint8 label maps masks [N][H][W] (row-major), for the labels 1..K,
+ * in the COCO order j = x * H + y (column-major; the bottom pixel of column x and the top pixel of column x + 1 are neighbours).
+ * With b_k[j] = (masks[j] == k) and b_k[-1] = 0, an EVENT of label k is a j with b_k[j] != b_k[j - 1]; the uncompressed COCO counts of
+ * k are diff([0, events..., H * W]) (the host's part: per event, never per pixel).
+ *   meta    int32 [N][K][XMEM_RLE_META] per frame and label k (row k - 1): {events, area, x0, y0, x1, y1} - the TRUE number of events
+ *           (also when they did not fit), the number of pixels, the inclusive box; a label without a pixel has {0, 0, 0, 0, -1, -1}.
+ *   events  uint32 [N][capacity] per frame: the ascending event positions of label 1, then of label 2, ... packed back to back (label
+ *           k starts at the sum of the event counts of the labels before it).  Entries at and beyond `capacity` are not written: a
+ *           frame whose counts sum to more than `capacity` is to be encoded again with that sum as its capacity.
+ * Three launches (count, scan, emit) and no inter-workgroup waiting; the position of every event in the output follows from the scan,
+ * not from the arrival order of atomics, and the sums / minima / maxima are integer: the same input gives the same bytes.
+ * Labels above K (and 0) belong to no plane.  K in [1, 254], capacity >= 1 (else XMEM_ERR_BAD_ARG); H, W in [1, 16384], N <= 65535
+ * (else XMEM_ERR_UNSUPPORTED).  workspace: xmem_rle_workspace_bytes(N, W, K) bytes (0 for arguments outside those ranges), 4-byte aligned. */
+#define XMEM_RLE_META 6
+size_t xmem_rle_workspace_bytes(int N, int W, int K);
+int xmem_rle_encode(const uint8_t* masks, int N, int H, int W, int K, int capacity, int32_t* meta, uint32_t* events, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

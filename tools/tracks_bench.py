@@ -1,0 +1,146 @@
+"""What the run-length track export (config['save_tracks'], ops.rle_encode) costs and what it sends to the host.
+
+    python tools/tracks_bench.py [--frames 60] [--runs 3] [--reps 200] [--out FILE]
+
+1. The encode on its own: seeded label maps of K ragged ellipses at 480 x 854 and 1080 x 1920, K = 1 and 5; device events around
+   `--reps` back-to-back `ops.rle_encode(map, K, wait=False)` calls (the three launches and two clears of one frame), nothing else
+   running; next to it the events found, the bytes of the record that travels (meta + the default capacity), the bytes of it that
+   are used, and H * W, the mask it stands for.
+2. `run_on_video` on files: one synthetic 480 x 854 clip of `--frames` JPEG frames (nothing outside the repository is read; the
+   synthetic checkpoint), one network, `--runs` runs per mode alternating in one process after a warm-up run: save_masks only and
+   neither (with save_tracks off the loop is the parent commit's), both, tracks only.  Each figure is a host clock around the whole
+   call - preload, frame loop, writers joined - in frames per second.
+No figure is asserted."""
+import argparse
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+MODES = (('save_masks only (parent)', True, False), ('neither (parent, save_masks=False)', False, False),
+         ('save_masks + save_tracks', True, True), ('save_tracks only', False, True))
+
+
+def label_map(hw, k, seed=3, shift=0.0):
+    """uint8 H x W: k ellipses with a ragged rim (a seeded radial wobble), labels 1..k."""
+    import numpy as np
+    h, w = hw
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = np.zeros(hw, np.uint8)
+    for o in range(k):
+        cx, cy = w * (o + 1) / (k + 1) + shift, h * (0.5 + 0.12 * (o - (k - 1) / 2))
+        ang = np.arctan2(yy - cy, xx - cx)
+        wobble = 1 + 0.08 * np.sin(ang * rng.integers(5, 12) + rng.random() * 6) + 0.03 * np.sin(ang * rng.integers(20, 40))
+        out[(((yy - cy) / (h / 6)) ** 2 + ((xx - cx) / (w / (2.5 * (k + 1)))) ** 2) <= wobble ** 2] = o + 1
+    return out
+
+
+def encode_alone(emit, reps):
+    import torch
+    from xmem2_amd import ops, rle
+    emit('\n1. ops.rle_encode on its own (us per frame: count, scan, emit and the two clears)')
+    for hw in ((480, 854), (1080, 1920)):
+        for k in (1, 5):
+            dev = torch.from_numpy(label_map(hw, k)).cuda()
+            meta, events = ops.rle_encode(dev, k)
+            cap = rle.default_capacity(*hw)
+            for _ in range(5):
+                ops.rle_encode(dev, k, wait=False)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                ops.rle_encode(dev, k, wait=False)
+            e1.record()
+            torch.cuda.synchronize()
+            total = int(meta[0, :, 0].sum())
+            sent, used = 4 * (k * rle.META + cap), 4 * (k * rle.META + total)
+            emit(f'   {hw[0]:4d} x {hw[1]:4d}, K = {k}: {e0.elapsed_time(e1) * 1e3 / reps:7.1f} us;  {total:5d} events;  record {sent} B '
+                 f'(used {used} B) against a mask of {hw[0] * hw[1]} B: {hw[0] * hw[1] / sent:.1f}x ({hw[0] * hw[1] / used:.1f}x) fewer')
+
+
+def write_clip(root, t, hw, k):
+    from PIL import Image
+    from resize_ingest_bench import seeded_frame
+    imgs, msks = os.path.join(root, 'JPEGImages'), os.path.join(root, 'Annotations')
+    os.makedirs(imgs); os.makedirs(msks)
+    pal = [0, 0, 0, 200, 0, 0, 0, 200, 0, 0, 0, 200] + [0] * (256 * 3 - 12)
+    for i in range(t):
+        Image.fromarray(seeded_frame(hw, 5, shift=2 * i)).save(os.path.join(imgs, f'{i:05d}.jpg'), quality=90)
+        im = Image.fromarray(label_map(hw, k, shift=1.5 * i - 0.75 * t))
+        im.putpalette(pal)
+        im.save(os.path.join(msks, f'{i:05d}.png'))
+    return imgs, msks
+
+
+def video(emit, frames, runs):
+    import torch
+    from session_bench import save_checkpoint
+    from xmem2_amd.network import XMem
+    from xmem2_amd.run_on_video import run_on_video
+    hw = (480, 854)
+    with tempfile.TemporaryDirectory() as tmp:
+        model = save_checkpoint(os.path.join(tmp, 'XMem_synth.pth'))
+        net = XMem({'model': model, 'size': 480}, model).to('cuda').eval()
+        imgs, msks = write_clip(os.path.join(tmp, 'clip'), frames, hw, 1)
+
+        def run(tag, masks, tracks, n):
+            out = os.path.join(tmp, f'out_{n}')
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run_on_video(imgs, msks, out, frames_with_masks=[0], print_progress=False, save_overlay=False, network=net,
+                         overwrite_config={'model': model, 'size': 480, 'save_masks': masks, 'save_tracks': tracks})
+            torch.cuda.synchronize()
+            return frames / (time.perf_counter() - t0)
+        from xmem2_amd import ops
+        run('warm-up', True, True, 0)
+        before = dict(ops.RLE_STATS)
+        fps = {tag: [] for tag, _, _ in MODES}
+        n = 1
+        for _ in range(runs):
+            for tag, masks, tracks in MODES:
+                fps[tag].append(run(tag, masks, tracks, n))
+                n += 1
+        emit(f'\n2. run_on_video on files, {frames} JPEG frames of {hw[0]} x {hw[1]}, one object, one reference; frames per second of the '
+             f'whole call, {runs} runs per mode alternating')
+        for tag, _, _ in MODES:
+            emit(f'   {tag:36s} ' + ' '.join(f'{v:7.1f}' for v in fps[tag]) + f'   median {statistics.median(fps[tag]):7.1f}')
+        import json
+        path = os.path.join(tmp, f'out_{n - 1}', 'tracks.json')
+        doc = json.load(open(path))
+        per_frame = [len(s['counts']) - 1 for a in doc['annotations'] for s in a['segmentations'] if s is not None]
+        emit(f'   tracks.json of the clip: {os.path.getsize(path)} bytes; events per frame of the PREDICTED masks (synthetic weights: ragged): '
+             f'min {min(per_frame)}, median {int(statistics.median(per_frame))}, max {max(per_frame)}; default capacity '
+             f'{__import__("xmem2_amd.rle", fromlist=["rle"]).default_capacity(*hw)}')
+        emit(f'   encode calls in the timed runs: {ops.RLE_STATS["launches"] - before["launches"]} for {2 * runs * frames} frames; frames '
+             f'encoded again because their events did not fit: {ops.RLE_STATS["retries"] - before["retries"]}')
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--frames', type=int, default=60)
+    ap.add_argument('--runs', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=200)
+    ap.add_argument('--out', default=None, help='also append the report to this file')
+    args = ap.parse_args()
+    import torch
+    torch.set_grad_enabled(False)
+
+    def emit(line):
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'a') as f:
+                f.write(line + '\n')
+    emit(f'tools/tracks_bench.py on {torch.cuda.get_device_name(0)}: run-length track export, precision fp32')
+    encode_alone(emit, args.reps)
+    video(emit, args.frames, args.runs)
+
+
+if __name__ == '__main__':
+    main()

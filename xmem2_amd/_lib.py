@@ -39,6 +39,7 @@ class ConvPlanInfo(C.Structure):
 CONV_FORMS = ('gemv', 'direct', 'f2', 'f2_fused', 'f2_f16', 'f4')    # include/xmem_hip.h XMEM_CONV_*
 UNSUPPORTED = -2         # include/xmem_hip.h XMEM_ERR_UNSUPPORTED
 DILATED_NO_TAP_SKIP = 1  # include/xmem_hip.h XMEM_DILATED_NO_TAP_SKIP
+RLE_META = 6             # include/xmem_hip.h XMEM_RLE_META: int32 values per (frame, label) of xmem_rle_encode's meta
 COPY_MAX_SEGMENTS = 16   # include/xmem_hip.h XMEM_COPY_MAX_SEGMENTS: (src, dst, bytes) triples one xmem_copy_segments launch carries
 
 
@@ -142,6 +143,9 @@ _SIGS = {
     'xmem_resize_u8_bilinear_aa': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     'xmem_copy_segments': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
+    'xmem_rle_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'xmem_rle_encode': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
     'xmem_nhwc_to_nchw': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'xmem_nchw_to_nhwc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'xmem_affinity_topk_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -1,4 +1,4 @@
-"""Inference configuration: same keys and defaults as VIDEO_INFERENCE_CONFIG (util/configuration.py:138-162)."""
+"""Inference configuration: the keys and defaults of VIDEO_INFERENCE_CONFIG (util/configuration.py:138-162), and this project's opt-ins."""
 
 VIDEO_INFERENCE_CONFIG = {
     'buffer_size': 100,
@@ -24,4 +24,5 @@ VIDEO_INFERENCE_CONFIG = {
     'masks_out_path': None,
     'workspace': None,
     'save_masks': True,
+    'save_tracks': False,       # not in the reference: write <masks_out_path>/tracks.json, run-length tracks encoded on the device (rle.py)
 }

@@ -1292,6 +1292,54 @@ def next_click(d2, not_clicked, counts=None, record=None):
     return record
 
 
+# ---- run-length track export (csrc/rle.hip): integer arithmetic, bit-reproducible -------------------------------------
+
+RLE_STATS = {'launches': 0, 'retries': 0}      # calls of xmem_rle_encode / frames encoded again because their events did not fit
+
+
+def rle_encode(masks, K, capacity=None, wait=True):
+    """Run boundaries, areas and boxes of the labels 1..K of uint8 label maps `masks` [H,W] or [B,H,W] in the COCO order x * H + y
+    (xmem2_amd/rle.py has the definitions).  `capacity`: events per frame there is room for (default `rle.default_capacity`).
+    wait=True: returns (meta int32 [B,K,6] = events, area, x0, y0, x1, y1 per label, list of B uint32 arrays: the frame's events of
+    label 1, 2, ... back to back) on the HOST; a frame whose events did not fit is encoded again with exactly its size - nothing is
+    ever cut off.  wait=False: one launch sequence on the current stream and no synchronisation; returns the int32 device tensor
+    `rle.split_record(., B, K, capacity)` takes apart, whose true counts tell the caller which frames to encode again."""
+    from . import rle
+    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
+        raise RuntimeError('masks: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
+    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= 254):
+        raise ValueError(f'rle_encode: K = {K!r} must be an integer in 1..254')
+    masks = masks.contiguous()
+    B, H, W = (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
+    if B == 0 or H == 0 or W == 0:
+        raise RuntimeError(f'rle_encode: empty input {tuple(masks.shape)}')
+    capacity = rle.default_capacity(H, W) if capacity is None else int(capacity)
+    if capacity < 1:
+        raise ValueError(f'rle_encode: capacity = {capacity} must be at least 1')
+    lib = load()
+    rec = torch.empty(B * K * rle.META + B * capacity, dtype=torch.int32, device=masks.device)
+    nbytes = lib.xmem_rle_workspace_bytes(B, W, K)
+    ws = workspace(max(nbytes, 4), masks.device, 'rle')
+    RLE_STATS['launches'] += 1
+    check(lib.xmem_rle_encode(ptr(masks), B, H, W, K, capacity, ptr(rec), C.c_void_p(rec.data_ptr() + 4 * B * K * rle.META), ptr(ws),
+                              ws.numel(), stream_ptr()))
+    if not wait:
+        return rec
+    meta, events = rle.split_record(rec.cpu().numpy(), B, K, capacity)
+    out = []
+    for b in range(B):
+        total = int(meta[b, :, 0].sum())
+        if total > capacity:                                  # the counts are the true ones: once more, with room for all of them
+            RLE_STATS['retries'] += 1
+            meta_b, ev_b = rle_encode(masks[b:b + 1], K, capacity=total)
+            if (meta_b[0] != meta[b]).any():
+                raise RuntimeError('rle_encode: a frame encoded again gave other counts')
+            out.append(ev_b[0])
+        else:
+            out.append(events[b, :total].copy())
+    return meta.copy(), out
+
+
 # ---- f-BRS click refinement (csrc/brs.hip): every kernel bit-reproducible --------------------------------------------
 
 BRS_RECORD = 8          # floats of the evaluation record ahead of the gradient (include/xmem_hip.h, xmem_brs_loss)

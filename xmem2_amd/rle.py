@@ -1,0 +1,243 @@
+"""Run-length object tracks: the host side of `ops.rle_encode` and the file `<masks_out_path>/tracks.json`.
+
+The specification (plain numpy, `encode_host` / `decode`), which the kernel of csrc/rle.hip is tested against:
+
+* the COCO order of pixel (y, x) of an H x W plane is j = x * H + y (column-major; the bottom pixel of column x and the top pixel of
+  column x + 1 are neighbours, a run continues across them);
+* for label k the binary plane is b_k[j] = (mask[j] == k) with b_k[-1] := 0; an EVENT of k is a j with b_k[j] != b_k[j - 1];
+* the uncompressed COCO counts of k are diff([0, events..., H * W]): they start with the run of zeros (0 long when pixel 0 belongs to
+  k), every later count is positive, they sum to H * W.
+
+The device finds the events, areas and boxes (`ops.rle_encode`); the host turns events into counts (`counts_from_events`) - work per
+event, never per pixel.  `TrackWriter` collects one video's frames into the YouTube-VIS layout
+
+    {"videos": [{"id": 1, "height": H, "width": W, "length": T, "file_names": [...]}],
+     "categories": [{"id": 1, "name": "object"}],
+     "annotations": [{"id": n, "video_id": 1, "category_id": 1, "label": <label in the annotation PNGs>,
+                      "segmentations": [{"size": [H, W], "counts": [...]} | null, ...],      one entry per frame
+                      "bboxes": [[x, y, w, h] | null, ...], "areas": [int | null, ...]}]}
+
+`counts` is the uncompressed list form, which COCO tools accept; the compressed string form is not built.  A frame in which a label
+has no pixel, or which has no mask at all, carries null in all three lists.  `python -m xmem2_amd.rle --tracks F --out DIR` is the way
+back: tracks to index PNGs.
+"""
+import argparse
+import collections
+import json
+import os
+import sys
+
+import numpy as np
+
+META = 6                                        # int32 per (frame, label): events, area, x0, y0, x1, y1 (include/xmem_hip.h XMEM_RLE_META)
+EMPTY_BOX = (0, 0, -1, -1)
+MIN_CAPACITY = 2048
+
+HostRle = collections.namedtuple('HostRle', 'events counts area box')
+
+
+def default_capacity(h, w):
+    """Events per frame `ops.rle_encode` makes room for when it is not told: a label that crosses every column of the frame in two runs
+    has 4 * W events, the clips measured so far stay far below it; more is never lost, the frame is encoded again."""
+    return max(MIN_CAPACITY, 4 * int(w))
+
+
+def counts_from_events(events, h, w):
+    """Ascending event positions of one label -> its uncompressed COCO counts (a list of ints)."""
+    ev = np.asarray(events, dtype=np.int64).reshape(-1)
+    return np.diff(np.concatenate(([0], ev, [int(h) * int(w)]))).tolist()
+
+
+def encode_host(mask, k):
+    """The specification: label k of an H x W index array -> HostRle(events uint32 [E], counts list, area, box (x0, y0, x1, y1)
+    inclusive; EMPTY_BOX without a pixel)."""
+    mask = np.asarray(mask)
+    if mask.ndim != 2:
+        raise ValueError(f'encode_host: expected an H x W array, got shape {mask.shape}')
+    h, w = mask.shape
+    plane = mask == k
+    b = plane.T.reshape(-1)                                          # column-major
+    events = np.flatnonzero(b != np.concatenate(([False], b[:-1]))).astype(np.uint32)
+    area = int(b.sum())
+    if area:
+        ys, xs = np.flatnonzero(plane.any(axis=1)), np.flatnonzero(plane.any(axis=0))
+        box = (int(xs[0]), int(ys[0]), int(xs[-1]), int(ys[-1]))
+    else:
+        box = EMPTY_BOX
+    return HostRle(events, counts_from_events(events, h, w), area, box)
+
+
+def decode(counts, h, w):
+    """Uncompressed COCO counts -> bool [h, w]."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if counts.size == 0 or (counts < 0).any() or (counts[1:] == 0).any() or int(counts.sum()) != int(h) * int(w):
+        raise ValueError(f'decode: counts do not describe a {h} x {w} plane')
+    values = (np.arange(counts.size) & 1).astype(bool)
+    return np.repeat(values, counts).reshape(int(w), int(h)).T
+
+
+def split_record(buf, n_frames, k, capacity):
+    """The int32 words one `ops.rle_encode` launch leaves ([n_frames * k * META] meta, then [n_frames * capacity] events) ->
+    (meta int32 [n_frames, k, META], events uint32 [n_frames, capacity]) as views."""
+    buf = np.asarray(buf).reshape(-1).view(np.int32)
+    cut = n_frames * k * META
+    return buf[:cut].reshape(n_frames, k, META), buf[cut:cut + n_frames * capacity].view(np.uint32).reshape(n_frames, capacity)
+
+
+def label_events(meta, events):
+    """One frame's packed events -> the list of per-label event arrays (label 1 first).  `meta` [K, META] holds the true counts; the
+    frame must have been encoded with room for all of them."""
+    n = meta[:, 0].astype(np.int64)
+    if int(n.sum()) > len(events):
+        raise ValueError(f'label_events: {int(n.sum())} events, but only {len(events)} were kept - encode the frame again')
+    ends = np.cumsum(n)
+    return [events[e - c:e] for c, e in zip(n, ends)]
+
+
+def record_host(mask, k):
+    """(meta [k, META], packed events) of an H x W index array as `ops.rle_encode` returns them for one frame, by `encode_host`."""
+    meta = np.zeros((k, META), np.int32)
+    ev = []
+    for lab in range(1, k + 1):
+        r = encode_host(mask, lab)
+        meta[lab - 1] = (len(r.events), r.area) + tuple(r.box)
+        ev.append(r.events)
+    return meta, np.concatenate(ev) if ev else np.zeros(0, np.uint32)
+
+
+class TrackWriter:
+    """One video's tracks.  Frames are added in order; a track is opened when its label is first named and has null wherever the
+    label was not known yet, had no pixel, or the frame had no mask."""
+
+    def __init__(self, height, width):
+        self.height, self.width = int(height), int(width)
+        self.file_names = []
+        self._tracks = collections.OrderedDict()                     # label in the annotation PNGs -> {frame index: (counts, bbox, area)}
+
+    def add_frame(self, file_name, meta=None, events=None, labels=None):
+        """`meta` [K, META] and the frame's packed `events` as `ops.rle_encode` gives them (`events` holding all of them), `labels`
+        the annotation's label of every row (default 1..K; `inverse_labels`).  Without `meta` the frame has no mask."""
+        t = len(self.file_names)
+        self.file_names.append(str(file_name))
+        if meta is None:
+            return
+        meta = np.asarray(meta)
+        labels = list(range(1, len(meta) + 1)) if labels is None else [int(v) for v in labels]
+        if len(labels) != len(meta):
+            raise ValueError(f'add_frame: {len(meta)} label rows, {len(labels)} labels')
+        for lab, row, ev in zip(labels, meta, label_events(meta, events)):
+            track = self._tracks.setdefault(lab, {})
+            area = int(row[1])
+            if area:
+                x0, y0, x1, y1 = (int(v) for v in row[2:6])
+                track[t] = (counts_from_events(ev, self.height, self.width), [x0, y0, x1 - x0 + 1, y1 - y0 + 1], area)
+
+    def add_mask(self, file_name, mask, k=None, labels=None):
+        """A frame from a host index array (dense ids 1..k, default its largest id), encoded on the host; None: a frame without mask."""
+        if mask is None:
+            return self.add_frame(file_name)
+        mask = np.asarray(mask)
+        if tuple(mask.shape) != (self.height, self.width):
+            raise ValueError(f'add_mask: expected {(self.height, self.width)}, got {tuple(mask.shape)}')
+        k = int(mask.max()) if k is None else int(k)
+        if k == 0:
+            return self.add_frame(file_name, np.zeros((0, META), np.int32), np.zeros(0, np.uint32), [])
+        return self.add_frame(file_name, *record_host(mask, k), labels=labels)
+
+    def to_dict(self):
+        T, size = len(self.file_names), [self.height, self.width]
+        anns = []
+        for n, (lab, track) in enumerate(self._tracks.items(), start=1):
+            seg = [{'size': size, 'counts': track[t][0]} if t in track else None for t in range(T)]
+            anns.append({'id': n, 'video_id': 1, 'category_id': 1, 'label': lab, 'segmentations': seg,
+                         'bboxes': [track[t][1] if t in track else None for t in range(T)],
+                         'areas': [track[t][2] if t in track else None for t in range(T)]})
+        return {'videos': [{'id': 1, 'height': self.height, 'width': self.width, 'length': T, 'file_names': list(self.file_names)}],
+                'categories': [{'id': 1, 'name': 'object'}], 'annotations': anns}
+
+    def write(self, path):
+        """Write the file (`path`: the file, or a directory that gets tracks.json); returns the file's path."""
+        path = str(path)
+        if os.path.isdir(path) or not path.endswith('.json'):
+            os.makedirs(path, exist_ok=True)
+            path = os.path.join(path, 'tracks.json')
+        elif os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        text = json.dumps(self.to_dict(), separators=(',', ':'))      # dumps, not dump: one pass of the C encoder
+        with open(path, 'w') as f:
+            f.write(text)
+        return path
+
+
+def inverse_labels(mapper, k):
+    """The annotation's label of the dense ids 1..k of a MaskMapper (`remap_index_mask`, per label instead of per pixel)."""
+    inv = {dense: original for original, dense in mapper.remappings.items()}
+    return [int(inv.get(d, d)) for d in range(1, k + 1)]
+
+
+def read_tracks(path):
+    """tracks.json -> (video dict, list of index masks uint8 [H, W] holding the annotations' labels, None for a frame in which no
+    track has an entry)."""
+    with open(path) as f:
+        doc = json.load(f)
+    if len(doc.get('videos', [])) != 1:
+        raise ValueError('read_tracks: expected one video per file')
+    video = doc['videos'][0]
+    h, w, T = int(video['height']), int(video['width']), int(video['length'])
+    masks = [None] * T
+    for ann in doc['annotations']:
+        lab = int(ann['label'])
+        if not (1 <= lab <= 255):
+            raise ValueError(f'read_tracks: label {lab} does not fit an index PNG')
+        if not (len(ann['segmentations']) == len(ann['bboxes']) == len(ann['areas']) == T):
+            raise ValueError(f'read_tracks: track {ann["id"]} does not have one entry per frame')
+        for t, seg in enumerate(ann['segmentations']):
+            if seg is None:
+                continue
+            if list(seg['size']) != [h, w]:
+                raise ValueError(f'read_tracks: track {ann["id"]}, frame {t}: size {seg["size"]} is not the video\'s {[h, w]}')
+            if masks[t] is None:
+                masks[t] = np.zeros((h, w), np.uint8)
+            masks[t][decode(seg['counts'], h, w)] = lab
+    return video, masks
+
+
+def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
+    """Write every frame of tracks.json as an index PNG `<out_dir>/<frame>.png` whose pixel values are the tracks' labels (mode P with
+    the palette of the PNG `palette_from`, else mode L).  A frame without any entry is written all zero (`empty_frames`) or left out.
+    Returns the written paths."""
+    from PIL import Image
+    video, masks = read_tracks(tracks)
+    palette = None
+    if palette_from is not None:
+        palette = Image.open(palette_from).convert('P').getpalette()
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name, m in zip(video['file_names'], masks):
+        if m is None:
+            if not empty_frames:
+                continue
+            m = np.zeros((video['height'], video['width']), np.uint8)
+        img = Image.fromarray(m)
+        if palette is not None:
+            img.putpalette(palette)                                  # mode L becomes mode P: the pixel values are the indices
+        path = os.path.join(out_dir, os.path.splitext(name)[0] + '.png')
+        img.save(path)
+        written.append(path)
+    return written
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle', description='tracks.json -> index PNGs (one per frame)')
+    ap.add_argument('--tracks', required=True, help='the tracks.json of one video')
+    ap.add_argument('--out', required=True, help='directory the PNGs are written to')
+    ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
+    ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
+    args = ap.parse_args(argv)
+    written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty)
+    print(json.dumps({'frames': len(written), 'out': args.out}))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -280,6 +280,45 @@ def _post_process(sample, prob):
     return ops.argmax_u8(prob).cpu().numpy()
 
 
+class _TrackLoop:
+    """config['save_tracks'] inside a frame loop: one `ops.rle_encode` launch sequence per frame on the compute stream, the record
+    delivered through pinned memory one frame behind like the mask (its own AsyncMaskFetcher, fed right before the mask's: when the
+    mask of a frame has arrived, so has its record), the counts made on the host per event, the file written at the end.  A frame
+    whose events did not fit is encoded again when its record arrives, and the capacity of the frames after it grows to twice its size."""
+
+    def __init__(self):
+        self.writer = self.capacity = None                           # made for the first frame's size (that of the written PNGs)
+        self.fetcher = AsyncMaskFetcher()
+
+    def submit(self, tag, mask_dev, k):
+        """-> the (tag, record) pairs that have arrived.  `mask_dev` must stay untouched until its record was delivered: it is
+        encoded again should its events not fit."""
+        if self.writer is None:
+            from .rle import TrackWriter, default_capacity
+            self.writer, self.capacity = TrackWriter(*mask_dev.shape), default_capacity(*mask_dev.shape)
+        rec = ops.rle_encode(mask_dev, k, self.capacity, wait=False)
+        return self.fetcher.submit((tag, mask_dev, k, self.capacity), rec.view(torch.uint8))
+
+    def drain(self):
+        return self.fetcher.drain()
+
+    def finish(self, item, name, mapper):
+        from .rle import inverse_labels, split_record
+        (_, mask_dev, k, capacity), buf = item
+        meta, events = split_record(buf, 1, k, capacity)
+        meta, events = meta[0], events[0]
+        total = int(meta[:, 0].sum())
+        if total > capacity:                                         # the exact size is known now: once more, nothing is cut off
+            ops.RLE_STATS['retries'] += 1
+            meta_all, ev_all = ops.rle_encode(mask_dev, k, capacity=total)
+            meta, events = meta_all[0], ev_all[0]
+            self.capacity = max(self.capacity, 2 * total)            # and the frames to come get room for a video as ragged as this
+        self.writer.add_frame(name, meta, events, inverse_labels(mapper, k))
+
+    def write(self, masks_out_path):
+        return self.writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
+
+
 def _working_u8(src_u8, target_hw, device, flip=False):
     """resize_on_device outside the frame loop (preloads, key extraction): upload a source-size frame (or take a device one) and
     resize it on the current stream."""
@@ -399,6 +438,10 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
     fetcher = AsyncMaskFetcher()
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
+    # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).  The
+    # H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou.
+    tracks = _TrackLoop() if config.get('save_tracks', False) else None
+    need_mask = tracks is None or saver is not None or compute_iou
 
     def finish(tag, out_mask):                                       # host side of a frame whose mask has arrived
         sample, had_mask = tag
@@ -455,15 +498,24 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
             out_dev = _post_process_gpu(sample, prob)
             if scorer is not None and sample.mask is not None:
                 scorer.add(ti, sample.mask, out_dev, mapper)
-            done = fetcher.submit((sample, msk is not None), out_dev)
+            tag = (sample, msk is not None)
+            tdone = tracks.submit(tag, out_dev, len(mapper.labels)) if tracks is not None else ()
+            done = fetcher.submit(tag, out_dev) if need_mask else [(it[0][0], None) for it in tdone]
             total_time += perf_counter() - a
+            for item in tdone:
+                tracks.finish(item, item[0][0][0].frame, mapper)
             for tag, out_mask in done:
                 finish(tag, out_mask)
         a = perf_counter()
-        done = fetcher.drain()
+        tdone = tracks.drain() if tracks is not None else ()
+        done = fetcher.drain() if need_mask else [(it[0][0], None) for it in tdone]
         total_time += perf_counter() - a
+        for item in tdone:
+            tracks.finish(item, item[0][0][0].frame, mapper)
         for tag, out_mask in done:
             finish(tag, out_mask)
+        if tracks is not None:
+            tracks.write(config['masks_out_path'])
     finally:
         decoder.close()
         loop_wall = perf_counter() - loop_t0
@@ -676,6 +728,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     fetcher = AsyncMaskFetcher()
     mapper = mappers[0]
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
+    tracks = _TrackLoop() if config.get('save_tracks', False) else None     # as in run_on_video, on the merged mask
+    need_mask = tracks is None or saver is not None or compute_iou
 
     def finish(tag, out_mask):                                       # as in run_on_video, on the merged mask
         sample, had_mask = tag
@@ -748,15 +802,25 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                 ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
             if scorer is not None and sample.mask is not None:
                 scorer.add(ti, sample.mask, merged, mapper)
-            done = fetcher.submit((sample, given), merged)
+            tag = (sample, given)
+            # `merged` is written again by the next frame: the record keeps a copy for the case that it has to be encoded again
+            tdone = tracks.submit(tag, merged.clone(), len(mapper.labels)) if tracks is not None else ()
+            done = fetcher.submit(tag, merged) if need_mask else [(it[0][0], None) for it in tdone]
             total_time += perf_counter() - a
+            for item in tdone:
+                tracks.finish(item, item[0][0][0].frame, mapper)
             for tag, out_mask in done:
                 finish(tag, out_mask)
         a = perf_counter()
-        done = fetcher.drain()
+        tdone = tracks.drain() if tracks is not None else ()
+        done = fetcher.drain() if need_mask else [(it[0][0], None) for it in tdone]
         total_time += perf_counter() - a
+        for item in tdone:
+            tracks.finish(item, item[0][0][0].frame, mapper)
         for tag, out_mask in done:
             finish(tag, out_mask)
+        if tracks is not None:
+            tracks.write(config['masks_out_path'])
     finally:
         decoder.close()
         loop_wall = perf_counter() - loop_t0

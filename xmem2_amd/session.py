@@ -500,6 +500,29 @@ class VideoSession:
         finally:
             saver.close()
 
+    def save_tracks(self, masks_out_path, batch=32):
+        """<masks_out_path>/tracks.json (xmem2_amd/rle.py) of the masks as they stand: the frames that have one are encoded from the
+        resident `masks` in launches of `batch` frames and only their run boundaries, areas and boxes reach the host; a frame without a
+        mask has null in every track.  Returns the file's path."""
+        from .rle import TrackWriter, inverse_labels
+        k = len(self.mapper.labels)
+        if k == 0:
+            raise ValueError('No valid masks provided!')
+        labels = inverse_labels(self.mapper, k)
+        writer = TrackWriter(*self.shape)
+        present = [t for t, p in enumerate(self._present) if p]
+        encoded = {}
+        for i in range(0, len(present), max(1, int(batch))):
+            chunk = present[i:i + max(1, int(batch))]
+            contiguous = chunk == list(range(chunk[0], chunk[-1] + 1))
+            dev = self.masks[chunk[0]:chunk[-1] + 1] if contiguous else self.masks[torch.tensor(chunk, device=self.device)]
+            meta, events = ops.rle_encode(dev, k)
+            for j, t in enumerate(chunk):
+                encoded[t] = (meta[j], events[j])
+        for t, fr in enumerate(self.frames):
+            writer.add_frame(fr.frame, *encoded.get(t, (None, None)), labels=labels)
+        return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
+
     def stats(self, compute_iou=False, compute_jf=False):
         """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
         import pandas as pd
@@ -560,6 +583,7 @@ def parse_args(argv=None):
     ap.add_argument('--mask-form', default='objects', choices=MASK_FORMS)
     ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG')
     ap.add_argument('--overlay', action='store_true', help='write overlays next to the masks')
+    ap.add_argument('--tracks', action='store_true', help='write <out>/tracks.json, run-length tracks encoded on the device, next to the masks')
     ap.add_argument('--feature-cache-gb', type=float, default=0.0,
                     help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
@@ -589,6 +613,8 @@ def main(argv=None):
                                   mask_form=args.mask_form) if len(s.references) < len(s) else []
         print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
     s.save(args.out, save_overlay=args.overlay)
+    if args.tracks:
+        s.save_tracks(args.out)
     return 0
 
 
