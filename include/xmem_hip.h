@@ -512,6 +512,20 @@ size_t xmem_rle_workspace_bytes(int N, int W, int K);
 int xmem_rle_encode(const uint8_t* masks, int N, int H, int W, int K, int capacity, int32_t* meta, uint32_t* events, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* The inverse of xmem_rle_encode's record: label maps masks uint8 [N][H][W] from meta [N][K][XMEM_RLE_META] and events [N][capacity].
+ * Of `meta` only field 0 is read, the number of events of row k; the rows' ascending event lists are packed back to back per frame.
+ * Pixel (y, x), j = x * H + y, belongs to row k iff the number of events e of row k with e <= j is odd (a row with an odd number of
+ * events runs to the last pixel, as counts = diff([0, events..., H * W]) says).  `masks` is written completely: a pixel gets
+ * values[k - 1] (k when `values` is NULL) of the HIGHEST row that contains it, else 0 - rows from the encoder never overlap, rows
+ * from other tools may, and the later one wins.
+ *   status  int32 [N]: 0 for a good frame; 1 when the frame's counts sum to more than `capacity` (or one is negative): that frame is
+ *           written all zero, and no event at or beyond `capacity` is ever read.
+ * One launch, no workspace, no atomics: every thread computes and stores only pixels it owns, so no event value steers a store and the
+ * same input gives the same bytes.  A NULL meta / events / masks / status is XMEM_ERR_BAD_ARG; outside H, W in [1, 16384],
+ * K in [1, 254], N in [1, 65535], capacity >= 1 the call is XMEM_ERR_UNSUPPORTED. */
+int xmem_rle_decode(const int32_t* meta, const uint32_t* events, int N, int H, int W, int K, int capacity, const uint8_t* values,
+                    uint8_t* masks, int32_t* status, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

@@ -10,7 +10,12 @@
    synthetic checkpoint), one network, `--runs` runs per mode alternating in one process after a warm-up run: save_masks only and
    neither (with save_tracks off the loop is the parent commit's), both, tracks only.  Each figure is a host clock around the whole
    call - preload, frame loop, writers joined - in frames per second.
-No figure is asserted."""
+3. The decode on its own (`ops.rle_decode`, one launch), at the sizes of part 1: device events around `--reps` back-to-back decodes
+   of the device record `ops.rle_encode(map, K, wait=False)` left, checked once against the map.
+4. `metrics.compute_metrics` on one synthetic 480 x 854 video of `--frames` frames whose predictions exist twice, as the palette
+   PNGs `run_on_video` writes and as tracks.json: frames per second of the whole call from each, `--runs` runs alternating after a
+   warm-up.  The PNG row is the parent commit's code path.
+`--only` picks parts.  No figure is asserted."""
 import argparse
 import os
 import statistics
@@ -121,12 +126,73 @@ def video(emit, frames, runs):
              f'encoded again because their events did not fit: {ops.RLE_STATS["retries"] - before["retries"]}')
 
 
+def decode_alone(emit, reps):
+    import torch
+    from xmem2_amd import ops, rle
+    emit('\n3. ops.rle_decode on its own (us per frame: one launch, from the device record of ops.rle_encode)')
+    for hw in ((480, 854), (1080, 1920)):
+        for k in (1, 5):
+            dev = torch.from_numpy(label_map(hw, k)).cuda()
+            cap = rle.default_capacity(*hw)
+            rec = ops.rle_encode(dev, k, cap, wait=False)
+            out = torch.empty((1,) + hw, dtype=torch.uint8, device='cuda')
+            for _ in range(5):
+                ops.rle_decode(rec, *hw, k, cap, out=out, check=False)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                ops.rle_decode(rec, *hw, k, cap, out=out, check=False)
+            e1.record()
+            torch.cuda.synchronize()
+            exact = bool(torch.equal(ops.rle_decode(rec, *hw, k, cap)[0], dev))
+            emit(f'   {hw[0]:4d} x {hw[1]:4d}, K = {k}: {e0.elapsed_time(e1) * 1e3 / reps:7.1f} us;  equal to the encoded map: {exact}')
+
+
+def evaluate(emit, frames, runs):
+    import torch
+    from PIL import Image
+    from xmem2_amd.metrics import compute_metrics
+    from xmem2_amd.rle import TrackWriter
+    hw = (480, 854)
+    pal = [0, 0, 0, 200, 0, 0, 0, 200, 0, 0, 0, 200] + [0] * (256 * 3 - 12)
+    with tempfile.TemporaryDirectory() as tmp:
+        gt, png, trk = (os.path.join(tmp, d, 'clip') for d in ('gt', 'png', 'tracks'))
+        os.makedirs(gt); os.makedirs(os.path.join(png, 'masks')); os.makedirs(trk)
+        writer = TrackWriter(*hw)
+        for i in range(frames):
+            truth = label_map(hw, 1, shift=1.5 * i - 0.75 * frames)
+            pred = label_map(hw, 1, seed=4, shift=1.5 * i - 0.75 * frames + 3)
+            for d, m in ((gt, truth), (os.path.join(png, 'masks'), pred)):
+                im = Image.fromarray(m)
+                im.putpalette(pal)
+                im.save(os.path.join(d, f'{i:05d}.png'), compress_level=1)       # as the writers of run_on_video save them
+            writer.add_mask(f'{i:05d}.png', pred)
+        writer.write(trk)
+        frames_of = {'from PNGs (parent)': os.path.join(tmp, 'png'), 'from tracks.json': os.path.join(tmp, 'tracks')}
+        tables = {tag: compute_metrics(os.path.join(tmp, 'gt'), d) for tag, d in frames_of.items()}      # warm-up, and the check
+        same = tables['from PNGs (parent)'].equals(tables['from tracks.json'])
+        fps = {tag: [] for tag in frames_of}
+        for _ in range(runs):
+            for tag, d in frames_of.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                compute_metrics(os.path.join(tmp, 'gt'), d)
+                fps[tag].append(frames / (time.perf_counter() - t0))
+        emit(f'\n4. metrics.compute_metrics, one video of {frames} frames of {hw[0]} x {hw[1]}, one object, ground truth from PNGs (8 decode '
+             f'threads); frames per second of the whole call, {runs} runs per source alternating; the two tables are equal: {same}')
+        for tag in frames_of:
+            emit(f'   {tag:36s} ' + ' '.join(f'{v:7.1f}' for v in fps[tag]) + f'   median {statistics.median(fps[tag]):7.1f}')
+        emit(f'   tracks.json: {os.path.getsize(os.path.join(trk, "tracks.json"))} bytes; the prediction PNGs: '
+             f'{sum(os.path.getsize(os.path.join(png, "masks", f)) for f in os.listdir(os.path.join(png, "masks")))} bytes')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--frames', type=int, default=60)
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=None, help='also append the report to this file')
+    ap.add_argument('--only', default='encode,video,decode,evaluate', help='comma-separated parts: encode, video, decode, evaluate')
     args = ap.parse_args()
     import torch
     torch.set_grad_enabled(False)
@@ -138,8 +204,15 @@ def main():
             with open(args.out, 'a') as f:
                 f.write(line + '\n')
     emit(f'tools/tracks_bench.py on {torch.cuda.get_device_name(0)}: run-length track export, precision fp32')
-    encode_alone(emit, args.reps)
-    video(emit, args.frames, args.runs)
+    parts = set(args.only.split(','))
+    if 'encode' in parts:
+        encode_alone(emit, args.reps)
+    if 'video' in parts:
+        video(emit, args.frames, args.runs)
+    if 'decode' in parts:
+        decode_alone(emit, args.reps)
+    if 'evaluate' in parts:
+        evaluate(emit, args.frames, args.runs)
 
 
 if __name__ == '__main__':

@@ -185,6 +185,81 @@ __global__ __launch_bounds__(RLE_SCAN_THREADS) void rle_scan_kernel(int* __restr
     }
 }
 
+// The inverse of the record (include/xmem_hip.h, xmem_rle_decode): output-driven.  A lane owns RLE_DEC_COLS adjacent columns over
+// RLE_DEC_ROWS rows, holds their bytes in registers and stores nothing else, so no event value can steer a store.  For every label row
+// with events it finds, per column, the number of events at or below the chunk's first j by binary search, then walks a cursor down
+// the column; a pixel inside an odd number of events takes the row's value, later rows overwrite earlier ones.  A wave writes 256
+// consecutive bytes of a mask row (dwords when every row starts on a multiple of 4).  The running start of a row in the packed list
+// is checked against `capacity` BEFORE any of its events is read; a frame that fails is written all zero.  No atomics, no workspace.
+#define RLE_DEC_COLS 4
+#define RLE_DEC_ROWS 16
+#define RLE_DEC_WAVES 4            // wave w of a workgroup owns the rows 16 w .. 16 w + 15 of its 64
+
+__global__ __launch_bounds__(RLE_DEC_WAVES * XMEM_WAVE) void rle_decode_kernel(const int* __restrict__ meta,
+                                                                                const uint32_t* __restrict__ events, int H, int W, int K,
+                                                                                int capacity, const uint8_t* __restrict__ values,
+                                                                                int dword_ok, uint8_t* __restrict__ masks,
+                                                                                int* __restrict__ status) {
+    const int n = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x0 = (blockIdx.x * XMEM_WAVE + lane) * RLE_DEC_COLS;
+    const int y0 = (blockIdx.y * RLE_DEC_WAVES + wave) * RLE_DEC_ROWS;
+    const int* mt = meta + (size_t)n * K * XMEM_RLE_META;
+    const uint32_t* ev_frame = events + (size_t)n * capacity;
+    uint32_t px[RLE_DEC_ROWS];
+#pragma unroll
+    for (int r = 0; r < RLE_DEC_ROWS; ++r) px[r] = 0u;
+
+    int base = 0, bad = 0;
+    for (int k = 0; k < K; ++k) {                        // uniform over the grid: every thread of a frame reaches the same verdict
+        const int cnt = mt[(size_t)k * XMEM_RLE_META];
+        if (cnt == 0) continue;
+        if (cnt < 0 || cnt > capacity - base) { bad = 1; break; }
+        const uint32_t* ev = ev_frame + base;            // ev[0 .. cnt) lies below `capacity`
+        base += cnt;
+        if (x0 >= W || y0 >= H) continue;
+        const uint32_t val = values ? (uint32_t)values[k] : (uint32_t)(k + 1);
+#pragma unroll
+        for (int c = 0; c < RLE_DEC_COLS; ++c) {
+            const int x = x0 + c;
+            if (x >= W) break;
+            const uint32_t j0 = (uint32_t)x * (uint32_t)H + (uint32_t)y0;
+            int lo = 0, hi = cnt;                        // pos: the number of events <= j0
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ev[mid] <= j0) lo = mid + 1; else hi = mid;
+            }
+            int pos = lo;
+            uint32_t next = pos < cnt ? ev[pos] : 0xffffffffu;
+#pragma unroll
+            for (int r = 0; r < RLE_DEC_ROWS; ++r) {
+                const uint32_t j = j0 + (uint32_t)r;
+                while (next <= j) {                      // at most cnt - pos turns: next becomes 0xffffffff > j at the end of the list
+                    ++pos;
+                    next = pos < cnt ? ev[pos] : 0xffffffffu;
+                }
+                if (pos & 1) px[r] = (px[r] & ~(255u << (8 * c))) | (val << (8 * c));
+            }
+        }
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) status[n] = bad;
+    if (x0 >= W || y0 >= H) return;
+    uint8_t* out = masks + (size_t)n * H * W;
+#pragma unroll
+    for (int r = 0; r < RLE_DEC_ROWS; ++r) {
+        const int y = y0 + r;
+        if (y >= H) break;
+        const uint32_t v = bad ? 0u : px[r];
+        uint8_t* row = out + (size_t)y * W + x0;
+        if (dword_ok) {                                  // W % 4 == 0: the lane's 4 columns are all inside the row
+            *reinterpret_cast<uint32_t*>(row) = v;
+        } else {
+#pragma unroll
+            for (int c = 0; c < RLE_DEC_COLS; ++c)
+                if (x0 + c < W) row[c] = (uint8_t)(v >> (8 * c));
+        }
+    }
+}
+
 inline bool rle_args_ok(int N, int W, int K) { return N > 0 && W > 0 && K >= 1 && K <= 254; }
 inline bool rle_size_ok(int N, int H, int W) { return H <= RLE_MAX_HW && W <= RLE_MAX_HW && N <= 65535; }
 
@@ -214,5 +289,17 @@ extern "C" int xmem_rle_encode(const uint8_t* masks, int N, int H, int W, int K,
     rc = xmem_check_launch();
     if (rc != XMEM_OK) return rc;
     hipLaunchKernelGGL(rle_walk_kernel<true>, grid, block, 0, s, masks, H, W, K, vec_ok, ofs, (int*)meta, events, capacity);
+    return xmem_check_launch();
+}
+
+extern "C" int xmem_rle_decode(const int32_t* meta, const uint32_t* events, int N, int H, int W, int K, int capacity,
+                               const uint8_t* values, uint8_t* masks, int32_t* status, void* stream) {
+    if (!meta || !events || !masks || !status) return XMEM_ERR_BAD_ARG;
+    if (H <= 0 || capacity < 1 || !rle_args_ok(N, W, K) || !rle_size_ok(N, H, W)) return XMEM_ERR_UNSUPPORTED;
+    // dword stores need every row of every frame to start on a multiple of 4
+    const int dword_ok = (W % 4 == 0) && (((uintptr_t)masks & 3) == 0);
+    const dim3 grid(cdiv(W, XMEM_WAVE * RLE_DEC_COLS), cdiv(H, RLE_DEC_WAVES * RLE_DEC_ROWS), N), block(RLE_DEC_WAVES * XMEM_WAVE);
+    hipLaunchKernelGGL(rle_decode_kernel, grid, block, 0, (hipStream_t)stream, (const int*)meta, events, H, W, K, capacity, values,
+                       dword_ok, masks, (int*)status);
     return xmem_check_launch();
 }

@@ -169,11 +169,85 @@ def load_video(gt_dir, pred_dir, pool):
     return gts, preds
 
 
-def compute_metrics(p_source_masks, p_preds, pred_to_annot_names_lookup=None, workers=8):
+PRED_FORMATS = ('auto', 'png', 'tracks')
+TRACKS_NAME = 'tracks.json'
+
+
+def _has_files(d):
+    return os.path.isdir(d) and any(os.path.isfile(os.path.join(d, f)) for f in os.listdir(d))
+
+
+def _tracks_of(video_dir, png_dir, fmt):
+    """The tracks file one side of a video is read from, or None for its PNGs: 'tracks' forces the file, 'png' the PNGs, 'auto'
+    takes the file only where `png_dir` is absent or holds no file and `<video_dir>/tracks.json` exists."""
+    path = os.path.join(video_dir, TRACKS_NAME)
+    if fmt == 'tracks':
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f'{video_dir}: no {TRACKS_NAME}')
+        return path
+    if fmt == 'auto' and not _has_files(png_dir) and os.path.isfile(path):
+        return path
+    return None
+
+
+def _device_maps(path):
+    """Every frame of a tracks file as device label maps uint8 [T,H,W] holding the annotations' labels (`ops.rle_decode`): no pixel
+    is touched on the host.  A frame without an entry is all zero."""
+    from .rle import TrackReader
+    return TrackReader(path).masks_device(values='label')[0]
+
+
+def _gt_tracks(gt_dir):
+    """`<gt>/<video>/tracks.json` when the directory holds no other file (no PNG), else None."""
+    path = os.path.join(gt_dir, TRACKS_NAME)
+    if os.path.isfile(path) and not any(f != TRACKS_NAME and os.path.isfile(os.path.join(gt_dir, f)) for f in os.listdir(gt_dir)):
+        return path
+    return None
+
+
+def load_video_tracks(name, gt_dir, gt_tracks, pred_dir, pred_tracks, pool):
+    """(gts, preds) of one video with at least one side read from tracks.json.  Frames pair in order; the tracks' size must be the
+    ground truth's (tracks are not resampled) and both sides must have one entry per frame: ValueError naming the video otherwise."""
+    import torch
+    if gt_tracks is not None:
+        gts = _device_maps(gt_tracks)
+    else:
+        gt_files = _sorted_files(gt_dir)
+        if not gt_files:
+            raise ValueError(f'{gt_dir}: no ground-truth masks')
+        gts = np.stack(list(pool.map(_load_gt, gt_files)))
+    if pred_tracks is not None:
+        preds = _device_maps(pred_tracks)
+    else:                                                            # PNG predictions against ground truth from tracks: no palette
+        pred_files = _sorted_files(pred_dir)                         # to quantise to, the index plane is taken as it is
+        if len(pred_files) != gts.shape[0]:
+            raise ValueError(f'video {name}: {len(pred_files)} predicted masks for {gts.shape[0]} ground-truth frames')
+        preds = np.stack(list(pool.map(_load_gt, pred_files))) if pred_files else np.zeros((0,) + tuple(gts.shape[1:]), np.uint8)
+    if preds.shape[0] != gts.shape[0]:
+        raise ValueError(f'video {name}: {preds.shape[0]} predicted frames for {gts.shape[0]} ground-truth frames')
+    if gts.shape[0] == 0:
+        raise ValueError(f'video {name}: no ground-truth masks')
+    if tuple(preds.shape[1:]) != tuple(gts.shape[1:]):
+        raise ValueError(f'video {name}: predictions are {tuple(preds.shape[1:])}, the ground truth is {tuple(gts.shape[1:])} '
+                         '(tracks are not resampled)')
+    if isinstance(gts, torch.Tensor) != isinstance(preds, torch.Tensor):      # `jf` takes a pair on one side
+        dev = gts.device if isinstance(gts, torch.Tensor) else preds.device
+        gts = gts if isinstance(gts, torch.Tensor) else torch.from_numpy(gts).to(dev)
+        preds = preds if isinstance(preds, torch.Tensor) else torch.from_numpy(preds).to(dev)
+    return gts, preds
+
+
+def compute_metrics(p_source_masks, p_preds, pred_to_annot_names_lookup=None, workers=8, pred_format='auto'):
     """Per-video mean J ('iou') and F ('f') of the predictions under `p_preds/<video>/masks/` against `p_source_masks/<video>/`
     (run_experiments.py:376-410), plus 'jf' = (iou + f) / 2.  DataFrame indexed by video_name, rows sorted by it.  PNG decoding runs
-    on `workers` host threads; each video is scored in one or a few kernel launches."""
+    on `workers` host threads; each video is scored in one or a few kernel launches.
+    `pred_format`: 'auto' reads the PNGs wherever `masks/` holds a file and `p_preds/<video>/tracks.json` (config['save_tracks'])
+    where it is absent or empty; 'png' / 'tracks' force one source.  Tracks are decoded on the device and scored there - no
+    prediction pixel reaches the host, no image is opened for them.  The ground truth of a video may come from
+    `p_source_masks/<video>/tracks.json` in the same way when the directory holds no other file."""
     import pandas as pd
+    if pred_format not in PRED_FORMATS:
+        raise ValueError(f'pred_format must be one of {PRED_FORMATS}, got {pred_format!r}')
     p_source_masks, p_preds = str(p_source_masks), str(p_preds)
     rows = []
     with ThreadPoolExecutor(max_workers=max(1, int(workers)), thread_name_prefix='xmem-metrics') as pool:
@@ -182,7 +256,13 @@ def compute_metrics(p_source_masks, p_preds, pred_to_annot_names_lookup=None, wo
             if not os.path.isdir(pred_video):
                 continue
             name = pred_to_annot_names_lookup[entry] if pred_to_annot_names_lookup is not None else entry
-            gts, preds = load_video(os.path.join(p_source_masks, name), os.path.join(pred_video, 'masks'), pool)
+            gt_dir, pred_dir = os.path.join(p_source_masks, name), os.path.join(pred_video, 'masks')
+            pred_tracks = _tracks_of(pred_video, pred_dir, pred_format)
+            gt_tracks = _gt_tracks(gt_dir)
+            if pred_tracks is None and gt_tracks is None:
+                gts, preds = load_video(gt_dir, pred_dir, pool)
+            else:
+                gts, preds = load_video_tracks(name, gt_dir, gt_tracks, pred_dir, pred_tracks, pool)
             J, F = jf(gts, preds)
             rows.append({'video_name': name, 'iou': float(J.mean(axis=0)), 'f': float(F.mean(axis=0))})
     if not rows:

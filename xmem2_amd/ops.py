@@ -1340,6 +1340,79 @@ def rle_encode(masks, K, capacity=None, wait=True):
     return meta.copy(), out
 
 
+def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True):
+    """The inverse of `rle_encode`: uint8 label maps [B,H,W] on the device from a record.  `record`: the int32 device tensor
+    `rle_encode(..., wait=False)` returns (B follows from its length; `capacity` is the one it was encoded with; no host step), or a
+    host pair (meta [B,K,>=1] whose field 0 is the rows' event counts, list of B packed event arrays) as wait=True returns, which is
+    packed and uploaded - with the capacity the frames need unless `capacity` says otherwise (events beyond it are cut, as the
+    encoder does not write them).  A pixel gets values[k - 1] (default k) of the highest row that contains it, else 0.
+    check=True reads the per-frame status (one synchronisation) and raises for a frame whose counts exceed the capacity;
+    check=False returns (masks, status int32 [B] on the device) without synchronising: such a frame is all zero, status 1."""
+    import numpy as np
+    from . import rle
+    for name, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (1 <= v <= top):
+            raise ValueError(f'rle_decode: {name} = {v!r} must be an integer in 1..{top}')
+    H, W, K = int(H), int(W), int(K)
+    if capacity is not None:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 1:
+            raise ValueError(f'rle_decode: capacity = {capacity!r} must be an integer of at least 1')
+        capacity = int(capacity)
+    if torch.is_tensor(record):
+        if not record.is_cuda or record.dtype != torch.int32 or record.dim() != 1 or not record.is_contiguous():
+            raise RuntimeError('record: expected the contiguous int32 CUDA (HIP) tensor of rle_encode(wait=False) - xmem2_amd has no CPU path')
+        if capacity is None:
+            raise ValueError('rle_decode: a device record needs the capacity it was encoded with')
+        per_frame = K * rle.META + capacity
+        B = record.numel() // per_frame
+        if B < 1 or B * per_frame != record.numel():
+            raise ValueError(f'rle_decode: a record of {record.numel()} words is not a whole number of frames of K = {K}, capacity = {capacity}')
+        device = record.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError('rle_decode: needs an MI355X (HIP) device - xmem2_amd has no CPU path')
+        meta, events = record
+        meta = np.asarray(meta)
+        if meta.ndim != 3 or meta.shape[0] < 1 or meta.shape[1] != K or meta.shape[2] < 1 or len(events) != meta.shape[0]:
+            raise ValueError(f'rle_decode: expected (meta [B, {K}, >= 1], B event arrays), got meta {meta.shape} and {len(events)} arrays')
+        B = meta.shape[0]
+        events = [np.asarray(e).reshape(-1) for e in events]
+        if capacity is None:
+            capacity = max(1, max(len(e) for e in events))
+        buf = np.zeros(B * K * rle.META + B * capacity, np.int32)
+        m, ev = rle.split_record(buf, B, K, capacity)
+        m[:, :, 0] = meta[:, :, 0]
+        for b, e in enumerate(events):
+            n = min(len(e), capacity)
+            ev[b, :n] = e[:n]
+        device = values.device if torch.is_tensor(values) and values.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        record = torch.from_numpy(buf).to(device)
+    if B > 65535:
+        raise ValueError(f'rle_decode: {B} frames in one launch, at most 65535')
+    if values is not None:
+        if not torch.is_tensor(values):
+            v = np.asarray(values)
+            if v.shape != (K,) or v.dtype.kind not in 'iu' or (v.size and (v.min() < 0 or v.max() > 255)):
+                raise ValueError(f'rle_decode: values must be {K} integers in 0..255')
+            values = torch.from_numpy(v.astype(np.uint8))
+        if values.dtype != torch.uint8 or tuple(values.shape) != (K,):
+            raise ValueError(f'rle_decode: values must be uint8 [{K}]')
+        values = values.to(device).contiguous()
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.uint8, device=device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W) or not out.is_contiguous():
+        raise RuntimeError(f'rle_decode: out must be a contiguous uint8 CUDA (HIP) tensor {(B, H, W)}')
+    status = torch.empty(B, dtype=torch.int32, device=device)
+    _lib.check(load().xmem_rle_decode(ptr(record), C.c_void_p(record.data_ptr() + 4 * B * K * rle.META), B, H, W, K, capacity,
+                                      ptr(values) if values is not None else None, ptr(out), ptr(status), stream_ptr()))
+    if not check:
+        return out, status
+    bad = torch.nonzero(status).reshape(-1).tolist()
+    if bad:
+        raise RuntimeError(f'rle_decode: the events of frame(s) {bad} do not fit the capacity {capacity}')
+    return out
+
+
 # ---- f-BRS click refinement (csrc/brs.hip): every kernel bit-reproducible --------------------------------------------
 
 BRS_RECORD = 8          # floats of the evaluation record ahead of the gradient (include/xmem_hip.h, xmem_brs_loss)

@@ -19,7 +19,9 @@ event, never per pixel.  `TrackWriter` collects one video's frames into the YouT
 
 `counts` is the uncompressed list form, which COCO tools accept; the compressed string form is not built.  A frame in which a label
 has no pixel, or which has no mask at all, carries null in all three lists.  `python -m xmem2_amd.rle --tracks F --out DIR` is the way
-back: tracks to index PNGs.
+back to index PNGs; `TrackReader` is the way back without them: counts to events per event (`events_from_counts`), events to label maps
+on the device (`ops.rle_decode`) - for scoring (`metrics.compute_metrics`), as annotations (`run_on_video.VideoReader`) and for
+`VideoSession.load_tracks`.
 """
 import argparse
 import collections
@@ -65,6 +67,15 @@ def encode_host(mask, k):
     else:
         box = EMPTY_BOX
     return HostRle(events, counts_from_events(events, h, w), area, box)
+
+
+def events_from_counts(counts, h, w):
+    """Uncompressed COCO counts of one label -> its ascending event positions (uint32), the inverse of `counts_from_events`; refuses
+    what `decode` refuses.  A cumulative sum: work per event."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if counts.size == 0 or (counts < 0).any() or (counts[1:] == 0).any() or int(counts.sum()) != int(h) * int(w):
+        raise ValueError(f'events_from_counts: counts do not describe a {h} x {w} plane')
+    return np.cumsum(counts[:-1]).astype(np.uint32)                  # the last count ends at h * w, which is no event
 
 
 def decode(counts, h, w):
@@ -200,6 +211,118 @@ def read_tracks(path):
                 masks[t] = np.zeros((h, w), np.uint8)
             masks[t][decode(seg['counts'], h, w)] = lab
     return video, masks
+
+
+class TrackReader:
+    """One video's tracks.json, parsed once (`path_or_doc`: the file, or the parsed document) with `read_tracks`'s validation.  The
+    annotations are the label rows of a record in file order, so a later annotation wins where tracks overlap, as in `read_tracks`.
+    `mask_host(t)` decodes a frame on the host (few frames: annotations); `masks_device` builds packed records from the counts - work
+    per event, never per pixel - and decodes them with `ops.rle_decode`."""
+
+    def __init__(self, path_or_doc):
+        if isinstance(path_or_doc, dict):
+            doc = path_or_doc
+        else:
+            with open(path_or_doc) as f:
+                doc = json.load(f)
+        if len(doc.get('videos', [])) != 1:
+            raise ValueError('read_tracks: expected one video per file')
+        self.video = doc['videos'][0]
+        self.height, self.width, self.length = int(self.video['height']), int(self.video['width']), int(self.video['length'])
+        self.file_names = [str(n) for n in self.video.get('file_names', [])]
+        h, w, T = self.height, self.width, self.length
+        self.labels, self._segs = [], []                             # per annotation: its label, {frame index: counts}
+        for ann in doc['annotations']:
+            lab = int(ann['label'])
+            if not (1 <= lab <= 255):
+                raise ValueError(f'read_tracks: label {lab} does not fit an index PNG')
+            if not (len(ann['segmentations']) == len(ann['bboxes']) == len(ann['areas']) == T):
+                raise ValueError(f'read_tracks: track {ann["id"]} does not have one entry per frame')
+            segs = {}
+            for t, seg in enumerate(ann['segmentations']):
+                if seg is None:
+                    continue
+                if list(seg['size']) != [h, w]:
+                    raise ValueError(f'read_tracks: track {ann["id"]}, frame {t}: size {seg["size"]} is not the video\'s {[h, w]}')
+                segs[t] = seg['counts']
+            self.labels.append(lab)
+            self._segs.append(segs)
+        self._index = {}
+        for t, name in enumerate(self.file_names):
+            self._index.setdefault(os.path.splitext(name)[0], t)
+        self._events = {}                                            # (annotation, frame) -> validated events
+
+    def __len__(self):
+        return self.length
+
+    def _frame(self, t):
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not (0 <= t < self.length):
+            raise IndexError(f'frame {t!r} is not a frame of these tracks (0..{self.length - 1})')
+        return int(t)
+
+    def has_mask(self, t):
+        """True when any track has an entry for frame t."""
+        t = self._frame(t)
+        return any(t in segs for segs in self._segs)
+
+    def frame_index(self, name_or_stem):
+        """The index of the frame whose file name, or file name without extension, is given; None when there is none."""
+        name = str(name_or_stem)
+        if name in self.file_names:
+            return self.file_names.index(name)
+        return self._index.get(name, self._index.get(os.path.splitext(name)[0]))
+
+    def mask_host(self, t):
+        """uint8 [H, W] holding the annotations' labels, as `read_tracks` gives it; None for a frame without any entry."""
+        t = self._frame(t)
+        mask = None
+        for lab, segs in zip(self.labels, self._segs):
+            if t in segs:
+                if mask is None:
+                    mask = np.zeros((self.height, self.width), np.uint8)
+                mask[decode(segs[t], self.height, self.width)] = lab
+        return mask
+
+    def record(self, t):
+        """(meta int32 [n, META], packed uint32 events) of frame t with one row per annotation, in the layout `ops.rle_encode`
+        writes; of `meta` only field 0, the number of events, is filled."""
+        t = self._frame(t)
+        meta = np.zeros((len(self.labels), META), np.int32)
+        ev = []
+        for a, segs in enumerate(self._segs):
+            if t in segs:
+                if (a, t) not in self._events:
+                    self._events[(a, t)] = events_from_counts(segs[t], self.height, self.width)
+                ev.append(self._events[(a, t)])
+                meta[a, 0] = len(ev[-1])
+        return meta, np.concatenate(ev) if ev else np.zeros(0, np.uint32)
+
+    def masks_device(self, frames=None, device=None, values='label', batch=32):
+        """(uint8 [n, H, W] on the device, present bool [n]) of `frames` (default: all), decoded in launches of `batch` frames.
+        values='label': the annotations' labels; 'dense': 1..n in file order.  A frame without any entry is all zero, not present."""
+        import torch
+        from . import ops
+        if values not in ('label', 'dense'):
+            raise ValueError(f"values must be 'label' or 'dense', got {values!r}")
+        frames = list(range(self.length)) if frames is None else [self._frame(t) for t in frames]
+        n_rows = len(self.labels)
+        if n_rows > 254:
+            raise ValueError(f'masks_device: {n_rows} tracks, at most 254 fit a launch')
+        if not torch.cuda.is_available():
+            raise RuntimeError('TrackReader.masks_device needs an MI355X (HIP) device - there is no CPU path')
+        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        present = np.array([self.has_mask(t) for t in frames], bool)
+        out = torch.zeros((len(frames), self.height, self.width), dtype=torch.uint8, device=device)
+        if n_rows == 0 or not frames:
+            return out, present
+        table = torch.tensor(self.labels, dtype=torch.uint8, device=device) if values == 'label' else None
+        step = max(1, int(batch))
+        with torch.cuda.device(device):
+            for i in range(0, len(frames), step):
+                records = [self.record(t) for t in frames[i:i + step]]
+                ops.rle_decode((np.stack([m for m, _ in records]), [e for _, e in records]), self.height, self.width, n_rows,
+                               values=table, out=out[i:i + len(records)])
+        return out, present
 
 
 def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):

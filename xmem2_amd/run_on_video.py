@@ -68,7 +68,12 @@ class Sample:
 
 
 class VideoReader:
-    """Directory-of-frames reader (inference/data/video_reader.py:31-118 without cv2 / torchvision)."""
+    """Directory-of-frames reader (inference/data/video_reader.py:31-118 without cv2 / torchvision).
+    `mask_dir` may name a tracks file (xmem2_amd/rle.py) instead of a directory of palette PNGs, or a directory that holds no PNG
+    but a tracks.json: frames then match the file's `file_names` by stem, a frame's mask is `TrackReader.mask_host`, the first mask
+    is the first frame with an entry, and - tracks carry no palette - the written PNGs take the DAVIS palette, so that their indices
+    are the tracks' labels."""
+    tracks = None                                   # the TrackReader when the annotations come from a tracks file
 
     def __init__(self, vid_name, video_path, mask_dir, size=-1, use_all_masks=False, resize_on_device=False):
         from PIL import Image
@@ -79,7 +84,20 @@ class VideoReader:
         self.vid_name, self.image_dir, self.mask_dir = vid_name, video_path, mask_dir
         self.size, self.use_all_masks = size, use_all_masks
         self.frames = sorted(os.listdir(self.image_dir))
-        masks = sorted(os.listdir(mask_dir))
+        tracks_path = mask_dir if os.path.isfile(mask_dir) else None
+        if tracks_path is None:
+            masks = sorted(os.listdir(mask_dir))
+            if 'tracks.json' in masks and not any(m.endswith(('.png', '.PNG')) for m in masks):
+                tracks_path = os.path.join(mask_dir, 'tracks.json')
+        if tracks_path is not None:
+            from .rle import TrackReader
+            from .scribble import _palette
+            self.tracks = TrackReader(tracks_path)
+            self.first_gt_path = None
+            self._first_track_frame = next((t for t in range(len(self.tracks)) if self.tracks.has_mask(t)), None)
+            self.reference_mask = Image.new('P', (1, 1))
+            self.reference_mask.putpalette(_palette())
+            return
         self.first_gt_path = os.path.join(mask_dir, masks[0])
         self.reference_mask = Image.open(self.first_gt_path).convert('P')
         self.reference_mask.load()                   # decoded once here: the writer threads only read it afterwards
@@ -117,12 +135,17 @@ class VideoReader:
             src_u8, target_hw = self.frame_src_u8(img)
         else:
             rgb_u8 = self.frame_u8(img)
-        gt_path = os.path.join(self.mask_dir, name[:-4] + '.png')
-        if not os.path.exists(gt_path):
-            gt_path = os.path.join(self.mask_dir, name[:-4] + '.PNG')
         mask = None
-        if (self.use_all_masks or gt_path == self.first_gt_path) and os.path.exists(gt_path):
-            mask = np.array(Image.open(gt_path).convert('P'), dtype=np.uint8)
+        if self.tracks is not None:
+            t = self.tracks.frame_index(name[:-4])
+            if t is not None and (self.use_all_masks or t == self._first_track_frame):
+                mask = self.tracks.mask_host(t)
+        else:
+            gt_path = os.path.join(self.mask_dir, name[:-4] + '.png')
+            if not os.path.exists(gt_path):
+                gt_path = os.path.join(self.mask_dir, name[:-4] + '.PNG')
+            if (self.use_all_masks or gt_path == self.first_gt_path) and os.path.exists(gt_path):
+                mask = np.array(Image.open(gt_path).convert('P'), dtype=np.uint8)
         return Sample(rgb_u8=rgb_u8, raw_image_pil=img, frame=name, save=True, shape=shape,
                       need_resize=not (self.size < 0), mask=mask, src_u8=src_u8, target_hw=target_hw)
 

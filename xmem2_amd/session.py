@@ -192,8 +192,8 @@ class VideoSession:
         from .run_on_video import _make_network, _working_u8
         if not os.path.isdir(imgs_in_path):
             raise NotADirectoryError(f'imgs_in_path: {imgs_in_path!r} is not a directory of frames')
-        if masks_in_path is not None and not os.path.isdir(masks_in_path):
-            raise NotADirectoryError(f'masks_in_path: {masks_in_path!r} is not a directory')
+        if masks_in_path is not None and not os.path.isdir(masks_in_path) and not os.path.isfile(masks_in_path):
+            raise NotADirectoryError(f'masks_in_path: {masks_in_path!r} is not a directory')      # a file: tracks (xmem2_amd/rle.py)
         if overwrite_config is not None and not isinstance(overwrite_config, dict):
             raise TypeError('overwrite_config must be a dict (or None)')
         if not torch.cuda.is_available():
@@ -523,6 +523,42 @@ class VideoSession:
             writer.add_frame(fr.frame, *encoded.get(t, (None, None)), labels=labels)
         return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
 
+    def load_tracks(self, path, batch=32):
+        """The inverse of `save_tracks`: the frames of tracks.json (`path`: the file, or the directory that holds it) that have an
+        entry are decoded on the device, in launches of `batch` frames, into the resident `masks` with dense ids and marked present;
+        labels the mapper has not seen are registered as an annotation registers them.  Returns the frames' indices.  Keys are not
+        restored (what needs a key pass keeps needing it) and the references are not touched.  ValueError when the file's size or
+        `file_names` are not the session's; nothing has been changed then."""
+        from .rle import TrackReader
+        path = str(path)
+        reader = TrackReader(os.path.join(path, 'tracks.json') if os.path.isdir(path) else path)
+        if (reader.height, reader.width) != tuple(self.shape):
+            raise ValueError(f'load_tracks: the tracks are {(reader.height, reader.width)}, the video is {tuple(self.shape)}')
+        names = [fr.frame for fr in self.frames]
+        if reader.length != len(names) or reader.file_names != names:
+            raise ValueError(f'load_tracks: the file_names of {path!r} are not the {len(names)} frames of this video')
+        if len(reader.labels) > 254:
+            raise ValueError(f'load_tracks: {len(reader.labels)} tracks, at most 254 fit a launch')
+        present = [t for t in range(len(names)) if reader.has_mask(t)]
+        if not present:
+            return present
+        for lab in reader.labels:                                        # in file order, which is `save_tracks`'s dense order: a new
+            self.mapper.convert_mask(np.array([[lab]], np.uint8), exhaustive=True)      # label gets the next dense id, as annotated
+        dense = torch.tensor([self.mapper.remappings[lab] for lab in reader.labels], dtype=torch.uint8, device=self.device)
+        step = max(1, int(batch))
+        with torch.cuda.device(self.device):
+            for i in range(0, len(present), step):
+                chunk = present[i:i + step]
+                records = [reader.record(t) for t in chunk]
+                record = (np.stack([m for m, _ in records]), [e for _, e in records])
+                if chunk == list(range(chunk[0], chunk[-1] + 1)):                  # straight into the arena
+                    ops.rle_decode(record, *self.shape, len(reader.labels), values=dense, out=self.masks[chunk[0]:chunk[-1] + 1])
+                else:
+                    self.masks[torch.tensor(chunk, device=self.device)] = ops.rle_decode(record, *self.shape, len(reader.labels), values=dense)
+        for t in present:
+            self._present[t] = True
+        return present
+
     def stats(self, compute_iou=False, compute_jf=False):
         """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
         import pandas as pd
@@ -552,7 +588,7 @@ def _session_reader(imgs_in_path, masks_in_path, size, resize_on_device):
     the written masks are mapped to a grey ramp instead of the first annotation's palette."""
     from PIL import Image
     from .run_on_video import VideoReader
-    if masks_in_path is not None and len(os.listdir(masks_in_path)) > 0:
+    if masks_in_path is not None and (os.path.isfile(masks_in_path) or len(os.listdir(masks_in_path)) > 0):
         return VideoReader('', imgs_in_path, masks_in_path, size=size, use_all_masks=True, resize_on_device=resize_on_device)
     r = VideoReader.__new__(VideoReader)
     r.resize_on_device, r._Image = bool(resize_on_device), Image
@@ -573,7 +609,7 @@ def parse_args(argv=None):
                                              'references so far, lets the selector propose the next frames and takes their annotations '
                                              'from --masks (run_experiments.py).')
     ap.add_argument('--images', required=True, help='directory of frames')
-    ap.add_argument('--masks', required=True, help='directory of annotations (palette PNGs named like the frames)')
+    ap.add_argument('--masks', required=True, help='directory of annotations (palette PNGs named like the frames), or a tracks.json (xmem2_amd/rle.py)')
     ap.add_argument('--out', required=True, help='the masks of the last round are written to <out>/masks')
     ap.add_argument('--rounds', type=int, default=1)
     ap.add_argument('--k', type=int, default=5, help='frames the selector proposes per round')
