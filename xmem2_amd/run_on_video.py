@@ -11,6 +11,10 @@ What is reproduced from the reference: config merge and the derived ``enable_lon
 ``step`` call and its flags (:98-108), resize + argmax post-processing (:165-173, on the GPU), the stats rows
 (:115-123) and the output layout ``<out>/masks/<frame>.png`` (+ ``overlay/<frame>.jpg``).
 Not reproduced: mp4 extraction (needs cv2).  `augment_images_with_masks` uses xmem2_amd/augmentations.py (unpinned restatement).
+
+There is one frame loop, `_run_frame_loop`: `hinted` decides which frames are hinted when, `_FrameOutputs` is the whole output side
+(scorer, tracks, mask copy one frame behind, stats rows, saver jobs).  `run_on_video` and `run_on_video_ensemble` are a preload and
+three callbacks each (hint / prepare / frame); `VideoSession` shares `hinted`, `_stats_row` and `_saver_job`.
 """
 import collections
 import os
@@ -296,13 +300,6 @@ def _post_process_gpu(sample, prob):
     return ops.argmax_u8(prob)
 
 
-def _post_process(sample, prob):
-    """run_on_video.py:165-173: resize to the original shape if needed, argmax over classes, uint8 on the host."""
-    if sample.need_resize and tuple(prob.shape[-2:]) != tuple(sample.shape):
-        prob = ops.resize_bilinear(prob, sample.shape)
-    return ops.argmax_u8(prob).cpu().numpy()
-
-
 class _TrackLoop:
     """config['save_tracks'] inside a frame loop: one `ops.rle_encode` launch sequence per frame on the compute stream, the record
     delivered through pinned memory one frame behind like the mask (its own AsyncMaskFetcher, fed right before the mask's: when the
@@ -378,16 +375,154 @@ def _make_network(config, device, network=None):
     return network
 
 
-def _load_main_objects(imgs_in_path, masks_in_path, config, device, network=None):
-    network = _make_network(config, device, network)
-    vid_reader = VideoReader('', imgs_in_path, masks_in_path, size=config['size'], use_all_masks=True,
-                             resize_on_device=config.get('resize_on_device', False))
-    vid_length = len(vid_reader)
+def _merged_config(overwrite_config, masks_out_path):
+    """VIDEO_INFERENCE_CONFIG with the call's overrides; `masks_out_path` is written into the given dict too."""
+    config = VIDEO_INFERENCE_CONFIG.copy()
+    overwrite_config['masks_out_path'] = masks_out_path
+    config.update(overwrite_config)
+    return config
+
+
+def _inference_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError('xmem2_amd.run_on_video needs an MI355X (HIP) device - there is no CPU path')
+    torch.autograd.set_grad_enabled(False)
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _set_long_term_count_usage(config, vid_length):
     config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196
         config['enable_long_term'] and
         (vid_length / (config['max_mid_term_frames'] - config['min_mid_term_frames']) * config['num_prototypes'])
         >= config['max_long_term_elements'])
+
+
+def _load_main_objects(imgs_in_path, masks_in_path, config, device, network=None):
+    network = _make_network(config, device, network)
+    vid_reader = VideoReader('', imgs_in_path, masks_in_path, size=config['size'], use_all_masks=True,
+                             resize_on_device=config.get('resize_on_device', False))
+    _set_long_term_count_usage(config, len(vid_reader))
     return MaskMapper(), InferenceCore(network, config=config), vid_reader
+
+
+def hinted(order, key_batch, prefetch):
+    """Yield (frame index, what `prefetch` returned for it) over `order`, hinting the key encoder ahead of the frame loop: whenever
+    fewer than `key_batch` hinted frames are pending, the next `key_batch` frames IN THE DIRECTION OF TRAVEL go to
+    `prefetch(list of indices) -> list` as one batch; a tail shorter than a batch goes frame by frame (no new graph shapes)."""
+    key_batch = max(1, int(key_batch))
+    pending, nxt = collections.deque(), 0
+    for _ in order:
+        if len(pending) < key_batch and nxt < len(order):
+            remaining = len(order) - nxt
+            n = key_batch if remaining >= key_batch else 1
+            batch = list(order[nxt:nxt + n])
+            pending.extend(zip(batch, prefetch(batch)))
+            nxt += n
+        yield pending.popleft()
+
+
+def _stats_row(frame, had_mask, compute_iou, out_mask=None, gt=None):
+    """One row of the returned DataFrame (run_on_video.py:115-123)."""
+    stat = {'frame': frame, 'mask_provided': had_mask}
+    if compute_iou:
+        stat['iou'] = float(compute_array_iou(out_mask, gt)) if (gt is not None and not had_mask) else -1
+    return stat
+
+
+def _saver_job(reader, ids, frame, overlay_image=None):
+    """The _AsyncSaver job that colour-maps the index mask `ids` and yields <frame>.png and, when `overlay_image() -> PIL image` is
+    given, the overlay <frame>.jpg on it."""
+    def job():
+        from PIL import Image
+        out_img = reader.map_the_colors_back(Image.fromarray(ids))
+        yield out_img, 'masks', frame[:-4] + '.png'
+        if overlay_image is not None:
+            yield _overlay(overlay_image(), out_img), 'overlay', frame[:-4] + '.jpg'
+    return job
+
+
+class _FrameOutputs:
+    """Everything a frame loop does with a frame's index mask once it is on the device: J&F scoring, the track record, the copy to the
+    host one frame behind, and - when a frame has arrived - its stats row and its saver job.  `submit` and `drain` enqueue and wait
+    (the caller times them); `deliver` is the host side of whatever arrived.  With tracks only, no mask travels: a frame is delivered
+    with its record.  `reused_output`: the caller rewrites `out_dev` next frame, so the track loop, which may encode a frame again when
+    its record arrives, gets a copy."""
+
+    def __init__(self, reader, mapper, fetcher, saver=None, tracks=None, scorer=None, compute_iou=False, save_overlay=True,
+                 masks_out_path=None, reused_output=False):
+        self.reader, self.mapper, self.fetcher, self.saver, self.tracks, self.scorer = reader, mapper, fetcher, saver, tracks, scorer
+        self.compute_iou, self.save_overlay, self.masks_out_path, self.reused_output = compute_iou, save_overlay, masks_out_path, reused_output
+        # the H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou
+        self.need_mask = tracks is None or saver is not None or compute_iou
+        self.stats = []
+        self._arrived = ((), ())
+
+    @staticmethod
+    def _tags(tdone):
+        """tracks only: the frames whose record arrived stand in for the masks that were never copied"""
+        return [(it[0][0], None) for it in tdone]
+
+    def submit(self, ti, sample, had_mask, out_dev):
+        if self.scorer is not None and sample.mask is not None:
+            self.scorer.add(ti, sample.mask, out_dev, self.mapper)
+        tag = (sample, had_mask)
+        tdone = self.tracks.submit(tag, out_dev.clone() if self.reused_output else out_dev, len(self.mapper.labels)) \
+            if self.tracks is not None else ()
+        self._arrived = tdone, (self.fetcher.submit(tag, out_dev) if self.need_mask else self._tags(tdone))
+
+    def drain(self):
+        tdone = self.tracks.drain() if self.tracks is not None else ()
+        self._arrived = tdone, (self.fetcher.drain() if self.need_mask else self._tags(tdone))
+
+    def deliver(self, last=False):
+        tdone, done = self._arrived
+        self._arrived = ((), ())
+        for item in tdone:
+            self.tracks.finish(item, item[0][0][0].frame, self.mapper)
+        for (sample, had_mask), out_mask in done:
+            self.stats.append(_stats_row(sample.frame, had_mask, self.compute_iou, out_mask, sample.mask))
+            if self.saver is not None:
+                ids = self.mapper.remap_index_mask(out_mask)         # label LUT as of this frame (cheap); the rest is off-thread
+                self.saver.submit(_saver_job(self.reader, ids, sample.frame,
+                                             (lambda s=sample: s.raw_image_pil) if self.save_overlay else None))
+        if last and self.tracks is not None:
+            self.tracks.write(self.masks_out_path)
+
+    def close(self):
+        if self.saver is not None:
+            self.saver.close()                                       # re-raises a writer's error
+
+
+def _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame):
+    """The frame loop of run_on_video and of the ensemble.  Frames come from `decoder` (a FramePrefetcher: the DataLoader role, outside
+    the timed region, run_on_video.py:80-113) and are hinted `key_batch` ahead: `hint(samples) -> one device input per sample`.
+    Per frame, `prepare(ti, sample)` is the untimed host side of an annotation (the reference converts the mask before it starts the
+    clock, :94-105) and `frame(ti, sample, inputs, prepared) -> (had_mask, out_dev)` the timed step; the clock covers `frame` and
+    `outputs.submit` - which includes the wait for the earlier frame's copy - and the final drain, nothing else.
+    -> (total_time, loop_wall, total_wall)."""
+    def prefetch(batch):
+        samples = decoder.get(len(batch))
+        return zip(samples, hint(samples))
+
+    total_time, loop_t0 = 0.0, perf_counter()
+    try:
+        for ti, (sample, inputs) in hinted(range(vid_length), key_batch, prefetch):
+            prepared = prepare(ti, sample)
+            a = perf_counter()
+            had_mask, out_dev = frame(ti, sample, inputs, prepared)
+            outputs.submit(ti, sample, had_mask, out_dev)
+            total_time += perf_counter() - a
+            outputs.deliver()
+        a = perf_counter()
+        outputs.drain()
+        total_time += perf_counter() - a
+        outputs.deliver(last=True)
+    finally:
+        decoder.close()
+        loop_wall = perf_counter() - loop_t0
+        outputs.close()
+        total_wall = perf_counter() - loop_t0
+    return total_time, loop_wall, total_wall
 
 
 def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out_path, original_memory_mechanism=False,
@@ -396,16 +531,9 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
                         object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
                         compute_jf=False, network=None):
     import pandas as pd
-    from PIL import Image
-    if not torch.cuda.is_available():
-        raise RuntimeError('xmem2_amd.run_on_video needs an MI355X (HIP) device - there is no CPU path')
-    device = torch.device('cuda', torch.cuda.current_device())
-    torch.autograd.set_grad_enabled(False)
+    device = _inference_device()
     frames_with_masks = set(frames_with_masks)
-    config = VIDEO_INFERENCE_CONFIG.copy()
-    overwrite_config = {} if overwrite_config is None else overwrite_config
-    overwrite_config['masks_out_path'] = masks_out_path
-    config.update(overwrite_config)
+    config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
@@ -457,94 +585,38 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     if not loaded:
         raise ValueError('No valid masks provided!')
 
-    stats, total_time = [], 0.0
-    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
-    fetcher = AsyncMaskFetcher()
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
-    # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).  The
-    # H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou.
-    tracks = _TrackLoop() if config.get('save_tracks', False) else None
-    need_mask = tracks is None or saver is not None or compute_iou
+    # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).
+    outputs = _FrameOutputs(
+        vid_reader, mapper, AsyncMaskFetcher(),
+        saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
+        tracks=_TrackLoop() if config.get('save_tracks', False) else None, scorer=scorer, compute_iou=compute_iou,
+        save_overlay=save_overlay, masks_out_path=config['masks_out_path'])
 
-    def finish(tag, out_mask):                                       # host side of a frame whose mask has arrived
-        sample, had_mask = tag
-        stat = {'frame': sample.frame, 'mask_provided': had_mask}
-        if compute_iou:
-            gt = sample.mask
-            stat['iou'] = float(compute_array_iou(out_mask, gt)) if (gt is not None and not had_mask) else -1
-        stats.append(stat)
-        if saver is not None:
-            ids = mapper.remap_index_mask(out_mask)                  # label LUT as of this frame (cheap); the rest is off-thread
+    def hint(samples):
+        if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
+            return processor.prefetch_keys([smp.src_u8 for smp in samples], working_size=samples[0].target_hw)
+        return processor.prefetch_keys([smp.rgb_u8 for smp in samples])      # uint8 H2D + normalise + key encoder, side stream
 
-            def job(ids=ids, sample=sample):
-                out_img = vid_reader.map_the_colors_back(Image.fromarray(ids))
-                yield out_img, 'masks', sample.frame[:-4] + '.png'
-                if save_overlay:
-                    yield _overlay(sample.raw_image_pil, out_img), 'overlay', sample.frame[:-4] + '.jpg'
-            saver.submit(job)
+    def prepare(ti, sample):
+        if ti not in frames_with_masks or sample.mask is None:
+            return None
+        msk, labels = mapper.convert_mask(sample.mask, exhaustive=True)
+        if sample.need_resize:
+            msk = vid_reader.resize_mask(msk)
+        processor.set_all_labels(list(mapper.remappings.values()))
+        return msk.to(device), labels
+
+    def frame(ti, sample, rgb, given):
+        msk, labels = given or (None, None)
+        skip_add = (ti == 0) if original_memory_mechanism else (msk is not None)
+        prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
+                              manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
+        return msk is not None, _post_process_gpu(sample, prob)
 
     key_batch = max(1, int(config.get('key_batch', 4)))                # frames per batched key-encoder hint
     decoder = FramePrefetcher(vid_reader, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
-    pending, next_idx = collections.deque(), 0                       # decoded + hinted frames, in frame order
-
-    def refill():
-        nonlocal next_idx
-        remaining = vid_length - next_idx
-        if remaining <= 0:
-            return
-        n = key_batch if remaining >= key_batch else 1               # the tail goes frame by frame (no new graph shapes)
-        samples = decoder.get(n)
-        if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
-            devs = processor.prefetch_keys([smp.src_u8 for smp in samples], working_size=samples[0].target_hw)
-        else:
-            devs = processor.prefetch_keys([smp.rgb_u8 for smp in samples])   # uint8 H2D + normalise + key encoder, side stream
-        pending.extend(zip(samples, devs))
-        next_idx += n
-
-    loop_t0 = perf_counter()
-    try:
-        for ti in range(vid_length):
-            if len(pending) < key_batch:                             # frames come from the decode threads (DataLoader role:
-                refill()                                             # outside the timed region, run_on_video.py:80-113)
-            sample, rgb = pending.popleft()
-            msk = labels = None
-            if ti in frames_with_masks and sample.mask is not None:
-                msk, labels = mapper.convert_mask(sample.mask, exhaustive=True)
-                if sample.need_resize:
-                    msk = vid_reader.resize_mask(msk)
-                msk = msk.to(device)
-                processor.set_all_labels(list(mapper.remappings.values()))
-            skip_add = (ti == 0) if original_memory_mechanism else (msk is not None)
-            a = perf_counter()
-            prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
-                                  manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
-            out_dev = _post_process_gpu(sample, prob)
-            if scorer is not None and sample.mask is not None:
-                scorer.add(ti, sample.mask, out_dev, mapper)
-            tag = (sample, msk is not None)
-            tdone = tracks.submit(tag, out_dev, len(mapper.labels)) if tracks is not None else ()
-            done = fetcher.submit(tag, out_dev) if need_mask else [(it[0][0], None) for it in tdone]
-            total_time += perf_counter() - a
-            for item in tdone:
-                tracks.finish(item, item[0][0][0].frame, mapper)
-            for tag, out_mask in done:
-                finish(tag, out_mask)
-        a = perf_counter()
-        tdone = tracks.drain() if tracks is not None else ()
-        done = fetcher.drain() if need_mask else [(it[0][0], None) for it in tdone]
-        total_time += perf_counter() - a
-        for item in tdone:
-            tracks.finish(item, item[0][0][0].frame, mapper)
-        for tag, out_mask in done:
-            finish(tag, out_mask)
-        if tracks is not None:
-            tracks.write(config['masks_out_path'])
-    finally:
-        decoder.close()
-        loop_wall = perf_counter() - loop_t0
-        if saver is not None:
-            saver.close()
-        total_wall = perf_counter() - loop_t0
+    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame)
     if print_fps:
         print(f'TOTAL PRELOADING TIME: {preload_time:.4f}s')
         print(f'TOTAL PROCESSING TIME: {total_time:.4f}s')
@@ -552,7 +624,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_jf(pd.DataFrame(stats), scorer)
+    return _with_jf(pd.DataFrame(outputs.stats), scorer)
 
 
 def _with_jf(df, scorer):
@@ -677,19 +749,12 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                        object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
                        compute_jf=False, network=None):
     import pandas as pd
-    from PIL import Image
-    config = VIDEO_INFERENCE_CONFIG.copy()
-    overwrite_config = {} if overwrite_config is None else dict(overwrite_config)
-    overwrite_config['masks_out_path'] = masks_out_path
-    config.update(overwrite_config)
+    config = _merged_config(dict(overwrite_config or {}), masks_out_path)           # on a copy: the caller's dict stays as it is
     passes = parse_ensemble(config.get('ensemble'), config['size'])
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
-    if not torch.cuda.is_available():
-        raise RuntimeError('xmem2_amd.run_on_video needs an MI355X (HIP) device - there is no CPU path')
-    device = torch.device('cuda', torch.cuda.current_device())
-    torch.autograd.set_grad_enabled(False)
+    device = _inference_device()                                     # after the errors of the call itself, which need no device
     frames_with_masks = set(frames_with_masks)
     P = len(passes)
 
@@ -702,10 +767,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True, resize_on_device=dev_resize)
     vid_reader = readers[passes[0][0]]
     vid_length = len(vid_reader)
-    config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196, once for all passes
-        config['enable_long_term'] and
-        (vid_length / (config['max_mid_term_frames'] - config['min_mid_term_frames']) * config['num_prototypes'])
-        >= config['max_long_term_elements'])
+    _set_long_term_count_usage(config, vid_length)                   # once for all passes
     mappers = [MaskMapper() for _ in passes]
     cores = [InferenceCore(network, config=config) for _ in passes]
 
@@ -746,43 +808,16 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     if not loaded:
         raise ValueError('No valid masks provided!')
 
-    stats, total_time = [], 0.0
-    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
-    fetcher = AsyncMaskFetcher()
     mapper = mappers[0]
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
-    tracks = _TrackLoop() if config.get('save_tracks', False) else None     # as in run_on_video, on the merged mask
-    need_mask = tracks is None or saver is not None or compute_iou
-
-    def finish(tag, out_mask):                                       # as in run_on_video, on the merged mask
-        sample, had_mask = tag
-        stat = {'frame': sample.frame, 'mask_provided': had_mask}
-        if compute_iou:
-            gt = sample.mask
-            stat['iou'] = float(compute_array_iou(out_mask, gt)) if (gt is not None and not had_mask) else -1
-        stats.append(stat)
-        if saver is not None:
-            ids = mapper.remap_index_mask(out_mask)
-
-            def job(ids=ids, sample=sample):
-                out_img = vid_reader.map_the_colors_back(Image.fromarray(ids))
-                yield out_img, 'masks', sample.frame[:-4] + '.png'
-                if save_overlay:
-                    yield _overlay(sample.raw_image_pil, out_img), 'overlay', sample.frame[:-4] + '.jpg'
-            saver.submit(job)
-
-    key_batch = max(1, int(config.get('key_batch', 4)))
-    decoder = EnsembleFramePrefetcher(readers, passes, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
-    pending, next_idx = collections.deque(), 0
+    outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again
+        vid_reader, mapper, AsyncMaskFetcher(),
+        saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
+        tracks=_TrackLoop() if config.get('save_tracks', False) else None, scorer=scorer, compute_iou=compute_iou,
+        save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=True)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
-    def refill():
-        nonlocal next_idx
-        remaining = vid_length - next_idx
-        if remaining <= 0:
-            return
-        n = key_batch if remaining >= key_batch else 1
-        samples = decoder.get(n)
+    def hint(samples):
         if dev_resize:
             # one upload per frame; the first pass of each (size, flip) makes that variant on the side stream (copy, resize / mirror and
             # key pass are stream-ordered there: inputs_complete), later passes with the same variant hint the same tensors
@@ -797,59 +832,32 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                 devs.append(made[(s, f)])
         else:
             devs = [cores[p].prefetch_keys([smp.rgb_u8[p] for smp in samples]) for p in range(P)]   # each core hints its own variants
-        pending.extend((smp, [devs[p][i] for p in range(P)]) for i, smp in enumerate(samples))
-        next_idx += n
+        return [[devs[p][i] for p in range(P)] for i in range(len(samples))]
 
-    loop_t0 = perf_counter()
-    try:
-        for ti in range(vid_length):
-            if len(pending) < key_batch:
-                refill()
-            sample, rgbs = pending.popleft()
-            given = ti in frames_with_masks and sample.mask is not None
-            per_pass = pass_masks(sample.mask) if given else None
-            skip_add = (ti == 0) if original_memory_mechanism else given
-            a = perf_counter()
-            H, W = sample.shape
-            for p, (s, f) in enumerate(passes):
-                msk = labels = None
-                if given:
-                    msk, labels = per_pass[p][0].to(device), per_pass[p][1]
-                    cores[p].set_all_labels(list(mappers[p].remappings.values()))
-                prob = cores[p].step(rgbs[p], msk, labels, end=(ti == vid_length - 1),
-                                     manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
-                shp = (prob.shape[0], H, W)                          # one pair per object count (a late object adds a class)
-                if shp not in bufs:
-                    bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
-                acc, merged = bufs[shp]
-                ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
-            if scorer is not None and sample.mask is not None:
-                scorer.add(ti, sample.mask, merged, mapper)
-            tag = (sample, given)
-            # `merged` is written again by the next frame: the record keeps a copy for the case that it has to be encoded again
-            tdone = tracks.submit(tag, merged.clone(), len(mapper.labels)) if tracks is not None else ()
-            done = fetcher.submit(tag, merged) if need_mask else [(it[0][0], None) for it in tdone]
-            total_time += perf_counter() - a
-            for item in tdone:
-                tracks.finish(item, item[0][0][0].frame, mapper)
-            for tag, out_mask in done:
-                finish(tag, out_mask)
-        a = perf_counter()
-        tdone = tracks.drain() if tracks is not None else ()
-        done = fetcher.drain() if need_mask else [(it[0][0], None) for it in tdone]
-        total_time += perf_counter() - a
-        for item in tdone:
-            tracks.finish(item, item[0][0][0].frame, mapper)
-        for tag, out_mask in done:
-            finish(tag, out_mask)
-        if tracks is not None:
-            tracks.write(config['masks_out_path'])
-    finally:
-        decoder.close()
-        loop_wall = perf_counter() - loop_t0
-        if saver is not None:
-            saver.close()
-        total_wall = perf_counter() - loop_t0
+    def prepare(ti, sample):
+        return pass_masks(sample.mask) if ti in frames_with_masks and sample.mask is not None else None
+
+    def frame(ti, sample, rgbs, per_pass):
+        given = per_pass is not None
+        skip_add = (ti == 0) if original_memory_mechanism else given
+        H, W = sample.shape
+        for p, (s, f) in enumerate(passes):
+            msk = labels = None
+            if given:
+                msk, labels = per_pass[p][0].to(device), per_pass[p][1]
+                cores[p].set_all_labels(list(mappers[p].remappings.values()))
+            prob = cores[p].step(rgbs[p], msk, labels, end=(ti == vid_length - 1),
+                                 manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
+            shp = (prob.shape[0], H, W)                              # one pair per object count (a late object adds a class)
+            if shp not in bufs:
+                bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
+            acc, merged = bufs[shp]
+            ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
+        return given, merged
+
+    key_batch = max(1, int(config.get('key_batch', 4)))
+    decoder = EnsembleFramePrefetcher(readers, passes, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
+    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame)
     if print_fps:
         print(f'ENSEMBLE PASSES: {P} (' + ', '.join(str(s) + (' flip' if f else '') for s, f in passes) + ')')
         print(f'TOTAL PRELOADING TIME: {preload_time:.4f}s')
@@ -857,7 +865,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_jf(pd.DataFrame(stats), scorer)
+    return _with_jf(pd.DataFrame(outputs.stats), scorer)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),

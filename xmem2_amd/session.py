@@ -27,7 +27,6 @@ with one copy launch per frame on the side stream instead of running the encoder
 to the cache being off; profiles/r07_session_cache.txt has the measurement.
 """
 import argparse
-import collections
 import contextlib
 import json
 import os
@@ -41,6 +40,7 @@ from . import ops
 from .configuration import VIDEO_INFERENCE_CONFIG
 from .inference_core import InferenceCore
 from .mask_mapper import MaskMapper
+from .run_on_video import hinted                 # the hint-ahead rule of every frame loop (re-exported: callers import it from here too)
 
 DEFAULT_DEVICE_FRAME_BYTES = 16 << 30          # config['session_device_frame_bytes']: frames beyond it stay in pinned host memory
 MASK_FORMS = ('objects', 'files')
@@ -64,22 +64,6 @@ def visit_order(n_frames, start=0, direction='forward', stop=None):
     if (stop - start) * step < 0:
         raise ValueError(f'stop = {stop} lies behind start = {start} when going {direction}')
     return list(range(int(start), int(stop) + step, step))
-
-
-def hinted(order, key_batch, prefetch):
-    """Yield (frame index, what `prefetch` returned for it) over `order`, hinting the key encoder as the frame loop of run_on_video
-    does: whenever fewer than `key_batch` hinted frames are pending, the next `key_batch` frames IN THE DIRECTION OF TRAVEL go to
-    `prefetch(list of indices) -> list` as one batch; a tail shorter than a batch goes frame by frame (no new graph shapes)."""
-    key_batch = max(1, int(key_batch))
-    pending, nxt = collections.deque(), 0
-    for _ in order:
-        if len(pending) < key_batch and nxt < len(order):
-            remaining = len(order) - nxt
-            n = key_batch if remaining >= key_batch else 1
-            batch = list(order[nxt:nxt + n])
-            pending.extend(zip(batch, prefetch(batch)))
-            nxt += n
-        yield pending.popleft()
 
 
 def files_table(pic):
@@ -189,7 +173,7 @@ class _Frame:
 
 class VideoSession:
     def __init__(self, imgs_in_path, masks_in_path=None, overwrite_config=None, network=None):
-        from .run_on_video import _make_network, _working_u8
+        from .run_on_video import _make_network, _set_long_term_count_usage, _working_u8
         if not os.path.isdir(imgs_in_path):
             raise NotADirectoryError(f'imgs_in_path: {imgs_in_path!r} is not a directory of frames')
         if masks_in_path is not None and not os.path.isdir(masks_in_path) and not os.path.isfile(masks_in_path):
@@ -210,10 +194,7 @@ class VideoSession:
         n = len(reader)
         if n == 0:
             raise ValueError(f'no frames in {imgs_in_path!r}')
-        config['enable_long_term_count_usage'] = (                       # run_on_video.py:190-196
-            config['enable_long_term'] and
-            (n / (config['max_mid_term_frames'] - config['min_mid_term_frames']) * config['num_prototypes'])
-            >= config['max_long_term_elements'])
+        _set_long_term_count_usage(config, n)
         self.mapper = MaskMapper()
         self.core = InferenceCore(self.network, config=config)
         self.key_batch = max(1, int(config.get('key_batch', 4)))
@@ -481,22 +462,16 @@ class VideoSession:
     def save(self, masks_out_path, save_overlay=True):
         """Exactly the files run_on_video writes: <out>/masks/<frame>.png (+ overlay/<frame>.jpg) for every frame that has a mask."""
         from PIL import Image
-        from .run_on_video import _AsyncSaver, _overlay
+        from .run_on_video import _AsyncSaver, _saver_job
         host = self._host_masks()
         saver = _AsyncSaver(str(masks_out_path), '')
         try:
             for t, fr in enumerate(self.frames):
                 if not self._present[t]:
                     continue
-                ids = self.mapper.remap_index_mask(host[t])
-
-                def job(ids=ids, fr=fr):
-                    out_img = self.reader.map_the_colors_back(Image.fromarray(ids))
-                    yield out_img, 'masks', fr.frame[:-4] + '.png'
-                    if save_overlay:
-                        img = Image.open(os.path.join(self.reader.image_dir, fr.frame)).convert('RGB')
-                        yield _overlay(img, out_img), 'overlay', fr.frame[:-4] + '.jpg'
-                saver.submit(job)
+                def reopen(name=fr.frame):                               # the decoded frames were not kept: on the writer thread
+                    return Image.open(os.path.join(self.reader.image_dir, name)).convert('RGB')
+                saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(host[t]), fr.frame, reopen if save_overlay else None))
         finally:
             saver.close()
 
@@ -563,8 +538,7 @@ class VideoSession:
         """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
         import pandas as pd
         from .metrics import InLoopScorer
-        from .run_on_video import _with_jf
-        from .tensor_util import compute_array_iou
+        from .run_on_video import _stats_row, _with_jf
         host = self._host_masks() if compute_iou else None
         if compute_jf and not self.all_masks_present():
             raise RuntimeError('compute_jf scores the whole video: run propagation on all frames first')
@@ -573,13 +547,9 @@ class VideoSession:
         for t, fr in enumerate(self.frames):
             if not self._present[t]:
                 continue
-            had_mask = t in self._refs
-            stat = {'frame': fr.frame, 'mask_provided': had_mask}
-            if compute_iou:
-                stat['iou'] = float(compute_array_iou(host[t], fr.mask)) if (fr.mask is not None and not had_mask) else -1
             if scorer is not None and fr.mask is not None:
                 scorer.add(t, fr.mask, self.masks[t], self.mapper)
-            rows.append(stat)
+            rows.append(_stats_row(fr.frame, t in self._refs, compute_iou, host[t] if compute_iou else None, fr.mask))
         return _with_jf(pd.DataFrame(rows), scorer)
 
 
