@@ -153,6 +153,37 @@ int xmem_conv2d_plan_info(const xmem_conv_desc* d, xmem_conv_plan_info* out);
 
 int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* SHARED WINOGRAD TRANSFORMS.  Sibling 3x3 / stride 1 convolutions of a residual block read one tensor (conv1(relu(g)) and
+ * downsample(g); in the batched key pass three layers read f16), and the branch's result is only ever the residual of the block's
+ * last convolution.  These entry points run the same GEMMs under the same plans as xmem_conv2d_nhwc and give the same bits; they
+ * launch fewer transforms.  All of them take fp32 convolutions whose plan resolves to F(4x4) (xmem_conv2d_plan_info: form
+ * XMEM_CONV_F4) with arith = 0; anything else returns XMEM_ERR_UNSUPPORTED before any GPU work (the size queries return 0) and the
+ * caller issues separate xmem_conv2d_nhwc calls.
+ *
+ * xmem_conv2d_shared_input: descs[0..n-1], n = 2 or 3, agree in in / ldin / B / H / W / Cin.  ONE input-transform launch
+ * writes one V per distinct relu_in (at most two: raw and relu; consumers with the same flag share theirs), then every
+ * convolution runs its own position GEMMs and output transform, in order, as xmem_conv2d_nhwc would.  defer_m (NULL: none) names,
+ * per convolution, a buffer of defer_m_bytes[i] >= xmem_conv2d_m_bytes(descs[i]) bytes, 16-byte aligned: that convolution stops
+ * after its GEMMs and leaves M [36][tiles][Cout] there (its `out` is not written but must be a valid descriptor field), to be
+ * finished by xmem_conv2d_nhwc_folded or xmem_conv2d_output_from_m.  The buffer is the caller's: it must not be the workspace of
+ * any convolution issued in between.  workspace: xmem_conv2d_shared_input_workspace_bytes(descs, n) bytes.
+ *
+ * xmem_conv2d_nhwc_folded: the convolution `d` (d->res NULL) with the deferred convolution `branch` as its residual,
+ *   r   = [relu_out_b](A^T M_branch A * scale_b + shift_b [+ res_b])        (res_b plain or res_broadcast, as in `branch`)
+ *   out = [relu_out](A^T M A * scale + shift + r)
+ * in ONE output transform: r stays in registers instead of being stored by the branch and loaded back.  Same B, Ho, Wo, Cout on
+ * both sides.  workspace: xmem_conv2d_workspace_bytes(d) bytes.
+ *
+ * xmem_conv2d_output_from_m: the output transform + epilogue of a deferred convolution alone (when the fold does not apply). */
+#define XMEM_CONV_SHARED_MAX 3
+size_t xmem_conv2d_shared_input_workspace_bytes(const xmem_conv_desc* const* descs, int n);
+size_t xmem_conv2d_m_bytes(const xmem_conv_desc* d);
+int xmem_conv2d_shared_input(const xmem_conv_desc* const* descs, int n, void* const* defer_m, const size_t* defer_m_bytes,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int xmem_conv2d_nhwc_folded(const xmem_conv_desc* d, const xmem_conv_desc* branch, const void* branch_m, size_t branch_m_bytes,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int xmem_conv2d_output_from_m(const xmem_conv_desc* d, const void* m, size_t m_bytes, void* stream);
+
 /* Dilated convolution (atrous), the S2M network's DeepLabV3+ (inference/interact/s2m/s2m_resnet.py:17-20 conv3x3 with dilation, the
  * layer4 blocks 1-2 of _make_layer's replace_stride_with_dilation, :138-150; ASPPConv, s2m/_deeplab.py:113-119, rates 6 / 12 / 18).
  * Same descriptor and epilogue as xmem_conv2d_nhwc (scale / shift, res, relu_in / relu_out, ldin / ldout channel slices); tap (kh, kw)

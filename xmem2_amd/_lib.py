@@ -38,6 +38,7 @@ class ConvPlanInfo(C.Structure):
 
 CONV_FORMS = ('gemv', 'direct', 'f2', 'f2_fused', 'f2_f16', 'f4')    # include/xmem_hip.h XMEM_CONV_*
 UNSUPPORTED = -2         # include/xmem_hip.h XMEM_ERR_UNSUPPORTED
+CONV_SHARED_MAX = 3      # include/xmem_hip.h XMEM_CONV_SHARED_MAX: convolutions one xmem_conv2d_shared_input call carries
 DILATED_NO_TAP_SKIP = 1  # include/xmem_hip.h XMEM_DILATED_NO_TAP_SKIP
 RLE_META = 6             # include/xmem_hip.h XMEM_RLE_META: int32 values per (frame, label) of xmem_rle_encode's meta
 COPY_MAX_SEGMENTS = 16   # include/xmem_hip.h XMEM_COPY_MAX_SEGMENTS: (src, dst, bytes) triples one xmem_copy_segments launch carries
@@ -66,6 +67,13 @@ _SIGS = {
     'xmem_conv2d_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc)]),
     'xmem_conv2d_plan_info': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvPlanInfo)]),
     'xmem_conv2d_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'xmem_conv2d_shared_input_workspace_bytes': (C.c_size_t, [C.POINTER(C.POINTER(ConvDesc)), C.c_int]),
+    'xmem_conv2d_m_bytes': (C.c_size_t, [C.POINTER(ConvDesc)]),
+    'xmem_conv2d_shared_input': (C.c_int, [C.POINTER(C.POINTER(ConvDesc)), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    'xmem_conv2d_nhwc_folded': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
+    'xmem_conv2d_output_from_m': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     'xmem_conv2d_dilated_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc), C.c_int]),
     'xmem_conv2d_nhwc_dilated': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     'xmem_maxpool3x3s2': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -1104,7 +1104,8 @@ __global__ __launch_bounds__(256) void wino_fused_kernel(WinoArgs p) {
 #define W4_SUM 2.8125f         // a^2 + b^2
 #define W4_AB2 1.6875f         // a b^2
 #define W4_BA2 0.84375f        // b a^2
-__device__ __forceinline__ void wino4_bt(const f32x4* d, f32x4* t) {      // t = B^T d for one 6-vector
+template <typename T>
+__device__ __forceinline__ void wino4_bt(const T* d, T* t) {              // t = B^T d for one 6-vector
     t[0] = W4_A2B2 * d[0] - W4_SUM * d[2] + d[4];
     t[1] = -W4_AB2 * d[1] - W4_B2 * d[2] + W4_A * d[3] + d[4];
     t[2] = W4_AB2 * d[1] - W4_B2 * d[2] - W4_A * d[3] + d[4];
@@ -1112,15 +1113,19 @@ __device__ __forceinline__ void wino4_bt(const f32x4* d, f32x4* t) {      // t =
     t[4] = W4_BA2 * d[1] - W4_A2 * d[2] - W4_B * d[3] + d[4];
     t[5] = W4_A2B2 * d[1] - W4_SUM * d[3] + d[5];
 }
-__device__ __forceinline__ void wino4_at(const f32x4* m, f32x4* s) {      // s = A^T m for one 6-vector
+template <typename T>
+__device__ __forceinline__ void wino4_at(const T* m, T* s) {              // s = A^T m for one 6-vector
     s[0] = m[0] + m[1] + m[2] + m[3] + m[4];
     s[1] = W4_A * m[1] - W4_A * m[2] + W4_B * m[3] - W4_B * m[4];
     s[2] = W4_A2 * m[1] + W4_A2 * m[2] + W4_B2 * m[3] + W4_B2 * m[4];
     s[3] = W4_A3 * m[1] - W4_A3 * m[2] + W4_B3 * m[3] - W4_B3 * m[4] + m[5];
 }
 
+// blockIdx.y = 1 (xmem_conv2d_shared_input): the same transform with the activation flag `relu_in2` into `V2` - sibling convolutions
+// that read one tensor get the V of both variants (raw, relu) from ONE launch; the second read of a patch is served by the L2.
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ in, int ldin, int B, int H, int W, int C, int th, int tw,
-                                                          int relu_in, float* __restrict__ V, int split) {
+                                                          int relu_in, float* __restrict__ V, int split, float* __restrict__ V2, int relu_in2) {
+    if (blockIdx.y) { V = V2; relu_in = relu_in2; }
     const int C4 = C >> 2;
     const size_t P = (size_t)B * th * tw;
     const size_t total = P * C4;
@@ -1233,6 +1238,123 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restri
                 if (ow >= Wo) continue;
                 const size_t pix = ((size_t)b * Ho + oh) * Wo + ow;
                 *reinterpret_cast<f32x4*>(out + pix * ldout + n4 * 4) = rv[dy][dx];
+            }
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
+// SHARED TRANSFORMS (xmem_conv2d_shared_input, xmem_conv2d_nhwc_folded).  Sibling convolutions of a residual block read the same
+// tensor: conv1(relu(g)) and downsample(g), and in the batched key pass three layers read f16.  One launch of wino4_input_kernel
+// (blockIdx.y: the variant) writes the V of both activation variants; and the branch's output transform is formed inside the main
+// convolution's (below), instead of being stored and read back as its residual.  The fold works on TWO channels per lane: two M
+// sets and the branch residual requested together would not fit the 256 VGPRs at four.  Per channel its operations and their order
+// are those of wino4_output_kernel.
+// (The input side deliberately re-runs the UNCHANGED transform code per variant instead of forming both from one loaded patch: the
+// compiler contracts a*b + c into fma depending on the code around the expression - even the raw and the relu body of
+// wino4_input_kernel are contracted differently - and a kernel that formed both variants from one patch, two channels per lane,
+// differed from the separate launches in the last bit of 39 % of a layer's outputs on the MI355X.  Bit-identity with the separate
+// convolutions is the contract; the merged launch keeps the launch it saves, the second read of the patch comes from the L2.)
+// ----------------------------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct WinoFoldArgs {
+    const float* Mt; const float* Mb;                  // [36][P][Cout] of the main convolution and of the branch
+    const float* scale; const float* shift;            // main epilogue
+    const float* scale_b; const float* shift_b; const float* res_b;      // branch epilogue
+    float* out;
+    int B, Ho, Wo, Cout, th, tw, ldout, relu_out, ldres_b, res_b_bcast, relu_b;
+};
+
+// out = [relu](A^T M A * sc + sh + r), r = [relu_b](A^T M_b A * sc_b + sh_b [+ res_b]): what wino4_output_kernel computes for the
+// branch, kept in registers, and then for the main convolution with r as its residual
+__global__ __launch_bounds__(256) void wino4_output_fold_kernel(WinoFoldArgs p) {
+    const int N2 = p.Cout >> 1;
+    const size_t P = (size_t)p.B * p.th * p.tw;
+    const size_t total = P * N2;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int n2 = (int)(e % N2);
+        size_t t = e / N2;
+        const int tx = (int)(t % p.tw); size_t r = t / p.tw;
+        const int ty = (int)(r % p.th);
+        const int b = (int)(r / p.th);
+        f32x2 rv[4][4], mm[6][6], mb[6][6];            // every load of the item is requested before the first arithmetic
+        if (p.res_b) {
+#pragma unroll
+            for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < 4; ++dx) {
+                    const int oh = min(4 * ty + dy, p.Ho - 1), ow = min(4 * tx + dx, p.Wo - 1);  // clamped: never stored when outside
+                    const size_t pix = ((size_t)b * p.Ho + oh) * p.Wo + ow;
+                    rv[dy][dx] = *reinterpret_cast<const f32x2*>(p.res_b + (p.res_b_bcast ? (size_t)oh * p.Wo + ow : pix) * p.ldres_b + n2 * 2);
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                const size_t off = ((size_t)(i * 6 + j) * P + t) * p.Cout + n2 * 2;
+                mb[i][j] = *reinterpret_cast<const f32x2*>(p.Mb + off);
+                mm[i][j] = *reinterpret_cast<const f32x2*>(p.Mt + off);
+            }
+        const f32x2 sclb = *reinterpret_cast<const f32x2*>(p.scale_b + n2 * 2), shb = *reinterpret_cast<const f32x2*>(p.shift_b + n2 * 2);
+        const f32x2 scl = *reinterpret_cast<const f32x2*>(p.scale + n2 * 2), sh = *reinterpret_cast<const f32x2*>(p.shift + n2 * 2);
+        f32x2 s[4][6];
+        // the branch: A^T m column by column, then its epilogue into the residual registers
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            f32x2 col[6], sc[4];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) col[i] = mb[i][j];
+            wino4_at(col, sc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[i][j] = sc[i];
+        }
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy) {
+            f32x2 y[4];
+            wino4_at(s[dy], y);
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) {
+                f32x2 v = y[dx] * sclb + shb;
+                if (p.res_b) v += rv[dy][dx];
+                if (p.relu_b) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
+                rv[dy][dx] = v;
+            }
+        }
+        // the main convolution with the branch as its residual: the 16 outputs are finished in registers ...
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            f32x2 col[6], sc[4];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) col[i] = mm[i][j];
+            wino4_at(col, sc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[i][j] = sc[i];
+        }
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy) {
+            f32x2 y[4];
+            wino4_at(s[dy], y);
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) {
+                f32x2 v = y[dx] * scl + sh;
+                v += rv[dy][dx];
+                if (p.relu_out) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
+                rv[dy][dx] = v;
+            }
+        }
+        // ... then stored
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy) {
+            const int oh = 4 * ty + dy;
+            if (oh >= p.Ho) continue;
+#pragma unroll
+            for (int dx = 0; dx < 4; ++dx) {
+                const int ow = 4 * tx + dx;
+                if (ow >= p.Wo) continue;
+                const size_t pix = ((size_t)b * p.Ho + oh) * p.Wo + ow;
+                *reinterpret_cast<f32x2*>(p.out + pix * p.ldout + n2 * 2) = rv[dy][dx];
             }
         }
     }
@@ -1661,22 +1783,12 @@ int launch_splitk_reduce(const ConvArgs& a, bool half_out, hipStream_t s) {
 
 int stream_variant(const Plan& pl) { return pl.bm == 64 ? 0 : (pl.bn == 64 ? 1 : 2); }     // gemm_stream.hpp: 64x64, 128x64, 128x128
 
-// Unfused Winograd F(r x r, 3x3), r = 2 or 4: input transform -> V, the (r+2)^2 position GEMMs M[xi] = V[xi] U[xi]^T of
-// [P x Cin] x [Cin x Cout] (on the plan's tile of the implicit-GEMM kernel, or on the streaming kernel), output transform + epilogue.
-int run_winograd(const Plan& pl, const xmem_conv_desc* d, const ConvArgs& a, int r, void* workspace, hipStream_t s) {
-    const int th = cdiv(a.Ho, r), tw = cdiv(a.Wo, r), G = (r + 2) * (r + 2);
-    const size_t P = wino_tiles(d, a.Ho, a.Wo, r);
-    if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
+// The (r+2)^2 position GEMMs M[xi] = V[xi] U[xi]^T of [P x Cin] x [Cin x Cout]: on the plan's tile of the implicit-GEMM kernel, or
+// on the streaming kernel.
+int wino_position_gemm(const Plan& pl, const xmem_conv_desc* d, const ConvArgs& a, int r, const float* V, float* Mt, size_t P, hipStream_t s) {
+    const int G = (r + 2) * (r + 2);
     const float* U = r == 4 ? d->w_winograd4 : d->w_winograd;
     const void* U_split = r == 4 ? d->w_winograd4_split : d->w_winograd_split;
-    float* V = reinterpret_cast<float*>(workspace);
-    float* Mt = V + (size_t)G * P * d->Cin;
-    const auto input_kernel = r == 4 ? wino4_input_kernel : wino_input_kernel;
-    const auto output_kernel = r == 4 ? wino4_output_kernel : wino_output_kernel;
-    int blocks, threads, rc;
-    transform_grid(P * (d->Cin / 4), blocks, threads);
-    hipLaunchKernelGGL(input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W,
-                       d->Cin, th, tw, d->relu_in, V, pl.split ? 1 : 0);
     if (pl.ring) {
         GemmStreamArgs g = {};
         g.A = V; g.B = U; g.C = Mt;
@@ -1684,24 +1796,89 @@ int run_winograd(const Plan& pl, const xmem_conv_desc* d, const ConvArgs& a, int
         g.M = (int)P; g.N = d->Cout; g.K = d->Cin; g.G = G;
         g.lda = d->Cin; g.ldb = d->Cin; g.ldc = d->Cout;
         g.mode = 0; g.stride = 1;
-        rc = gemm_stream_launch(g, stream_variant(pl), pl.ring, s);
-    } else {
-        ConvArgs g = a;
-        g.in = V; g.w = pl.split ? reinterpret_cast<const float*>(U_split) : U;
-        g.a_presplit = 1; g.out = Mt; g.res = nullptr; g.partial = nullptr;
-        g.B = 1; g.H = 1; g.W = (int)P; g.ldin = d->Cin; g.Ho = 1; g.Wo = (int)P; g.ldout = d->Cout; g.ldres = 0;
-        g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.K = d->Cin; g.M = (int)P; g.HoWo = (int)P;
-        g.relu_in = 0; g.relu_out = 0; g.nk = pl.nk; g.splitk = 1; g.kt_per_split = pl.nk;
-        g.tiles_m = cdiv(g.M, pl.bm); g.tiles_n = cdiv(g.Cout, pl.bn);
-        g.raw = 1; g.in_gstride = (long)P * d->Cin; g.w_gstride = (long)d->Cout * d->Cin; g.out_gstride = (long)P * d->Cout;
-        rc = launch_tile(pl, g, s, G);
+        return gemm_stream_launch(g, stream_variant(pl), pl.ring, s);
     }
-    if (rc != XMEM_OK) return rc;
+    ConvArgs g = a;
+    g.in = V; g.w = pl.split ? reinterpret_cast<const float*>(U_split) : U;
+    g.a_presplit = 1; g.out = Mt; g.res = nullptr; g.partial = nullptr;
+    g.B = 1; g.H = 1; g.W = (int)P; g.ldin = d->Cin; g.Ho = 1; g.Wo = (int)P; g.ldout = d->Cout; g.ldres = 0;
+    g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.K = d->Cin; g.M = (int)P; g.HoWo = (int)P;
+    g.relu_in = 0; g.relu_out = 0; g.nk = pl.nk; g.splitk = 1; g.kt_per_split = pl.nk;
+    g.tiles_m = cdiv(g.M, pl.bm); g.tiles_n = cdiv(g.Cout, pl.bn);
+    g.raw = 1; g.in_gstride = (long)P * d->Cin; g.w_gstride = (long)d->Cout * d->Cin; g.out_gstride = (long)P * d->Cout;
+    return launch_tile(pl, g, s, G);
+}
+
+// output transform + epilogue of `d` from its M
+int wino_output(const xmem_conv_desc* d, int Ho, int Wo, int r, const float* Mt, size_t P, hipStream_t s) {
+    const auto output_kernel = r == 4 ? wino4_output_kernel : wino_output_kernel;
+    int blocks, threads;
     transform_grid(P * (d->Cout / 4), blocks, threads);
-    hipLaunchKernelGGL(output_kernel, dim3(blocks), dim3(threads), 0, s, Mt, d->B, a.Ho, a.Wo, d->Cout,
-                       th, tw, d->scale, d->shift, d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
+    hipLaunchKernelGGL(output_kernel, dim3(blocks), dim3(threads), 0, s, Mt, d->B, Ho, Wo, d->Cout,
+                       cdiv(Ho, r), cdiv(Wo, r), d->scale, d->shift, d->res, d->ldres, d->res_broadcast ? 1 : 0, d->relu_out, d->out, d->ldout);
     return xmem_check_launch();
 }
+
+// Unfused Winograd F(r x r, 3x3), r = 2 or 4: input transform -> V, the (r+2)^2 position GEMMs (wino_position_gemm), output
+// transform + epilogue.
+int run_winograd(const Plan& pl, const xmem_conv_desc* d, const ConvArgs& a, int r, void* workspace, hipStream_t s) {
+    const int th = cdiv(a.Ho, r), tw = cdiv(a.Wo, r), G = (r + 2) * (r + 2);
+    const size_t P = wino_tiles(d, a.Ho, a.Wo, r);
+    if (P > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
+    float* V = reinterpret_cast<float*>(workspace);
+    float* Mt = V + (size_t)G * P * d->Cin;
+    int blocks, threads, rc;
+    transform_grid(P * (d->Cin / 4), blocks, threads);
+    if (r == 4) hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W,
+                                   d->Cin, th, tw, d->relu_in, V, pl.split ? 1 : 0, nullptr, 0);
+    else hipLaunchKernelGGL(wino_input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W,
+                            d->Cin, th, tw, d->relu_in, V, pl.split ? 1 : 0);
+    if ((rc = wino_position_gemm(pl, d, a, r, V, Mt, P, s)) != XMEM_OK) return rc;
+    return wino_output(d, a.Ho, a.Wo, r, Mt, P, s);
+}
+
+// ---- shared transforms (xmem_conv2d_shared_input, xmem_conv2d_nhwc_folded) ----
+// An fp32 convolution whose plan is F(4x4) on unsplit operands: what the shared entry points run.  XMEM_OK and the plan, or why not.
+int f4_plan_of(const xmem_conv_desc* d, Plan& pl) {
+    const int rc = validate(d);
+    if (rc != XMEM_OK) return rc;
+    if (d->in_half || d->out_half) return XMEM_ERR_UNSUPPORTED;
+    pl = make_plan(d, d->plan_tile);
+    if (pl.form != F4 || pl.split) return XMEM_ERR_UNSUPPORTED;
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
+    if (wino_tiles(d, Ho, Wo, 4) > 0x7fffffff) return XMEM_ERR_UNSUPPORTED;
+    return XMEM_OK;
+}
+
+inline size_t f4_m_bytes(const xmem_conv_desc* d) {
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
+    return (size_t)36 * wino_tiles(d, Ho, Wo, 4) * d->Cout * sizeof(float);
+}
+
+// The layout of xmem_conv2d_shared_input's workspace: V of the raw input (when a consumer reads it), V of relu(input) (likewise),
+// then one M as wide as the widest consumer (the consumers run one after the other on the stream).
+struct SharedLayout { size_t P, v_floats, m_floats; int n_raw, n_relu; };
+int shared_layout(const xmem_conv_desc* const* ds, int n, Plan* pls, SharedLayout& L) {
+    if (!ds || n < 2 || n > XMEM_CONV_SHARED_MAX) return XMEM_ERR_BAD_ARG;
+    for (int i = 0; i < n; ++i) if (!ds[i]) return XMEM_ERR_BAD_ARG;
+    L = {};
+    int max_cout = 0;
+    for (int i = 0; i < n; ++i) {
+        const xmem_conv_desc* d = ds[i];
+        const int rc = f4_plan_of(d, pls[i]);
+        if (rc != XMEM_OK) return rc;
+        if (d->in != ds[0]->in || d->ldin != ds[0]->ldin || d->B != ds[0]->B || d->H != ds[0]->H || d->W != ds[0]->W || d->Cin != ds[0]->Cin)
+            return XMEM_ERR_UNSUPPORTED;
+        if (d->relu_in) ++L.n_relu; else ++L.n_raw;
+        if (d->Cout > max_cout) max_cout = d->Cout;
+    }
+    int Ho, Wo; out_dims(ds[0], 1, Ho, Wo);
+    L.P = wino_tiles(ds[0], Ho, Wo, 4);
+    L.v_floats = (size_t)36 * L.P * ds[0]->Cin;
+    L.m_floats = (size_t)36 * L.P * max_cout;
+    return XMEM_OK;
+}
+inline size_t shared_bytes(const SharedLayout& L) { return (((L.n_raw ? 1 : 0) + (L.n_relu ? 1 : 0)) * L.v_floats + L.m_floats) * sizeof(float); }
 
 }  // namespace
 
@@ -1832,6 +2009,92 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
     }
 #endif
     return pl.splitk > 1 ? launch_splitk_reduce(a, half == 2, s) : rc;
+}
+
+extern "C" size_t xmem_conv2d_shared_input_workspace_bytes(const xmem_conv_desc* const* descs, int n) {
+    Plan pls[XMEM_CONV_SHARED_MAX]; SharedLayout L;
+    return shared_layout(descs, n, pls, L) == XMEM_OK ? shared_bytes(L) : 0;
+}
+
+extern "C" size_t xmem_conv2d_m_bytes(const xmem_conv_desc* d) {
+    Plan pl;
+    return f4_plan_of(d, pl) == XMEM_OK ? f4_m_bytes(d) : 0;
+}
+
+extern "C" int xmem_conv2d_shared_input(const xmem_conv_desc* const* descs, int n, void* const* defer_m, const size_t* defer_m_bytes,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    Plan pls[XMEM_CONV_SHARED_MAX]; SharedLayout L;
+    int rc = shared_layout(descs, n, pls, L);
+    if (rc != XMEM_OK) return rc;
+    if (!workspace || workspace_bytes < shared_bytes(L)) return XMEM_ERR_WORKSPACE;
+    for (int i = 0; i < n; ++i)
+        if (defer_m && defer_m[i] && (!defer_m_bytes || defer_m_bytes[i] < f4_m_bytes(descs[i]) || (((uintptr_t)defer_m[i]) & 15) != 0))
+            return XMEM_ERR_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const xmem_conv_desc* d0 = descs[0];
+    int Ho, Wo; out_dims(d0, 1, Ho, Wo);
+    const int th = cdiv(Ho, 4), tw = cdiv(Wo, 4);
+    float* Vraw = reinterpret_cast<float*>(workspace);
+    float* Vrelu = Vraw + (L.n_raw ? L.v_floats : 0);
+    float* Mt = Vrelu + (L.n_relu ? L.v_floats : 0);
+    int blocks, threads;
+    const int variants = (L.n_raw ? 1 : 0) + (L.n_relu ? 1 : 0);       // one V per distinct relu_in; with both, raw first
+    transform_grid(L.P * (d0->Cin / 4), blocks, threads);
+    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks, variants), dim3(threads), 0, s, d0->in, d0->ldin, d0->B, d0->H, d0->W, d0->Cin,
+                       th, tw, L.n_raw ? 0 : 1, Vraw, 0, Vrelu, 1);
+    if ((rc = xmem_check_launch()) != XMEM_OK) return rc;
+    for (int i = 0; i < n; ++i) {                  // each consumer under its own plan: position GEMMs, then its output transform
+        const xmem_conv_desc* d = descs[i];
+        const ConvArgs a = conv_args(d, pls[i], Ho, Wo, nullptr);
+        float* m = defer_m && defer_m[i] ? reinterpret_cast<float*>(defer_m[i]) : Mt;
+        if ((rc = wino_position_gemm(pls[i], d, a, 4, d->relu_in ? Vrelu : Vraw, m, L.P, s)) != XMEM_OK) return rc;
+        if (m == Mt && (rc = wino_output(d, Ho, Wo, 4, Mt, L.P, s)) != XMEM_OK) return rc;
+    }
+    return XMEM_OK;
+}
+
+extern "C" int xmem_conv2d_output_from_m(const xmem_conv_desc* d, const void* m, size_t m_bytes, void* stream) {
+    Plan pl;
+    const int rc = f4_plan_of(d, pl);
+    if (rc != XMEM_OK) return rc;
+    if (!m || m_bytes < f4_m_bytes(d)) return XMEM_ERR_WORKSPACE;
+    int Ho, Wo; out_dims(d, 1, Ho, Wo);
+    return wino_output(d, Ho, Wo, 4, reinterpret_cast<const float*>(m), wino_tiles(d, Ho, Wo, 4), reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int xmem_conv2d_nhwc_folded(const xmem_conv_desc* d, const xmem_conv_desc* branch, const void* branch_m, size_t branch_m_bytes,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    Plan pl, plb;
+    int rc = f4_plan_of(d, pl);
+    if (rc != XMEM_OK) return rc;
+    if (!branch || (rc = f4_plan_of(branch, plb)) != XMEM_OK) return rc ? rc : XMEM_ERR_BAD_ARG;
+    if (d->res) return XMEM_ERR_BAD_ARG;          // the branch is the residual
+    int Ho, Wo, Hb, Wb; out_dims(d, 1, Ho, Wo); out_dims(branch, 1, Hb, Wb);
+    if (branch->B != d->B || Hb != Ho || Wb != Wo || branch->Cout != d->Cout) return XMEM_ERR_UNSUPPORTED;
+    if (!branch_m || branch_m_bytes < f4_m_bytes(branch) || (((uintptr_t)branch_m) & 15) != 0) return XMEM_ERR_WORKSPACE;
+    if (branch->res && (branch->ldres % 4 != 0 || (((uintptr_t)branch->res) & 15) != 0)) return XMEM_ERR_UNSUPPORTED;
+    const size_t need = workspace_need(pl, d, Ho, Wo);
+    if (!workspace || workspace_bytes < need) return XMEM_ERR_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int th = cdiv(Ho, 4), tw = cdiv(Wo, 4);
+    const size_t P = wino_tiles(d, Ho, Wo, 4);
+    float* V = reinterpret_cast<float*>(workspace);
+    float* Mt = V + (size_t)36 * P * d->Cin;
+    int blocks, threads;
+    transform_grid(P * (d->Cin / 4), blocks, threads);
+    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks), dim3(threads), 0, s, d->in, d->ldin, d->B, d->H, d->W, d->Cin, th, tw,
+                       d->relu_in, V, 0, nullptr, 0);
+    const ConvArgs a = conv_args(d, pl, Ho, Wo, nullptr);
+    if ((rc = wino_position_gemm(pl, d, a, 4, V, Mt, P, s)) != XMEM_OK) return rc;
+    WinoFoldArgs f;
+    f.Mt = Mt; f.Mb = reinterpret_cast<const float*>(branch_m);
+    f.scale = d->scale; f.shift = d->shift; f.scale_b = branch->scale; f.shift_b = branch->shift; f.res_b = branch->res;
+    f.out = d->out;
+    f.B = d->B; f.Ho = Ho; f.Wo = Wo; f.Cout = d->Cout; f.th = th; f.tw = tw; f.ldout = d->ldout; f.relu_out = d->relu_out;
+    f.ldres_b = branch->ldres; f.res_b_bcast = branch->res_broadcast ? 1 : 0; f.relu_b = branch->relu_out;
+    transform_grid(P * (d->Cout / 2), blocks, threads);
+    hipLaunchKernelGGL(wino4_output_fold_kernel, dim3(blocks), dim3(threads), 0, s, f);
+    return xmem_check_launch();
 }
 
 extern "C" int xmem_mask_head_gather(const float* g16, int c16, const float* g8, int c8, const float* g4, int c4, const float* w,

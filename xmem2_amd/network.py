@@ -74,6 +74,10 @@ class XMem:
         # weights are uploaded) keeps the separate launches and the unpadded filters: an A/B switch, bit-identical either way
         self.fused_tail = os.environ.get('XMEM_FUSED_TAIL', '1') != '0'
         self.fused_tail_min_pixels = FUSED_TAIL_MIN_PIXELS
+        # sibling 3x3 convolutions of a residual block / of the batched key pass behind one Winograd input transform, and the block's
+        # branch folded into its last output transform (ops.conv2d_shared / conv2d_folded).  XMEM_SHARED_TRANSFORMS=0 keeps the
+        # separate convolutions: an A/B switch, bit-identical either way.  fp32 only; the other precisions always run separately
+        self.shared_transforms = os.environ.get('XMEM_SHARED_TRANSFORMS', '1') != '0'
         # 'fp32' (default: the parity contract) | 'fp16' (opt-in: the fp16 loop - half activations in HBM, half-operand convolutions
         # on the fp16 MFMA with fp32 accumulation: the counterpart of the reference's autocast loop, run_on_video.py:76; the
         # permanent-memory preload stays fp32 as in run_on_video.py:59-66) | 'fp16w' / 'fp32x' (experiments, ops.PRECISIONS)
@@ -425,6 +429,10 @@ class XMem:
     def _group_res(self, g, p, out=None, out_ld=None):
         """GroupResBlock, model/group_modules.py:44-52: conv2(relu(conv1(relu(g)))) + (downsample(g) | g)."""
         W = self._w
+        if self.shared_transforms and (p + '.downsample') in W:
+            # one input transform of g for both convolutions; the branch stays in the Winograd domain until conv2's output transform
+            o, res = ops.conv2d_shared(g, [dict(cw=W[p + '.conv1'], relu_in=True, relu_out=True), dict(cw=W[p + '.downsample'])], defer=1)
+            return ops.conv2d_folded(o, W[p + '.conv2'], res, out=out, out_ld=out_ld)
         o = ops.conv2d(g, W[p + '.conv1'], relu_in=True, relu_out=True)
         res = ops.conv2d(g, W[p + '.downsample']) if (p + '.downsample') in W else g
         return ops.conv2d(o, W[p + '.conv2'], res=res, out=out, out_ld=out_ld)
@@ -447,9 +455,14 @@ class XMem:
             # pre = (conv1@x(relu(x)), downsample@x(x)) already made in the batched key pass (prefetched frames)
             sx = pre[0] if pre is not None else ops.conv2d(x, W[b1 + '.conv1@x'], relu_in=True)
             dx = pre[1] if pre is not None else ops.conv2d(x, W[b1 + '.downsample@x'])
-            o = ops.conv2d(gpart, W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True, in_ld=ld, cin=cg)
-            res = ops.conv2d(gpart, W[b1 + '.downsample@g'], res=dx, res_broadcast=True, in_ld=ld, cin=cg)
-            g = ops.conv2d(o, W[b1 + '.conv2'], res=res)
+            if self.shared_transforms:
+                o, res = ops.conv2d_shared(gpart, [dict(cw=W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True),
+                                                   dict(cw=W[b1 + '.downsample@g'], res=dx, res_broadcast=True)], in_ld=ld, cin=cg, defer=1)
+                g = ops.conv2d_folded(o, W[b1 + '.conv2'], res)
+            else:
+                o = ops.conv2d(gpart, W[b1 + '.conv1@g'], relu_in=True, relu_out=True, res=sx, res_broadcast=True, in_ld=ld, cin=cg)
+                res = ops.conv2d(gpart, W[b1 + '.downsample@g'], res=dx, res_broadcast=True, in_ld=ld, cin=cg)
+                g = ops.conv2d(o, W[b1 + '.conv2'], res=res)
         else:
             g = self._group_res(cat, b1)
         g = ops.cbam_residual(g, self._cbam[p + '.attention'])
@@ -493,16 +506,23 @@ class XMem:
         B, h, w, _ = f16.shape
         ld = _pad4(2 * self.key_dim + 1)
         proj = torch.empty((B, h, w, ld), dtype=torch.float32, device=f16.device)
-        ops.conv2d(f16, W['key_proj'], out=proj, out_ld=ld, out_dtype=torch.float32)     # keys / shrinkage / selection are fp32 in every mode
+        b1 = 'decoder.fuser.block1'
+        split_x = (b1 + '.conv1@x') in W and (b1 + '.downsample@x') in W
+        fx = None
+        if inline_skips and split_x and self.shared_transforms:
+            # the three 3x3 layers that read f16 behind one input transform (two V: raw for key_proj and downsample@x, relu for conv1@x)
+            _, *fx = ops.conv2d_shared(f16, [dict(cw=W['key_proj'], out=proj, out_ld=ld, out_dtype=torch.float32),
+                                             dict(cw=W[b1 + '.conv1@x'], relu_in=True), dict(cw=W[b1 + '.downsample@x'])])
+        else:
+            ops.conv2d(f16, W['key_proj'], out=proj, out_ld=ld, out_dtype=torch.float32)     # keys / shrinkage / selection are fp32 in every mode
         key, shr, sel = ops.key_post(proj, self.key_dim, need_sk, need_ek)
         if inline_skips:                      # same stream: f8 / f4 only depend on the image (model/modules.py:186,231-232)
             extras = (ops.conv2d(f8, W['decoder.up_16_8.skip_conv']), ops.conv2d(f4, W['decoder.up_8_4.skip_conv']))
-            if ('decoder.fuser.block1.conv1@x') in W and ('decoder.fuser.block1.downsample@x') in W:
+            if split_x:
                 # FeatureFusionBlock convolves cat([f16, readout, hidden]) (model/modules.py:31-41): W * cat = W_x * f16 + W_g * [readout |
                 # hidden], and the f16 half (1024 of 1600 input channels of block1's two 3x3 convolutions) depends on the frame only -
                 # so it is convolved HERE, in the batched pass on the side stream, and enters the decoder as a residual
-                b1 = 'decoder.fuser.block1'
-                extras += (ops.conv2d(f16, W[b1 + '.conv1@x'], relu_in=True), ops.conv2d(f16, W[b1 + '.downsample@x']))
+                extras += tuple(fx) if fx is not None else (ops.conv2d(f16, W[b1 + '.conv1@x'], relu_in=True), ops.conv2d(f16, W[b1 + '.downsample@x']))
             return key, shr, sel, f16, f8, f4, extras
         return key, shr, sel, f16, f8, f4
 

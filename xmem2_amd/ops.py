@@ -308,26 +308,28 @@ def _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out):
     d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
     d.res = res.data_ptr() if res is not None else None
     d.ldres = res.shape[-1] if res is not None else 0
-    d.out = out.data_ptr(); d.ldout = out_ld
+    d.out = out.data_ptr() if out is not None else None; d.ldout = out_ld
     d.relu_in, d.relu_out = int(relu_in), int(relu_out)
     return d
 
 
-def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half):
-    """One convolution of either path: descriptor, the operands of the precision mode, plan (conv_plan.choose), workspace, launch
-    on the current stream, and the RECORD entry."""
+def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, alloc=True, folded=False):
+    """What comes before the launch of one convolution of either path: the output buffer (`alloc` False: left None for the caller),
+    the descriptor with the operands of the precision mode and the plan (conv_plan.choose).  `folded`: the residual arrives inside the
+    output transform (conv2d_folded) - planned as the convolution with a residual that it is, the plan tables being keyed by the
+    epilogue too.  -> (d, out, out_ld, key, plan, wino_ok)"""
     lib = load()
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
     Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
     Wo = (W + 2 * cw.pad - cw.kw) // cw.stride + 1
     if out is None:
-        out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=out_dtype, device=x.device), cw.cout
+        out, out_ld = (torch.empty((B, Ho, Wo, cw.cout), dtype=out_dtype, device=x.device) if alloc else None), cw.cout
     elif out_ld is None:
         out_ld = out.shape[-1]
     d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
     d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
     wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
-    key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
+    key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None or folded)}{int(relu_in)}{int(relu_out)}'
     if half:
         d.in_half, d.out_half, d.w_half = 1, int(out.dtype == torch.float16), cw.half().data_ptr()
         key = f'h{key}o{d.out_half}'
@@ -352,6 +354,14 @@ def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, 
     plan = conv_plan.choose(lib, d, key, plan, x.device, _PRECISION, cw.cout, cw.wu is not None, wino_ok, B * Ho * Wo,
                             lambda: _f4_operand(cw, d))
     d.plan_tile, d.plan_splitk = plan
+    return d, out, out_ld, key, plan, wino_ok
+
+
+def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half):
+    """One convolution of either path: `_conv_prep`, workspace, launch on the current stream, and the RECORD entry."""
+    lib = load()
+    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half)
+    B, Ho, Wo = x.shape[0], (x.shape[1] + 2 * cw.pad - cw.kh) // cw.stride + 1, (x.shape[2] + 2 * cw.pad - cw.kw) // cw.stride + 1
     need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
     ws = workspace(need, x.device, 'conv') if need else None
     launch = lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr())
@@ -417,6 +427,100 @@ def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False
         raise RuntimeError(f'conv2d: weight expects Cin={cw.cin}, got {cin}')
     ldin = in_ld if in_ld is not None else x.shape[3]
     return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False)
+
+
+# ---- shared Winograd transforms (include/xmem_hip.h: SHARED WINOGRAD TRANSFORMS) -------------------------------------------------
+# conv2d_shared: sibling convolutions of one tensor behind ONE input transform; conv2d_folded: a deferred sibling finished inside the
+# output transform of the convolution it is the residual of.  Both give the bits of the separate conv2d calls under the same plans,
+# and both fall back to exactly those calls where the library declines (a plan that is not F(4x4), the half / split modes) - and
+# while RECORD is on, so that bench.py's per-layer survey times every convolution as its own re-launchable call.
+SHARED_STATS = {'shared_input': 0, 'folded': 0, 'separate': 0}      # calls that took the shared kernels / calls issued one by one
+
+
+class DeferredConv:
+    """A convolution of `conv2d_shared` that stopped after its position GEMMs: its descriptor and its M, for `conv2d_folded`."""
+    __slots__ = ('d', 'm', 'm_bytes', 'shape', 'keep')
+
+    def __init__(self, d, m, m_bytes, shape, keep):
+        self.d, self.m, self.m_bytes, self.shape, self.keep = d, m, m_bytes, shape, keep
+
+    def finish(self):
+        """The convolution's own output transform (the fold did not apply) -> its output tensor."""
+        out = torch.empty(self.shape, dtype=torch.float32, device=self.m.device)
+        self.d.out, self.d.ldout = out.data_ptr(), self.shape[3]
+        check(load().xmem_conv2d_output_from_m(C.byref(self.d), ptr(self.m), self.m_bytes, stream_ptr()))
+        return out
+
+
+def conv2d_shared(x, convs, in_ld=None, cin=None, defer=None):
+    """x as for conv2d; convs: 2 or 3 dicts of conv2d's keyword arguments, each with its weights under 'cw' (3x3, stride 1, the same
+    Cin).  -> the list of outputs.  `defer` (an index): that convolution may stop after its GEMMs and come back as a DeferredConv
+    (which only `conv2d_folded` takes) instead of a tensor."""
+    _req(x, 'conv2d_shared input', half_ok=True)
+    separate = lambda: [conv2d(x, in_ld=in_ld, cin=cin, **kw) for kw in convs]
+    if x.dtype != torch.float32 or _PRECISION != 'fp32' or RECORD is not None or not 2 <= len(convs) <= _lib.CONV_SHARED_MAX \
+            or any(kw['cw'].dilation != 1 or kw.get('out_dtype') not in (None, torch.float32) for kw in convs):
+        SHARED_STATS['separate'] += 1
+        return separate()
+    lib = load()
+    ldin = in_ld if in_ld is not None else x.shape[3]
+    preps = []
+    for kw in convs:
+        cw = kw['cw']
+        c = cin if cin is not None else cw.cin
+        if c != cw.cin:
+            raise RuntimeError(f'conv2d_shared: weight expects Cin={cw.cin}, got {c}')
+        preps.append(_conv_prep(x, cw, c, ldin, kw.get('out'), kw.get('out_ld'), torch.float32, kw.get('res'), kw.get('relu_in', False),
+                                kw.get('relu_out', False), kw.get('res_broadcast', False), kw.get('plan'), False, alloc=False))
+    n = len(preps)
+    descs = (C.POINTER(ConvDesc) * n)(*[C.pointer(p[0]) for p in preps])
+    placeholder = x.data_ptr()           # the size query reads no `out`; a descriptor without one is invalid
+    for p in preps:
+        if p[1] is None:
+            p[0].out = placeholder
+    need = lib.xmem_conv2d_shared_input_workspace_bytes(descs, n)
+    if not need:
+        SHARED_STATS['separate'] += 1
+        return separate()
+    B, Ho, Wo = x.shape[0], x.shape[1], x.shape[2]
+    outs, m, m_bytes = [], None, 0
+    dm, dmb = (C.c_void_p * n)(), (C.c_size_t * n)()
+    for i, (d, out, out_ld, key, plan, wino_ok) in enumerate(preps):
+        if i == defer and out is None:
+            m_bytes = lib.xmem_conv2d_m_bytes(C.byref(d))
+            m = workspace(m_bytes, x.device, 'conv_m')       # a buffer of its own: the convolutions in between reuse 'conv'
+            dm[i], dmb[i] = m.data_ptr(), m_bytes
+            d.out = m.data_ptr()                             # never written
+            outs.append(DeferredConv(d, m, m_bytes, (B, Ho, Wo, convs[i]['cw'].cout), (x, convs[i]['cw'], convs[i].get('res'))))
+            continue
+        if out is None:
+            out = torch.empty((B, Ho, Wo, convs[i]['cw'].cout), dtype=torch.float32, device=x.device)
+            d.out = out.data_ptr()
+        outs.append(out)
+    ws = workspace(need, x.device, 'conv')
+    check(lib.xmem_conv2d_shared_input(descs, n, dm, dmb, ptr(ws), need, stream_ptr()))
+    SHARED_STATS['shared_input'] += 1
+    return outs
+
+
+def conv2d_folded(x, cw, branch, out=None, out_ld=None, relu_in=False, relu_out=False, plan=None):
+    """conv2d(x, cw, res=branch) where `branch` is what conv2d_shared returned for its `defer` convolution: a DeferredConv, whose output
+    transform is then formed inside this convolution's (one launch, the branch result never stored), or already a tensor."""
+    if not isinstance(branch, DeferredConv):
+        return conv2d(x, cw, out=out, out_ld=out_ld, res=branch, relu_in=relu_in, relu_out=relu_out, plan=plan)
+    lib = load()
+    _req(x, 'conv2d_folded input')
+    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cw.cin, x.shape[3], out, out_ld, torch.float32, None, relu_in, relu_out,
+                                                    False, plan, False, folded=True)
+    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
+    ws = workspace(need, x.device, 'conv') if need else None
+    rc = lib.xmem_conv2d_nhwc_folded(C.byref(d), C.byref(branch.d), ptr(branch.m), branch.m_bytes, ptr(ws), need, stream_ptr())
+    if rc == _lib.UNSUPPORTED:
+        SHARED_STATS['separate'] += 1
+        return conv2d(x, cw, out=out, out_ld=out_ld, res=branch.finish(), relu_in=relu_in, relu_out=relu_out, plan=plan)
+    check(rc)
+    SHARED_STATS['folded'] += 1
+    return out
 
 
 def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
