@@ -557,6 +557,42 @@ int xmem_rle_encode(const uint8_t* masks, int N, int H, int W, int K, int capaci
 int xmem_rle_decode(const int32_t* meta, const uint32_t* events, int N, int H, int W, int K, int capacity, const uint8_t* values,
                     uint8_t* masks, int32_t* status, void* stream);
 
+/* The compressed COCO string of every label of a record (the public mask API's rleToString): for the counts c[0 .. E] of a label with
+ * E >= 1 events (c[0] = e[0], c[i] = e[i] - e[i - 1], c[E] = H * W - e[E - 1]) the values x[i] = c[i] for i <= 2 and c[i] - c[i - 2]
+ * after that, each written as little-endian groups of 5 bits g, one character (g | (more ? 0x20 : 0)) + 48 per group, `more` until
+ * the bits that remain are the sign alone - characters '0'..'o' (backslash among them), 1 to 6 per value for H, W <= 16384.
+ * Input: meta [N][K][XMEM_RLE_META] and events [N][capacity] as xmem_rle_encode leaves them, on the device.
+ *   str_len int32 [N][K]: the TRUE length of each label's string (also when it did not fit); 0 for a label without event; -1 for every
+ *           label of a frame whose event counts sum to more than `capacity` (or hold a negative one): nothing of that frame is read,
+ *           it is to be encoded again.
+ *   chars   uint8 [N][char_capacity] per frame: the strings of label 1, 2, ... packed back to back.  Bytes at and beyond
+ *           `char_capacity` are not written: a frame whose lengths sum to more is to be compressed again with that sum.
+ * One thread owns one count (four neighbouring events); three launches (lengths, a per-frame exclusive scan in label-major order, emit),
+ * no inter-workgroup waiting and no atomics: the same input gives the same bytes.  K in [1, 254], capacity >= 1, char_capacity >= 1
+ * (else XMEM_ERR_BAD_ARG); H, W in [1, 16384], N <= 65535, capacity <= 2^28 (else XMEM_ERR_UNSUPPORTED).
+ * workspace: xmem_rle_compress_workspace_bytes(N, K, capacity) bytes (0 outside those ranges), 4-byte aligned. */
+size_t xmem_rle_compress_workspace_bytes(int N, int K, int capacity);
+int xmem_rle_compress(const int32_t* meta, const uint32_t* events, int N, int H, int W, int K, int capacity, int char_capacity,
+                      int32_t* str_len, uint8_t* chars, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The inverse (rleFrString): compressed strings -> the record xmem_rle_decode reads.  chars uint8 [chars_len] holds the strings of a
+ * batch; str_ofs int32 [N][K + 1] per frame: row k's string is chars[str_ofs[k], str_ofs[k + 1]), an empty range is a row without
+ * string (no events, status 0).
+ *   meta    int32 [N][K][XMEM_RLE_META]: field 0 the row's number of events (its number of counts - 1), the other fields 0.
+ *   events  uint32 [N][capacity] per frame: the rows' events (the running sums of the counts but the last) packed in row order.
+ *   status  int32 [N][K]: 0 good; 1 malformed (a character outside 48..111, a value of more than 6 characters, a string that ends
+ *           inside a value, offsets that are no range of chars); 2 not a plane (a negative count, a zero count after the first, a
+ *           sum other than H * W); 3 the frame's events exceed `capacity` (every string of that frame).  A row with a non-zero status
+ *           writes no event and has 0 events in meta; the other rows of its frame are packed as if it had no string.
+ * One workgroup per string: a value is assembled at its last character from at most 5 characters before it, its index is a rank, the
+ * counts two stride-2 running sums, the events the running sum of the counts, carried over chunks of the string.  Three launches
+ * (check, a per-frame scan of the rows' starts, expand).  Every read stays inside the row's range, every store index is a rank checked
+ * against `capacity`; no decoded value forms an address.  Argument ranges and error codes as xmem_rle_encode; chars_len >= 0.
+ * workspace: xmem_rle_decompress_workspace_bytes(N, K) bytes, 4-byte aligned. */
+size_t xmem_rle_decompress_workspace_bytes(int N, int K);
+int xmem_rle_decompress(const uint8_t* chars, int chars_len, const int32_t* str_ofs, int N, int H, int W, int K, int capacity,
+                        int32_t* meta, uint32_t* events, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* NHWC [B][P][C] (pixel stride ld) <-> NCHW [B][C][P] layout transposes for the Python surface */
 int xmem_nhwc_to_nchw(const float* in, int ld, float* out, int B, int P, int C, void* stream);
 int xmem_nchw_to_nhwc(const float* in, float* out, int ld, int B, int P, int C, void* stream);

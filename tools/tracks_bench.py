@@ -1,6 +1,6 @@
 """What the run-length track export (config['save_tracks'], ops.rle_encode) costs and what it sends to the host.
 
-    python tools/tracks_bench.py [--frames 60] [--runs 3] [--reps 200] [--out FILE]
+    python tools/tracks_bench.py [--frames 60] [--runs 3] [--reps 200] [--counts {list,compressed}] [--out FILE]
 
 1. The encode on its own: seeded label maps of K ragged ellipses at 480 x 854 and 1080 x 1920, K = 1 and 5; device events around
    `--reps` back-to-back `ops.rle_encode(map, K, wait=False)` calls (the three launches and two clears of one frame), nothing else
@@ -15,6 +15,10 @@
 4. `metrics.compute_metrics` on one synthetic 480 x 854 video of `--frames` frames whose predictions exist twice, as the palette
    PNGs `run_on_video` writes and as tracks.json: frames per second of the whole call from each, `--runs` runs alternating after a
    warm-up.  The PNG row is the parent commit's code path.
+5. `--counts compressed` (config['tracks_counts']): the compressed COCO strings next to the list form in the same run - parts 2 and 4
+   get a compressed row per tracks row (and both files' sizes), and part 5 times `ops.rle_compress` and `ops.rle_decompress` on their
+   own at the sizes of part 1 (three runs of `--reps` launch sequences each: median and spread) and prints the bytes of the record
+   that travels in both forms.
 `--only` picks parts.  No figure is asserted."""
 import argparse
 import os
@@ -27,8 +31,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
-MODES = (('save_masks only (parent)', True, False), ('neither (parent, save_masks=False)', False, False),
-         ('save_masks + save_tracks', True, True), ('save_tracks only', False, True))
+MODES = (('save_masks only (parent)', True, False, 'list'), ('neither (parent, save_masks=False)', False, False, 'list'),
+         ('save_masks + save_tracks', True, True, 'list'), ('save_tracks only', False, True, 'list'))
+COMPRESSED_MODES = (('save_masks + save_tracks, compressed', True, True, 'compressed'),
+                    ('save_tracks only, compressed', False, True, 'compressed'))
 
 
 def label_map(hw, k, seed=3, shift=0.0):
@@ -83,7 +89,46 @@ def write_clip(root, t, hw, k):
     return imgs, msks
 
 
-def video(emit, frames, runs):
+def strings_alone(emit, reps):
+    import statistics as st
+    import torch
+    from xmem2_amd import ops, rle
+    emit('\n5. ops.rle_compress / ops.rle_decompress on their own (us per frame: the three launches of each and the clear of the output; '
+         f'median of 3 runs of {reps} with the spread), from / to the device record of ops.rle_encode')
+    for hw in ((480, 854), (1080, 1920)):
+        for k in (1, 5):
+            dev = torch.from_numpy(label_map(hw, k)).cuda()
+            cap, ccap = rle.default_capacity(*hw), rle.default_char_capacity(*hw)
+            rec = ops.rle_encode(dev, k, cap, wait=False)
+            srec = ops.rle_compress(rec, *hw, k, cap, ccap, wait=False)
+            pair = ops.rle_string_offsets(srec, 1, k, ccap)
+
+            def timed(fn):
+                for _ in range(5):
+                    fn()
+                out = []
+                for _ in range(3):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    out.append(e0.elapsed_time(e1) * 1e3 / reps)
+                return f'{st.median(out):7.1f} us ({min(out):.1f} .. {max(out):.1f})'
+            comp = timed(lambda: ops.rle_compress(rec, *hw, k, cap, ccap, wait=False))
+            dec = timed(lambda: ops.rle_decompress(pair, *hw, k, cap, check=False))
+            back, status = ops.rle_decompress(pair, *hw, k, cap, check=False)
+            str_len, _ = rle.split_string_record(srec.cpu().numpy(), 1, k, ccap)
+            total = int(rec[:k * rle.META].view(k, rle.META)[:, 0].sum())
+            exact = bool(not status.any() and torch.equal(back[k * rle.META:k * rle.META + total], rec[k * rle.META:k * rle.META + total]))
+            listed, sent, used = 4 * (k * rle.META + cap), 4 * k * (rle.META + 1) + ccap, 4 * k * (rle.META + 1) + int(str_len.sum())
+            emit(f'   {hw[0]:4d} x {hw[1]:4d}, K = {k}: compress {comp};  decompress {dec};  events back exactly: {exact};  {total} events, '
+                 f'{int(str_len.sum())} characters;  record per frame: list {listed} B (used {4 * (k * rle.META + total)} B), compressed '
+                 f'{sent} B (used {used} B)')
+
+
+def video(emit, frames, runs, counts='list'):
     import torch
     from session_bench import save_checkpoint
     from xmem2_amd.network import XMem
@@ -94,36 +139,56 @@ def video(emit, frames, runs):
         net = XMem({'model': model, 'size': 480}, model).to('cuda').eval()
         imgs, msks = write_clip(os.path.join(tmp, 'clip'), frames, hw, 1)
 
-        def run(tag, masks, tracks, n):
+        modes = MODES + (COMPRESSED_MODES if counts == 'compressed' else ())
+
+        def run(tag, masks, tracks, n, form='list'):
             out = os.path.join(tmp, f'out_{n}')
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             run_on_video(imgs, msks, out, frames_with_masks=[0], print_progress=False, save_overlay=False, network=net,
-                         overwrite_config={'model': model, 'size': 480, 'save_masks': masks, 'save_tracks': tracks})
+                         overwrite_config={'model': model, 'size': 480, 'save_masks': masks, 'save_tracks': tracks, 'tracks_counts': form})
             torch.cuda.synchronize()
+            if tracks:
+                written[form] = os.path.join(out, 'tracks.json')
             return frames / (time.perf_counter() - t0)
+        written = {}
         from xmem2_amd import ops
         run('warm-up', True, True, 0)
-        before = dict(ops.RLE_STATS)
-        fps = {tag: [] for tag, _, _ in MODES}
+        if counts == 'compressed':
+            run('warm-up', True, True, 0, 'compressed')
+        before, before_strings = dict(ops.RLE_STATS), dict(ops.RLE_STRING_STATS)
+        fps = {tag: [] for tag, _, _, _ in modes}
         n = 1
         for _ in range(runs):
-            for tag, masks, tracks in MODES:
-                fps[tag].append(run(tag, masks, tracks, n))
+            for tag, masks, tracks, form in modes:
+                fps[tag].append(run(tag, masks, tracks, n, form))
                 n += 1
         emit(f'\n2. run_on_video on files, {frames} JPEG frames of {hw[0]} x {hw[1]}, one object, one reference; frames per second of the '
              f'whole call, {runs} runs per mode alternating')
-        for tag, _, _ in MODES:
+        for tag, _, _, _ in modes:
             emit(f'   {tag:36s} ' + ' '.join(f'{v:7.1f}' for v in fps[tag]) + f'   median {statistics.median(fps[tag]):7.1f}')
         import json
-        path = os.path.join(tmp, f'out_{n - 1}', 'tracks.json')
+        path = written['list']
         doc = json.load(open(path))
         per_frame = [len(s['counts']) - 1 for a in doc['annotations'] for s in a['segmentations'] if s is not None]
         emit(f'   tracks.json of the clip: {os.path.getsize(path)} bytes; events per frame of the PREDICTED masks (synthetic weights: ragged): '
              f'min {min(per_frame)}, median {int(statistics.median(per_frame))}, max {max(per_frame)}; default capacity '
              f'{__import__("xmem2_amd.rle", fromlist=["rle"]).default_capacity(*hw)}')
-        emit(f'   encode calls in the timed runs: {ops.RLE_STATS["launches"] - before["launches"]} for {2 * runs * frames} frames; frames '
+        emit(f'   encode calls in the timed runs: {ops.RLE_STATS["launches"] - before["launches"]} for '
+             f'{sum(t for _, _, t, _ in modes) * runs * frames} frames; frames '
              f'encoded again because their events did not fit: {ops.RLE_STATS["retries"] - before["retries"]}')
+        if counts == 'compressed':
+            text = open(written['compressed']).read()
+            same = json.loads(open(path).read()) == __import__('xmem2_amd.rle', fromlist=['rle']).recode_tracks(json.loads(text), 'list')
+            emit(f'   tracks.json with compressed counts: {len(text)} bytes against {os.path.getsize(path)} as lists; recoded to lists it is '
+                 f'the list file: {same}; compress calls in the timed runs: '
+                 f'{ops.RLE_STRING_STATS["launches"] - before_strings["launches"]}; frames compressed again because their characters did '
+                 f'not fit: {ops.RLE_STRING_STATS["retries"] - before_strings["retries"]}')
+            for a, b in (('save_masks + save_tracks', 'save_masks + save_tracks, compressed'), ('save_tracks only', 'save_tracks only, compressed')):
+                spread = max(max(fps[t]) - min(fps[t]) for t in (a, b))
+                diff = statistics.median(fps[b]) - statistics.median(fps[a])
+                emit(f'   {b}: {diff:+.1f} frames/s against the list form, the spread of the runs is {spread:.1f}: '
+                     + ('SLOWER than the list form by more than the spread' if diff < -spread else 'within the spread or faster'))
 
 
 def decode_alone(emit, reps):
@@ -148,7 +213,7 @@ def decode_alone(emit, reps):
             emit(f'   {hw[0]:4d} x {hw[1]:4d}, K = {k}: {e0.elapsed_time(e1) * 1e3 / reps:7.1f} us;  equal to the encoded map: {exact}')
 
 
-def evaluate(emit, frames, runs):
+def evaluate(emit, frames, runs, counts='list'):
     import torch
     from PIL import Image
     from xmem2_amd.metrics import compute_metrics
@@ -156,9 +221,9 @@ def evaluate(emit, frames, runs):
     hw = (480, 854)
     pal = [0, 0, 0, 200, 0, 0, 0, 200, 0, 0, 0, 200] + [0] * (256 * 3 - 12)
     with tempfile.TemporaryDirectory() as tmp:
-        gt, png, trk = (os.path.join(tmp, d, 'clip') for d in ('gt', 'png', 'tracks'))
+        gt, png, trk, ctrk = (os.path.join(tmp, d, 'clip') for d in ('gt', 'png', 'tracks', 'ctracks'))
         os.makedirs(gt); os.makedirs(os.path.join(png, 'masks')); os.makedirs(trk)
-        writer = TrackWriter(*hw)
+        writer, cwriter = TrackWriter(*hw), TrackWriter(*hw)
         for i in range(frames):
             truth = label_map(hw, 1, shift=1.5 * i - 0.75 * frames)
             pred = label_map(hw, 1, seed=4, shift=1.5 * i - 0.75 * frames + 3)
@@ -167,10 +232,15 @@ def evaluate(emit, frames, runs):
                 im.putpalette(pal)
                 im.save(os.path.join(d, f'{i:05d}.png'), compress_level=1)       # as the writers of run_on_video save them
             writer.add_mask(f'{i:05d}.png', pred)
+            if counts == 'compressed':
+                cwriter.add_mask(f'{i:05d}.png', pred, counts='compressed')
         writer.write(trk)
         frames_of = {'from PNGs (parent)': os.path.join(tmp, 'png'), 'from tracks.json': os.path.join(tmp, 'tracks')}
+        if counts == 'compressed':
+            cwriter.write(ctrk)
+            frames_of['from tracks.json, compressed'] = os.path.join(tmp, 'ctracks')
         tables = {tag: compute_metrics(os.path.join(tmp, 'gt'), d) for tag, d in frames_of.items()}      # warm-up, and the check
-        same = tables['from PNGs (parent)'].equals(tables['from tracks.json'])
+        same = all(t.equals(tables['from PNGs (parent)']) for t in tables.values())
         fps = {tag: [] for tag in frames_of}
         for _ in range(runs):
             for tag, d in frames_of.items():
@@ -179,11 +249,13 @@ def evaluate(emit, frames, runs):
                 compute_metrics(os.path.join(tmp, 'gt'), d)
                 fps[tag].append(frames / (time.perf_counter() - t0))
         emit(f'\n4. metrics.compute_metrics, one video of {frames} frames of {hw[0]} x {hw[1]}, one object, ground truth from PNGs (8 decode '
-             f'threads); frames per second of the whole call, {runs} runs per source alternating; the two tables are equal: {same}')
+             f'threads); frames per second of the whole call, {runs} runs per source alternating; the tables are equal: {same}')
         for tag in frames_of:
             emit(f'   {tag:36s} ' + ' '.join(f'{v:7.1f}' for v in fps[tag]) + f'   median {statistics.median(fps[tag]):7.1f}')
         emit(f'   tracks.json: {os.path.getsize(os.path.join(trk, "tracks.json"))} bytes; the prediction PNGs: '
              f'{sum(os.path.getsize(os.path.join(png, "masks", f)) for f in os.listdir(os.path.join(png, "masks")))} bytes')
+        if counts == 'compressed':
+            emit(f'   tracks.json with compressed counts: {os.path.getsize(os.path.join(ctrk, "tracks.json"))} bytes')
 
 
 def main():
@@ -192,7 +264,10 @@ def main():
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--reps', type=int, default=200)
     ap.add_argument('--out', default=None, help='also append the report to this file')
-    ap.add_argument('--only', default='encode,video,decode,evaluate', help='comma-separated parts: encode, video, decode, evaluate')
+    ap.add_argument('--counts', default='list', choices=('list', 'compressed'),
+                    help="compressed: config['tracks_counts'] = 'compressed' next to the list form in parts 2 and 4, and part 5")
+    ap.add_argument('--only', default='encode,video,decode,evaluate,strings',
+                    help='comma-separated parts: encode, video, decode, evaluate, strings (the last with --counts compressed)')
     args = ap.parse_args()
     import torch
     torch.set_grad_enabled(False)
@@ -208,11 +283,13 @@ def main():
     if 'encode' in parts:
         encode_alone(emit, args.reps)
     if 'video' in parts:
-        video(emit, args.frames, args.runs)
+        video(emit, args.frames, args.runs, args.counts)
     if 'decode' in parts:
         decode_alone(emit, args.reps)
     if 'evaluate' in parts:
-        evaluate(emit, args.frames, args.runs)
+        evaluate(emit, args.frames, args.runs, args.counts)
+    if 'strings' in parts and args.counts == 'compressed':
+        strings_alone(emit, args.reps)
 
 
 if __name__ == '__main__':

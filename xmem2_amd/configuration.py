@@ -25,4 +25,5 @@ VIDEO_INFERENCE_CONFIG = {
     'workspace': None,
     'save_masks': True,
     'save_tracks': False,       # not in the reference: write <masks_out_path>/tracks.json, run-length tracks encoded on the device (rle.py)
+    'tracks_counts': 'list',    # the counts in tracks.json: 'list' (uncompressed) | 'compressed' (the COCO string, built on the device)
 }

@@ -15,6 +15,7 @@
 //          in the frame's packed event list; the per-label totals and the finished boxes go to `meta`;
 //   emit   the same walk, writing each event at its scanned position (below `capacity`).
 // No workgroup waits for another, no float arithmetic, and no output position depends on the order in which atomics arrive.
+// Further down: the compressed COCO strings of a record and back (xmem_rle_compress / xmem_rle_decompress).
 #include "common.hpp"
 
 #define RLE_MAX_HW 16384
@@ -301,5 +302,346 @@ extern "C" int xmem_rle_decode(const int32_t* meta, const uint32_t* events, int 
     const dim3 grid(cdiv(W, XMEM_WAVE * RLE_DEC_COLS), cdiv(H, RLE_DEC_WAVES * RLE_DEC_ROWS), N), block(RLE_DEC_WAVES * XMEM_WAVE);
     hipLaunchKernelGGL(rle_decode_kernel, grid, block, 0, (hipStream_t)stream, (const int*)meta, events, H, W, K, capacity, values,
                        dword_ok, masks, (int*)status);
+    return xmem_check_launch();
+}
+
+// ---- compressed COCO strings (include/xmem_hip.h, xmem_rle_compress / xmem_rle_decompress) --------------------------------------
+// The string of a label is a function of its counts c[i] = e[i] - e[i - 1] (e[-1] = 0, e[E] = H * W): the value x[i] = c[i] for
+// i <= 2 and c[i] - c[i - 2] after that, written as little-endian groups of 5 bits with a continuation bit (0x20), characters offset
+// by 48.  Compress: one thread owns one count - four neighbouring events, a length 1..6 - and the same three steps as the encoder:
+//   lengths  the length of every value into the workspace [N][capacity + K], the frame's values label-major;
+//   scan     one workgroup per frame: exclusive scan - the position of every value's first character; per-label lengths to str_len;
+//   emit     the value again, its characters at the scanned position (below `char_capacity`).
+// Decompress: one workgroup per string walks it in chunks of RLE_STR_THREADS characters.  A thread whose character ends a value (bit
+// 0x20 clear) assembles it from at most 5 characters before it; the value's index is the rank of its last character (a scan), the
+// counts are two stride-2 running sums of the values, the events the running sum of the counts - three block scans per chunk with the
+// sums carried from chunk to chunk.  Again three steps:
+//   check    the walk without stores: malformed / not a plane / the number of values, per string;
+//   scan     one workgroup per frame: the rows' starts in the frame's packed event list, `meta`, capacity overflow;
+//   expand   the walk again for the good rows, event i at start + i (below `capacity`).
+// The index of a store is always a rank or a scanned length, never a decoded value.  No workgroup waits for another, no atomics on
+// global memory: the same input gives the same bytes.
+#define RLE_STR_THREADS 256
+#define RLE_STR_WAVES (RLE_STR_THREADS / XMEM_WAVE)
+#define RLE_STR_MAX_GROUPS 6       // characters of a value the reader accepts: 30 bits
+#define RLE_STR_MAX_CAPACITY (1 << 28)
+
+namespace {
+
+// Inclusive scan of one int per thread over the workgroup; `part` holds one word per wave, `total` is the workgroup's sum.  Two
+// barriers: part may be reused right after the call.
+template <typename T>
+__device__ __forceinline__ T rle_block_scan(T v, T* part, T& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    T incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) part[wave] = incl;
+    __syncthreads();
+    T before = 0, sum = 0;
+    for (int w = 0; w < waves; ++w) {
+        const T t = part[w];
+        if (w < wave) before += t;
+        sum += t;
+    }
+    __syncthreads();
+    total = sum;
+    return incl + before;
+}
+
+// The frame's labels for the compressor: s_ev[k] = start of label k in the packed events, s_val[k] = start of its values (a label
+// with E >= 1 events has E + 1 values, a label without event none), both with a closing entry [K].  Returns false - for every
+// thread - when a count is negative or the events did not fit `capacity`: nothing of the frame may be read then.
+__device__ __forceinline__ bool rle_label_starts(const int* __restrict__ mt, int K, int capacity, int* s_ev, int* s_val, int* s_ok) {
+    if (threadIdx.x == 0) {
+        int ev = 0, val = 0, ok = 1;
+        for (int k = 0; k < K; ++k) {
+            const int e = mt[(size_t)k * XMEM_RLE_META];
+            s_ev[k] = ev;
+            s_val[k] = val;
+            if (e < 0 || e > capacity - ev) { ok = 0; break; }
+            ev += e;
+            val += e > 0 ? e + 1 : 0;
+        }
+        s_ev[K] = ev;
+        s_val[K] = val;
+        *s_ok = ok;
+    }
+    __syncthreads();
+    return *s_ok != 0;
+}
+
+// Value t of the frame: its label by binary search in s_val, then x from at most four events.  Unsigned arithmetic: a record that is
+// no encoder's (events not ascending) wraps instead of overflowing, and still gives a string of the length the scan counted.
+__device__ __forceinline__ int rle_value(const uint32_t* __restrict__ ev_frame, const int* s_ev, const int* s_val, int K, int t,
+                                         uint32_t hw) {
+    int lo = 0, hi = K - 1;                              // the last k with s_val[k] <= t among labels that have values
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_val[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    const int i = t - s_val[lo], E = s_ev[lo + 1] - s_ev[lo];        // count i of 0..E; E >= 1 because the label has values
+    const uint32_t* e = ev_frame + s_ev[lo];                         // e[0 .. E) lies below `capacity`
+    const uint32_t hi_i = i < E ? e[i] : hw, lo_i = i > 0 ? e[i - 1] : 0u;
+    uint32_t x = hi_i - lo_i;
+    if (i > 2) x -= e[i - 2] - e[i - 3];                             // c[i - 2]; i - 2 <= E - 1
+    return (int)x;
+}
+
+// the characters of x, at most 7 for any int; returns their number
+__device__ __forceinline__ int rle_value_chars(int x, uint8_t (&out)[7]) {
+    int n = 0;
+    bool more = true;
+#pragma unroll
+    for (int g = 0; g < 7; ++g) {                        // static indices: the characters stay in registers
+        const int c = x & 0x1f;
+        x >>= 5;                                         // arithmetic
+        const bool next = (c & 0x10) ? (x != -1) : (x != 0);
+        out[g] = (uint8_t)((c | (next ? 0x20 : 0)) + 48);
+        if (more) n = g + 1;
+        more = more && next;
+    }
+    return n;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(RLE_STR_THREADS) void rle_compress_kernel(const int* __restrict__ meta, const uint32_t* __restrict__ events,
+                                                                      int H, int W, int K, int capacity, int char_capacity,
+                                                                      int* __restrict__ ofs, uint8_t* __restrict__ chars) {
+    __shared__ int s_ev[256], s_val[256], s_ok;
+    const int n = blockIdx.y, t = blockIdx.x * RLE_STR_THREADS + threadIdx.x;
+    if (!rle_label_starts(meta + (size_t)n * K * XMEM_RLE_META, K, capacity, s_ev, s_val, &s_ok)) return;
+    if (t >= s_val[K]) return;
+    uint8_t c[7];
+    const int len = rle_value_chars(rle_value(events + (size_t)n * capacity, s_ev, s_val, K, t, (uint32_t)H * (uint32_t)W), c);
+    int* slot = ofs + (size_t)n * (capacity + K) + t;
+    if (!EMIT) {
+        *slot = len;
+    } else {
+        const int at = *slot;
+        uint8_t* out = chars + (size_t)n * char_capacity;
+#pragma unroll
+        for (int g = 0; g < 7; ++g)
+            if (g < len && at + g < char_capacity) out[at + g] = c[g];
+    }
+}
+
+__global__ __launch_bounds__(RLE_SCAN_THREADS) void rle_compress_scan_kernel(const int* __restrict__ meta, int K, int capacity,
+                                                                            int* __restrict__ ofs, int* __restrict__ str_len) {
+    __shared__ int s_part[RLE_SCAN_THREADS / XMEM_WAVE];
+    __shared__ int s_ev[256], s_val[256], s_start[256], s_ok;
+    const int n = blockIdx.x, tid = threadIdx.x;
+    if (!rle_label_starts(meta + (size_t)n * K * XMEM_RLE_META, K, capacity, s_ev, s_val, &s_ok)) {
+        if (tid < K) str_len[(size_t)n * K + tid] = -1;
+        return;
+    }
+    int* c = ofs + (size_t)n * (capacity + K);
+    const int M = s_val[K];
+    int carry = 0;
+    for (int base = 0; base < M; base += RLE_SCAN_THREADS) {         // uniform over the workgroup
+        const int i = base + tid;
+        const int v = i < M ? c[i] : 0;
+        int total;
+        const int excl = carry + rle_block_scan(v, s_part, total) - v;
+        if (i < M) c[i] = excl;
+        carry += total;
+    }
+    __syncthreads();
+    // the first character of label k: the scanned position of its first value (the frame's total where no value follows)
+    if (tid <= K) s_start[tid] = s_val[tid] < M ? c[s_val[tid]] : carry;
+    __syncthreads();
+    if (tid < K) str_len[(size_t)n * K + tid] = s_start[tid + 1] - s_start[tid];
+}
+
+// One string, [begin, end) of `chars`.  EMIT = false: -> s_res = {status, number of values}.  EMIT = true: events[i] for i < m - 1.
+template <bool EMIT>
+__device__ __forceinline__ void rle_string_walk(const uint8_t* __restrict__ chars, int begin, int end, long long hw, int m,
+                                                uint32_t* __restrict__ ev_row, int room, int* s_res) {
+    __shared__ long long s_part[2 * RLE_STR_WAVES];
+    __shared__ int s_ipart[RLE_STR_WAVES];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    int rank0 = 0;                                       // values before this chunk
+    long long even = 0, odd = 0, pos = 0;                // c[i - 2] for the next even / odd i, and the position, carried
+    for (int base = begin; base < end; base += RLE_STR_THREADS) {    // uniform over the workgroup
+        const int p = base + tid;
+        int c = 0x20, bad = 0;                           // beyond the end: neither a value's last character nor a fault
+        if (p < end) {
+            c = (int)chars[p] - 48;
+            if (c < 0 || c > 63) { bad |= 1; c = 0x20; }
+            if (p == end - 1 && (c & 0x20)) bad |= 1;    // the string ends inside a value
+        }
+        const bool term = !(c & 0x20);
+        int x = 0;
+        if (term) {
+            uint32_t u = (uint32_t)(c & 0x1f);
+            if (c & 0x10) u |= 0xffffffe0u;              // the last group carries the sign
+            int back = 1;
+            for (; back < RLE_STR_MAX_GROUPS && p - back >= begin; ++back) {
+                const int d = (int)chars[p - back] - 48; // inside [begin, end); a character outside 48..111 is reported by its owner
+                if (d < 0 || d > 63 || !(d & 0x20)) break;
+                u = (u << 5) | (uint32_t)(d & 0x1f);
+            }
+            if (back == RLE_STR_MAX_GROUPS && p - back >= begin) {   // a seventh character of the same value
+                const int d = (int)chars[p - back] - 48;
+                if (d >= 0 && d <= 63 && (d & 0x20)) bad |= 1;
+            }
+            x = (int)u;
+        }
+        int nterm;
+        const int i = rank0 + rle_block_scan(term ? 1 : 0, s_ipart, nterm) - 1;      // this value's index, where term
+        const bool ev = term && i >= 2 && !(i & 1), od = term && (i & 1);
+        long long te, to, tc;
+        const long long se = rle_block_scan<long long>(ev ? x : 0, s_part, te);
+        const long long so = rle_block_scan<long long>(od ? x : 0, s_part + RLE_STR_WAVES, to);
+        long long cnt = 0;
+        if (term) {
+            cnt = i == 0 ? (long long)x : (i & 1) ? odd + so : even + se;
+            if (cnt < 0 || (i > 0 && cnt == 0)) bad |= 2;
+        }
+        const long long at = pos + rle_block_scan<long long>(cnt, s_part, tc);        // the end of count i: event i
+        if (EMIT) {
+            if (term && i < m - 1 && i < room) ev_row[i] = (uint32_t)at;
+        } else if (bad) {
+            atomicOr(&s_bad, bad);
+        }
+        rank0 += nterm;
+        even += te;
+        odd += to;
+        pos += tc;
+    }
+    if (!EMIT) {
+        __syncthreads();
+        if (tid == 0) {
+            const int bad = s_bad;
+            const int status = (bad & 1) ? 1 : ((bad & 2) || pos != hw) ? 2 : 0;
+            s_res[0] = status;
+            s_res[1] = status == 0 ? rank0 : 0;
+        }
+    }
+}
+
+// a row's range of `chars`: false when the offsets do not describe one (status 1); an empty range is a row without string
+__device__ __forceinline__ bool rle_row_range(const int* __restrict__ str_ofs, int row_in_table, int chars_len, int& begin, int& end) {
+    begin = str_ofs[row_in_table];
+    end = str_ofs[row_in_table + 1];
+    return begin >= 0 && begin <= end && end <= chars_len;
+}
+
+// workspace of the reader: int32 [N][K][2] = {number of values (0: no events to write), the row's start in the frame's events}
+__global__ __launch_bounds__(RLE_STR_THREADS) void rle_decompress_check_kernel(const uint8_t* __restrict__ chars, int chars_len,
+                                                                              const int* __restrict__ str_ofs, int H, int W, int K,
+                                                                              int* __restrict__ ws, int* __restrict__ status) {
+    __shared__ int s_res[2];
+    const int k = blockIdx.x, n = blockIdx.y;
+    const size_t row = (size_t)n * K + k;
+    int begin, end;
+    const bool ok = rle_row_range(str_ofs, n * (K + 1) + k, chars_len, begin, end);
+    if (!ok || begin == end) {                           // uniform over the workgroup
+        if (threadIdx.x == 0) {
+            status[row] = ok ? 0 : 1;
+            ws[2 * row] = 0;
+        }
+        return;
+    }
+    rle_string_walk<false>(chars, begin, end, (long long)H * W, 0, nullptr, 0, s_res);
+    if (threadIdx.x == 0) {
+        status[row] = s_res[0];
+        ws[2 * row] = s_res[1];
+    }
+}
+
+__global__ __launch_bounds__(256) void rle_decompress_scan_kernel(int K, int capacity, int* __restrict__ ws, int* __restrict__ meta,
+                                                                  int* __restrict__ status) {
+    __shared__ int s_part[4];
+    const int n = blockIdx.x, k = threadIdx.x;
+    const size_t row = (size_t)n * K + k;
+    const int m = k < K ? ws[2 * row] : 0;               // K <= 254: one row per thread
+    const int e = m > 1 ? m - 1 : 0;
+    int total;
+    const int start = rle_block_scan(e, s_part, total) - e;
+    if (k >= K) return;
+    const bool fits = total <= capacity;
+    if (!fits && m > 0) status[row] = 3;                 // every good string of the frame: the frame is to be read again with more room
+    ws[2 * row] = fits ? m : 0;
+    ws[2 * row + 1] = start;
+    int* mt = meta + row * XMEM_RLE_META;
+    mt[0] = fits ? e : 0;
+#pragma unroll
+    for (int f = 1; f < XMEM_RLE_META; ++f) mt[f] = 0;
+}
+
+__global__ __launch_bounds__(RLE_STR_THREADS) void rle_decompress_expand_kernel(const uint8_t* __restrict__ chars, int chars_len,
+                                                                               const int* __restrict__ str_ofs, int H, int W, int K,
+                                                                               int capacity, const int* __restrict__ ws,
+                                                                               uint32_t* __restrict__ events) {
+    const int k = blockIdx.x, n = blockIdx.y;
+    const size_t row = (size_t)n * K + k;
+    const int m = ws[2 * row], start = ws[2 * row + 1];
+    int begin, end;
+    if (m < 2 || !rle_row_range(str_ofs, n * (K + 1) + k, chars_len, begin, end)) return;     // uniform over the workgroup
+    if (start < 0 || start >= capacity) return;
+    rle_string_walk<true>(chars, begin, end, (long long)H * W, m, events + (size_t)n * capacity + start, capacity - start, nullptr);
+}
+
+}  // namespace
+
+extern "C" size_t xmem_rle_compress_workspace_bytes(int N, int K, int capacity) {
+    if (!rle_args_ok(N, 1, K) || !rle_size_ok(N, 1, 1) || capacity < 1 || capacity > RLE_STR_MAX_CAPACITY) return 0;
+    return (size_t)N * ((size_t)capacity + K) * sizeof(int32_t);
+}
+
+extern "C" int xmem_rle_compress(const int32_t* meta, const uint32_t* events, int N, int H, int W, int K, int capacity,
+                                 int char_capacity, int32_t* str_len, uint8_t* chars, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    if (!meta || !events || !str_len || !chars || !workspace || H <= 0 || capacity < 1 || char_capacity < 1 || !rle_args_ok(N, W, K))
+        return XMEM_ERR_BAD_ARG;
+    if (!rle_size_ok(N, H, W) || capacity > RLE_STR_MAX_CAPACITY) return XMEM_ERR_UNSUPPORTED;
+    if (workspace_bytes < xmem_rle_compress_workspace_bytes(N, K, capacity) || ((uintptr_t)workspace & 3)) return XMEM_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    int* ofs = (int*)workspace;
+    const dim3 grid(cdiv(capacity + K, RLE_STR_THREADS), N), block(RLE_STR_THREADS);
+    hipLaunchKernelGGL(rle_compress_kernel<false>, grid, block, 0, s, (const int*)meta, events, H, W, K, capacity, char_capacity, ofs,
+                       chars);
+    int rc = xmem_check_launch();
+    if (rc != XMEM_OK) return rc;
+    hipLaunchKernelGGL(rle_compress_scan_kernel, dim3(N), dim3(RLE_SCAN_THREADS), 0, s, (const int*)meta, K, capacity, ofs,
+                       (int*)str_len);
+    rc = xmem_check_launch();
+    if (rc != XMEM_OK) return rc;
+    hipLaunchKernelGGL(rle_compress_kernel<true>, grid, block, 0, s, (const int*)meta, events, H, W, K, capacity, char_capacity, ofs,
+                       chars);
+    return xmem_check_launch();
+}
+
+extern "C" size_t xmem_rle_decompress_workspace_bytes(int N, int K) {
+    if (!rle_args_ok(N, 1, K) || !rle_size_ok(N, 1, 1)) return 0;
+    return (size_t)N * K * 2 * sizeof(int32_t);
+}
+
+extern "C" int xmem_rle_decompress(const uint8_t* chars, int chars_len, const int32_t* str_ofs, int N, int H, int W, int K,
+                                   int capacity, int32_t* meta, uint32_t* events, int32_t* status, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    if (!chars || !str_ofs || !meta || !events || !status || !workspace || H <= 0 || capacity < 1 || chars_len < 0 ||
+        !rle_args_ok(N, W, K))
+        return XMEM_ERR_BAD_ARG;
+    if (!rle_size_ok(N, H, W)) return XMEM_ERR_UNSUPPORTED;
+    if (workspace_bytes < xmem_rle_decompress_workspace_bytes(N, K) || ((uintptr_t)workspace & 3)) return XMEM_ERR_WORKSPACE;
+    const hipStream_t s = (hipStream_t)stream;
+    int* ws = (int*)workspace;
+    const dim3 grid(K, N), block(RLE_STR_THREADS);
+    hipLaunchKernelGGL(rle_decompress_check_kernel, grid, block, 0, s, chars, chars_len, (const int*)str_ofs, H, W, K, ws, (int*)status);
+    int rc = xmem_check_launch();
+    if (rc != XMEM_OK) return rc;
+    hipLaunchKernelGGL(rle_decompress_scan_kernel, dim3(N), dim3(256), 0, s, K, capacity, ws, (int*)meta, (int*)status);
+    rc = xmem_check_launch();
+    if (rc != XMEM_OK) return rc;
+    hipLaunchKernelGGL(rle_decompress_expand_kernel, grid, block, 0, s, chars, chars_len, (const int*)str_ofs, H, W, K, capacity,
+                       (const int*)ws, events);
     return xmem_check_launch();
 }

@@ -1399,6 +1399,7 @@ def next_click(d2, not_clicked, counts=None, record=None):
 # ---- run-length track export (csrc/rle.hip): integer arithmetic, bit-reproducible -------------------------------------
 
 RLE_STATS = {'launches': 0, 'retries': 0}      # calls of xmem_rle_encode / frames encoded again because their events did not fit
+RLE_STRING_STATS = {'launches': 0, 'retries': 0}       # calls of xmem_rle_compress / frames compressed again: their characters did not fit
 
 
 def rle_encode(masks, K, capacity=None, wait=True):
@@ -1515,6 +1516,156 @@ def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True
     if bad:
         raise RuntimeError(f'rle_decode: the events of frame(s) {bad} do not fit the capacity {capacity}')
     return out
+
+
+def _rle_int(name, v, low, top, fn):
+    import numpy as np
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (low <= v <= top):
+        raise ValueError(f'{fn}: {name} = {v!r} must be an integer in {low}..{top}')
+    return int(v)
+
+
+def rle_compress(record, H, W, K, capacity, char_capacity=None, wait=True):
+    """The compressed COCO strings (`rle.compress_counts` is the definition) of a record: `record` is the int32 device tensor
+    `rle_encode(..., wait=False)` returns, `capacity` the one it was encoded with, `char_capacity` the bytes per frame there is room
+    for (default `rle.default_char_capacity`).  wait=False: one launch sequence on the current stream and no synchronisation; returns
+    the uint8 device tensor [B * K int32 string lengths | B * char_capacity characters] that `rle.split_string_record(., B, K,
+    char_capacity)` takes apart - the lengths are the true ones, -1 in a frame whose EVENTS did not fit `capacity`.  wait=True: returns
+    a list of B lists of K str on the HOST ('' for a label without event); a frame whose characters did not fit is compressed again
+    with exactly its size; a frame whose events did not fit the record is None - only the masks can be encoded again."""
+    from . import rle
+    H, W, K = (_rle_int(n, v, 1, top, 'rle_compress') for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
+    capacity = _rle_int('capacity', capacity, 1, 1 << 28, 'rle_compress')
+    if not torch.is_tensor(record) or not record.is_cuda or record.dtype != torch.int32 or record.dim() != 1 or not record.is_contiguous():
+        raise RuntimeError('record: expected the contiguous int32 CUDA (HIP) tensor of rle_encode(wait=False) - xmem2_amd has no CPU path')
+    per_frame = K * rle.META + capacity
+    B = record.numel() // per_frame
+    if B < 1 or B * per_frame != record.numel():
+        raise ValueError(f'rle_compress: a record of {record.numel()} words is not a whole number of frames of K = {K}, capacity = {capacity}')
+    if B > 65535:
+        raise ValueError(f'rle_compress: {B} frames in one launch, at most 65535')
+    char_capacity = rle.default_char_capacity(H, W, capacity) if char_capacity is None \
+        else _rle_int('char_capacity', char_capacity, 1, (1 << 31) - 1, 'rle_compress')
+    lib = load()
+    out = torch.zeros(4 * B * K + B * char_capacity, dtype=torch.uint8, device=record.device)
+    ws = workspace(max(lib.xmem_rle_compress_workspace_bytes(B, K, capacity), 4), record.device, 'rle')
+    RLE_STRING_STATS['launches'] += 1
+    check(lib.xmem_rle_compress(ptr(record), C.c_void_p(record.data_ptr() + 4 * B * K * rle.META), B, H, W, K, capacity, char_capacity,
+                                ptr(out), C.c_void_p(out.data_ptr() + 4 * B * K), ptr(ws), ws.numel(), stream_ptr()))
+    if not wait:
+        return out
+    str_len, chars = rle.split_string_record(out.cpu().numpy(), B, K, char_capacity)
+    strings = []
+    for b in range(B):
+        if (str_len[b] < 0).any():
+            strings.append(None)
+            continue
+        total = int(str_len[b].sum())
+        if total > char_capacity:                                 # the lengths are the true ones: once more, with room for all of them
+            RLE_STRING_STATS['retries'] += 1
+            meta_b = record[b * K * rle.META:(b + 1) * K * rle.META]
+            ev_b = record[B * K * rle.META + b * capacity:B * K * rle.META + (b + 1) * capacity]
+            again = rle_compress(torch.cat([meta_b, ev_b]), H, W, K, capacity, char_capacity=total)[0]
+            if [len(v) for v in again] != str_len[b].tolist():
+                raise RuntimeError('rle_compress: a frame compressed again gave other lengths')
+            strings.append(again)
+        else:
+            strings.append(rle.label_strings(str_len[b], chars[b]))
+    return strings
+
+
+def rle_string_offsets(string_record, B, K, char_capacity):
+    """The device pair (chars, str_ofs int32 [B, K + 1]) `rle_decompress` takes, from the tensor `rle_compress(..., wait=False)` returned:
+    a cumulative sum of the lengths on the device, no host step.  A frame with lengths of -1 (its events did not fit) has no string."""
+    if not string_record.is_cuda or string_record.dtype != torch.uint8 or string_record.numel() != 4 * B * K + B * char_capacity:
+        raise ValueError(f'rle_string_offsets: expected the uint8 device tensor of rle_compress(wait=False) for {B} frames, K = {K}, '
+                         f'char_capacity = {char_capacity}')
+    if B * char_capacity >= 1 << 31:
+        raise ValueError('rle_string_offsets: the characters do not fit int32 offsets')
+    lens = string_record[:4 * B * K].view(torch.int32).reshape(B, K).clamp(min=0)
+    ofs = torch.zeros((B, K + 1), dtype=torch.int32, device=string_record.device)
+    ofs[:, 1:] = torch.cumsum(lens, 1).clamp(max=char_capacity)       # a frame that did not fit: its tail reads as malformed, in range
+    ofs += torch.arange(B, dtype=torch.int32, device=string_record.device)[:, None] * char_capacity
+    return string_record[4 * B * K:], ofs
+
+
+def rle_decompress(strings, H, W, K, capacity=None, check=True):
+    """Compressed COCO strings (`rle.decompress_counts` is the definition) -> the int32 device record `rle_decode(record, H, W, K,
+    capacity)` takes (field 0 of `meta` holds the rows' event counts, the rest is 0).  `strings`: a list of B frames, each a list of K
+    str / ASCII bytes / None (a row without string) - joined into one byte buffer and an offsets table and uploaded, with the
+    capacity every frame is sure to fit (its number of characters) unless `capacity` says otherwise; or the device pair (chars uint8
+    [n], str_ofs int32 [B, K + 1]) of `rle_string_offsets`, which needs `capacity`.  check=True reads the status (one synchronisation)
+    and raises ValueError naming the frame and row of a string that is malformed (1), describes no H x W plane (2) or belongs to a
+    frame whose events exceed the capacity (3); check=False returns (record, status int32 [B, K] on the device) without
+    synchronising: such a row has no events in the record, its neighbours are exact."""
+    import numpy as np
+    from . import rle
+    H, W, K = (_rle_int(n, v, 1, top, 'rle_decompress') for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
+    if capacity is not None:
+        capacity = _rle_int('capacity', capacity, 1, (1 << 31) - 1, 'rle_decompress')
+    if isinstance(strings, tuple) and len(strings) == 2 and torch.is_tensor(strings[0]):
+        chars, ofs = strings
+        if not chars.is_cuda or chars.dtype != torch.uint8 or chars.dim() != 1 or not chars.is_contiguous():
+            raise RuntimeError('rle_decompress: chars must be a contiguous uint8 CUDA (HIP) tensor - xmem2_amd has no CPU path')
+        if (not torch.is_tensor(ofs) or ofs.device != chars.device or ofs.dtype != torch.int32 or ofs.dim() != 2 or ofs.shape[1] != K + 1
+                or not ofs.is_contiguous()):
+            raise ValueError(f'rle_decompress: str_ofs must be a contiguous int32 tensor [B, {K + 1}] on the device of chars')
+        if capacity is None:
+            raise ValueError('rle_decompress: a device record needs a capacity')
+        B, device = ofs.shape[0], chars.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError('rle_decompress: needs an MI355X (HIP) device - xmem2_amd has no CPU path')
+        B = len(strings)
+        if B < 1:
+            raise ValueError('rle_decompress: no frames')
+        table = np.zeros((B, K + 1), np.int64)
+        parts = []
+        for b, frame in enumerate(strings):
+            if len(frame) != K:
+                raise ValueError(f'rle_decompress: frame {b} has {len(frame)} rows, expected {K}')
+            for k, v in enumerate(frame):
+                if v is None:
+                    continue
+                if isinstance(v, str):
+                    try:
+                        v = v.encode('ascii')
+                    except UnicodeEncodeError:
+                        raise ValueError(f'rle_decompress: frame {b}, row {k}: a character outside 48..111') from None
+                if not isinstance(v, (bytes, bytearray)):
+                    raise ValueError(f'rle_decompress: frame {b}, row {k}: expected str, bytes or None, got {type(v).__name__}')
+                if len(v) == 0:
+                    raise ValueError(f'rle_decompress: frame {b}, row {k}: an empty string holds no counts')
+                table[b, k] = len(v)
+                parts.append(v)
+        per_frame = table.sum(1)
+        if capacity is None:
+            capacity = max(1, int(per_frame.max()))                   # every value takes a character: events < characters
+        table = np.concatenate((np.zeros((B, 1), np.int64), np.cumsum(table[:, :K], 1)), 1) + (np.cumsum(per_frame) - per_frame)[:, None]
+        if int(table[-1, -1]) >= 1 << 31:
+            raise ValueError('rle_decompress: more than 2^31 characters in one launch')
+        device = torch.device('cuda', torch.cuda.current_device())
+        joined = b''.join(parts) or b'0'                              # never an empty allocation; no offset reaches the filler
+        chars = torch.frombuffer(bytearray(joined), dtype=torch.uint8).to(device)
+        ofs = torch.from_numpy(table.astype(np.int32)).to(device)
+    if B < 1 or B > 65535:
+        raise ValueError(f'rle_decompress: {B} frames in one launch, 1..65535 fit')
+    n_chars = chars.numel()
+    lib = load()
+    record = torch.zeros(B * K * rle.META + B * capacity, dtype=torch.int32, device=device)
+    status = torch.empty((B, K), dtype=torch.int32, device=device)
+    ws = workspace(max(lib.xmem_rle_decompress_workspace_bytes(B, K), 4), device, 'rle')
+    with torch.cuda.device(device):
+        _lib.check(lib.xmem_rle_decompress(ptr(chars), n_chars, ptr(ofs), B, H, W, K, capacity, ptr(record),
+                                           C.c_void_p(record.data_ptr() + 4 * B * K * rle.META), ptr(status), ptr(ws), ws.numel(),
+                                           stream_ptr()))
+    if not check:
+        return record, status
+    bad = status.cpu().numpy()
+    if bad.any():
+        b, k = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f'rle_decompress: frame {b}, row {k}: {rle.STRING_STATUS[int(bad[b, k])]}')
+    return record
 
 
 # ---- f-BRS click refinement (csrc/brs.hip): every kernel bit-reproducible --------------------------------------------

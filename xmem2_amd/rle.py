@@ -14,12 +14,17 @@ event, never per pixel.  `TrackWriter` collects one video's frames into the YouT
     {"videos": [{"id": 1, "height": H, "width": W, "length": T, "file_names": [...]}],
      "categories": [{"id": 1, "name": "object"}],
      "annotations": [{"id": n, "video_id": 1, "category_id": 1, "label": <label in the annotation PNGs>,
-                      "segmentations": [{"size": [H, W], "counts": [...]} | null, ...],      one entry per frame
+                      "segmentations": [{"size": [H, W], "counts": [...] | "..."} | null, ...],      one entry per frame
                       "bboxes": [[x, y, w, h] | null, ...], "areas": [int | null, ...]}]}
 
-`counts` is the uncompressed list form, which COCO tools accept; the compressed string form is not built.  A frame in which a label
-has no pixel, or which has no mask at all, carries null in all three lists.  `python -m xmem2_amd.rle --tracks F --out DIR` is the way
-back to index PNGs; `TrackReader` is the way back without them: counts to events per event (`events_from_counts`), events to label maps
+`counts` is the uncompressed list form, which COCO tools accept, or - config['tracks_counts'] = 'compressed' - the compressed ASCII
+string of the COCO mask API (`compress_counts` / `decompress_counts` are its definition: the counts from the fourth on as differences
+to the count two before, every value as little-endian groups of 5 bits with a continuation bit, characters '0'..'o'), the dict
+`pycocotools.mask.decode` takes.  The device builds the strings from the event record (`ops.rle_compress`: per count a function of
+four neighbouring events, then a scan) and reads them back into the record (`ops.rle_decompress`); every reader here takes both
+forms, also mixed in one file.  A frame in which a label has no pixel, or which has no mask at all, carries null in all three lists.
+`python -m xmem2_amd.rle --tracks F --out DIR` is the way back to index PNGs (`--recode` rewrites a file in the other form);
+`TrackReader` is the way back without them: counts to events per event (`events_from_counts`), events to label maps
 on the device (`ops.rle_decode`) - for scoring (`metrics.compute_metrics`), as annotations (`run_on_video.VideoReader`) and for
 `VideoSession.load_tracks`.
 """
@@ -42,6 +47,81 @@ def default_capacity(h, w):
     """Events per frame `ops.rle_encode` makes room for when it is not told: a label that crosses every column of the frame in two runs
     has 4 * W events, the clips measured so far stay far below it; more is never lost, the frame is encoded again."""
     return max(MIN_CAPACITY, 4 * int(w))
+
+
+def default_char_capacity(h, w, capacity=None):
+    """Bytes per frame `ops.rle_compress` makes room for when it is not told: two characters per event of `default_capacity`.  A count
+    below 16 takes one character and a difference between counts within +-512 two, which covers the runs of an object outline (the
+    chair annotations take 1.5 to 1.7 characters per count, about 1000 per frame); more is never lost, the frame is compressed again
+    with its true length."""
+    return 2 * (default_capacity(h, w) if capacity is None else int(capacity))
+
+
+def compress_counts(counts):
+    """Uncompressed COCO counts -> the compressed ASCII string of the COCO mask API (rleToString), the definition the device is tested
+    against: x[i] = c[i] for i <= 2 and c[i] - c[i - 2] after that, every x as little-endian groups of 5 bits, bit 0x20 of a character
+    saying that another group follows (it does until the remaining bits are the sign alone), characters offset by 48."""
+    counts = [int(c) for c in counts]
+    out = []
+    for i, c in enumerate(counts):
+        x = c - counts[i - 2] if i > 2 else c
+        more = True
+        while more:
+            g = x & 0x1f
+            x >>= 5                                                  # arithmetic: -1 stays -1
+            more = (x != -1) if (g & 0x10) else (x != 0)
+            out.append(chr((g | (0x20 if more else 0)) + 48))
+    return ''.join(out)
+
+
+MAX_GROUPS = 6                                  # characters per value: 30 bits, enough for |x| < 2^29 > 16384 * 16384
+
+
+def decompress_counts(s):
+    """The inverse of `compress_counts` (rleFrString): a str or ASCII bytes -> the list of counts.  ValueError for a character outside
+    '0'..'o', a value of more than MAX_GROUPS characters, a string that ends inside a value and an empty string."""
+    if isinstance(s, str):
+        try:
+            s = s.encode('ascii')
+        except UnicodeEncodeError:
+            raise ValueError('decompress_counts: a character outside 48..111') from None
+    s = bytes(s)
+    if not s:
+        raise ValueError('decompress_counts: an empty string holds no counts')
+    counts = []
+    p = 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            if p >= len(s):
+                raise ValueError('decompress_counts: the string ends inside a value')
+            c = s[p] - 48
+            if not (0 <= c <= 63):
+                raise ValueError(f'decompress_counts: character {s[p]} at {p} is outside 48..111')
+            if k >= MAX_GROUPS:
+                raise ValueError(f'decompress_counts: the value at {p - k} has more than {MAX_GROUPS} characters')
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def is_compressed(counts):
+    """True for the string form of `counts` (str or bytes), False for the list form."""
+    return isinstance(counts, (str, bytes, bytearray))
+
+
+def _count_array(counts):
+    """Either form of `counts` -> int64 [m]."""
+    if is_compressed(counts):
+        counts = decompress_counts(counts)
+    return np.asarray(counts, dtype=np.int64).reshape(-1)
 
 
 def counts_from_events(events, h, w):
@@ -70,17 +150,17 @@ def encode_host(mask, k):
 
 
 def events_from_counts(counts, h, w):
-    """Uncompressed COCO counts of one label -> its ascending event positions (uint32), the inverse of `counts_from_events`; refuses
-    what `decode` refuses.  A cumulative sum: work per event."""
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    """COCO counts of one label (list or compressed string) -> its ascending event positions (uint32), the inverse of
+    `counts_from_events`; refuses what `decode` refuses.  A cumulative sum: work per event."""
+    counts = _count_array(counts)
     if counts.size == 0 or (counts < 0).any() or (counts[1:] == 0).any() or int(counts.sum()) != int(h) * int(w):
         raise ValueError(f'events_from_counts: counts do not describe a {h} x {w} plane')
     return np.cumsum(counts[:-1]).astype(np.uint32)                  # the last count ends at h * w, which is no event
 
 
 def decode(counts, h, w):
-    """Uncompressed COCO counts -> bool [h, w]."""
-    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    """COCO counts (list or compressed string) -> bool [h, w]."""
+    counts = _count_array(counts)
     if counts.size == 0 or (counts < 0).any() or (counts[1:] == 0).any() or int(counts.sum()) != int(h) * int(w):
         raise ValueError(f'decode: counts do not describe a {h} x {w} plane')
     values = (np.arange(counts.size) & 1).astype(bool)
@@ -93,6 +173,25 @@ def split_record(buf, n_frames, k, capacity):
     buf = np.asarray(buf).reshape(-1).view(np.int32)
     cut = n_frames * k * META
     return buf[:cut].reshape(n_frames, k, META), buf[cut:cut + n_frames * capacity].view(np.uint32).reshape(n_frames, capacity)
+
+
+def split_string_record(buf, n_frames, k, char_capacity):
+    """The bytes one `ops.rle_compress` launch leaves ([n_frames * k] int32 string lengths, then [n_frames * char_capacity] characters)
+    -> (str_len int32 [n_frames, k], chars uint8 [n_frames, char_capacity]) as views."""
+    buf = np.asarray(buf).reshape(-1).view(np.uint8)
+    cut = 4 * n_frames * k
+    return buf[:cut].view(np.int32).reshape(n_frames, k), buf[cut:cut + n_frames * char_capacity].reshape(n_frames, char_capacity)
+
+
+def label_strings(str_len, chars):
+    """One frame's packed characters -> the list of per-label strings (label 1 first, '' for a label without event).  `str_len` [K]
+    holds the true lengths; the frame must have been compressed with room for all of them."""
+    n = np.asarray(str_len).astype(np.int64)
+    if (n < 0).any() or int(n.sum()) > len(chars):
+        raise ValueError(f'label_strings: {int(n.sum())} characters, but only {len(chars)} were kept - compress the frame again')
+    text = bytes(chars[:int(n.sum())]).decode('ascii')
+    ends = np.cumsum(n)
+    return [text[e - c:e] for c, e in zip(n, ends)]
 
 
 def label_events(meta, events):
@@ -116,6 +215,15 @@ def record_host(mask, k):
     return meta, np.concatenate(ev) if ev else np.zeros(0, np.uint32)
 
 
+COUNT_FORMS = ('list', 'compressed')            # config['tracks_counts']
+
+
+def check_count_form(counts):
+    if counts not in COUNT_FORMS:
+        raise ValueError(f"tracks_counts must be one of {COUNT_FORMS}, got {counts!r}")
+    return counts
+
+
 class TrackWriter:
     """One video's tracks.  Frames are added in order; a track is opened when its label is first named and has null wherever the
     label was not known yet, had no pixel, or the frame had no mask."""
@@ -125,9 +233,10 @@ class TrackWriter:
         self.file_names = []
         self._tracks = collections.OrderedDict()                     # label in the annotation PNGs -> {frame index: (counts, bbox, area)}
 
-    def add_frame(self, file_name, meta=None, events=None, labels=None):
+    def add_frame(self, file_name, meta=None, events=None, labels=None, strings=None):
         """`meta` [K, META] and the frame's packed `events` as `ops.rle_encode` gives them (`events` holding all of them), `labels`
-        the annotation's label of every row (default 1..K; `inverse_labels`).  Without `meta` the frame has no mask."""
+        the annotation's label of every row (default 1..K; `inverse_labels`).  Without `meta` the frame has no mask.  `strings`: the
+        rows' compressed counts as `ops.rle_compress` gives them; they are written in place of the lists and `events` is not read."""
         t = len(self.file_names)
         self.file_names.append(str(file_name))
         if meta is None:
@@ -136,15 +245,21 @@ class TrackWriter:
         labels = list(range(1, len(meta) + 1)) if labels is None else [int(v) for v in labels]
         if len(labels) != len(meta):
             raise ValueError(f'add_frame: {len(meta)} label rows, {len(labels)} labels')
-        for lab, row, ev in zip(labels, meta, label_events(meta, events)):
+        if strings is not None and len(strings) != len(meta):
+            raise ValueError(f'add_frame: {len(meta)} label rows, {len(strings)} strings')
+        rows = label_events(meta, events) if strings is None else strings
+        for lab, row, ev in zip(labels, meta, rows):
             track = self._tracks.setdefault(lab, {})
             area = int(row[1])
             if area:
                 x0, y0, x1, y1 = (int(v) for v in row[2:6])
-                track[t] = (counts_from_events(ev, self.height, self.width), [x0, y0, x1 - x0 + 1, y1 - y0 + 1], area)
+                counts = counts_from_events(ev, self.height, self.width) if strings is None else str(ev)
+                track[t] = (counts, [x0, y0, x1 - x0 + 1, y1 - y0 + 1], area)
 
-    def add_mask(self, file_name, mask, k=None, labels=None):
-        """A frame from a host index array (dense ids 1..k, default its largest id), encoded on the host; None: a frame without mask."""
+    def add_mask(self, file_name, mask, k=None, labels=None, counts='list'):
+        """A frame from a host index array (dense ids 1..k, default its largest id), encoded on the host; None: a frame without mask.
+        counts='compressed' writes the string form (`compress_counts`)."""
+        check_count_form(counts)
         if mask is None:
             return self.add_frame(file_name)
         mask = np.asarray(mask)
@@ -153,7 +268,11 @@ class TrackWriter:
         k = int(mask.max()) if k is None else int(k)
         if k == 0:
             return self.add_frame(file_name, np.zeros((0, META), np.int32), np.zeros(0, np.uint32), [])
-        return self.add_frame(file_name, *record_host(mask, k), labels=labels)
+        meta, events = record_host(mask, k)
+        strings = None
+        if counts == 'compressed':
+            strings = [compress_counts(counts_from_events(ev, self.height, self.width)) for ev in label_events(meta, events)]
+        return self.add_frame(file_name, meta, events, labels=labels, strings=strings)
 
     def to_dict(self):
         T, size = len(self.file_names), [self.height, self.width]
@@ -217,7 +336,9 @@ class TrackReader:
     """One video's tracks.json, parsed once (`path_or_doc`: the file, or the parsed document) with `read_tracks`'s validation.  The
     annotations are the label rows of a record in file order, so a later annotation wins where tracks overlap, as in `read_tracks`.
     `mask_host(t)` decodes a frame on the host (few frames: annotations); `masks_device` builds packed records from the counts - work
-    per event, never per pixel - and decodes them with `ops.rle_decode`."""
+    per event, never per pixel - and decodes them with `ops.rle_decode`.  Counts may be lists or compressed strings, also mixed in one
+    file: a frame whose entries are all strings goes up as bytes and becomes its record on the device (`ops.rle_decompress`), the host
+    doing nothing per character; `mask_host` and `record` read a string with `decompress_counts`."""
 
     def __init__(self, path_or_doc):
         if isinstance(path_or_doc, dict):
@@ -319,10 +440,63 @@ class TrackReader:
         step = max(1, int(batch))
         with torch.cuda.device(device):
             for i in range(0, len(frames), step):
-                records = [self.record(t) for t in frames[i:i + step]]
-                ops.rle_decode((np.stack([m for m, _ in records]), [e for _, e in records]), self.height, self.width, n_rows,
-                               values=table, out=out[i:i + len(records)])
+                chunk, dst = frames[i:i + step], out[i:i + step]
+                comp = [j for j, t in enumerate(chunk) if self._all_compressed(t)]
+                plain = [j for j in range(len(chunk)) if j not in set(comp)]
+                for idx, decode_group in ((plain, self._decode_lists), (comp, self._decode_strings)):
+                    if not idx:
+                        continue
+                    whole = len(idx) == len(chunk)
+                    got = decode_group([chunk[j] for j in idx], table, dst if whole else None)
+                    if not whole:                                    # a batch that mixes both forms: each group lands in its frames
+                        dst[torch.tensor(idx, device=device)] = got
         return out, present
+
+    def _all_compressed(self, t):
+        """True when frame t has an entry and every entry's counts are a string: the frame is decoded by `ops.rle_decompress`."""
+        forms = [is_compressed(segs[t]) for segs in self._segs if t in segs]
+        return bool(forms) and all(forms)
+
+    def _decode_lists(self, frames, table, out):
+        from . import ops
+        records = [self.record(t) for t in frames]
+        return ops.rle_decode((np.stack([m for m, _ in records]), [e for _, e in records]), self.height, self.width, len(self.labels),
+                              values=table, out=out)
+
+    def _decode_strings(self, frames, table, out):
+        """The strings go up as they are - one byte buffer and an offsets table - and become the record on the device."""
+        from . import ops
+        n_rows = len(self.labels)
+        record, status = ops.rle_decompress([[segs.get(t) for segs in self._segs] for t in frames], self.height, self.width, n_rows,
+                                            check=False)
+        bad = status.cpu().numpy().reshape(len(frames), n_rows)
+        if bad.any():
+            j, a = (int(v) for v in np.argwhere(bad)[0])
+            raise ValueError(f'TrackReader: track {a + 1}, frame {frames[j]}: ' + STRING_STATUS[int(bad[j, a])])
+        capacity = record.numel() // len(frames) - n_rows * META
+        return ops.rle_decode(record, self.height, self.width, n_rows, capacity, values=table, out=out)
+
+
+# what `ops.rle_decompress` says about a row (include/xmem_hip.h, xmem_rle_decompress)
+STRING_STATUS = {1: 'the compressed counts are malformed', 2: 'the counts do not describe a plane of the video\'s size',
+                 3: 'the events of the frame do not fit the capacity'}
+
+
+def recode_tracks(doc, counts):
+    """A parsed tracks document with every entry's counts in the form `counts` ('list' | 'compressed'), by the host definitions, per
+    count; everything else - and an entry that already has the form - is kept as it is."""
+    check_count_form(counts)
+    doc = json.loads(json.dumps(doc))                                # a deep copy that keeps the order of the keys
+    for ann in doc.get('annotations', []):
+        for seg in ann.get('segmentations', []):
+            if seg is None:
+                continue
+            have = seg['counts']
+            if counts == 'compressed' and not is_compressed(have):
+                seg['counts'] = compress_counts(have)
+            elif counts == 'list' and is_compressed(have):
+                seg['counts'] = decompress_counts(have)
+    return doc
 
 
 def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
@@ -351,12 +525,26 @@ def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle', description='tracks.json -> index PNGs (one per frame)')
-    ap.add_argument('--tracks', required=True, help='the tracks.json of one video')
-    ap.add_argument('--out', required=True, help='directory the PNGs are written to')
+    ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle',
+                                 description='tracks.json -> index PNGs (one per frame), or - with --recode - tracks.json with its '
+                                             'counts in the other form')
+    ap.add_argument('--tracks', required=True, help='the tracks.json of one video (counts as lists, compressed strings, or both)')
+    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode the file that is written')
+    ap.add_argument('--recode', default=None, choices=COUNT_FORMS,
+                    help='write no PNGs: rewrite the file with every counts entry as a list or as the compressed COCO string')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
     args = ap.parse_args(argv)
+    if args.recode is not None:
+        with open(args.tracks) as f:
+            doc = recode_tracks(json.load(f), args.recode)
+        if os.path.dirname(args.out):
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        text = json.dumps(doc, separators=(',', ':'))
+        with open(args.out, 'w') as f:
+            f.write(text)
+        print(json.dumps({'recode': args.recode, 'bytes': len(text), 'out': args.out}))
+        return 0
     written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty)
     print(json.dumps({'frames': len(written), 'out': args.out}))
     return 0

@@ -304,19 +304,30 @@ class _TrackLoop:
     """config['save_tracks'] inside a frame loop: one `ops.rle_encode` launch sequence per frame on the compute stream, the record
     delivered through pinned memory one frame behind like the mask (its own AsyncMaskFetcher, fed right before the mask's: when the
     mask of a frame has arrived, so has its record), the counts made on the host per event, the file written at the end.  A frame
-    whose events did not fit is encoded again when its record arrives, and the capacity of the frames after it grows to twice its size."""
+    whose events did not fit is encoded again when its record arrives, and the capacity of the frames after it grows to twice its size.
+    counts='compressed' (config['tracks_counts']): `ops.rle_compress` runs right behind the encoder on the same stream and what
+    travels is meta + string lengths + characters, not the events; a frame whose events or characters did not fit is done again at
+    its exact size when its record arrives."""
 
-    def __init__(self):
-        self.writer = self.capacity = None                           # made for the first frame's size (that of the written PNGs)
+    def __init__(self, counts='list'):
+        from .rle import check_count_form
+        self.counts = check_count_form(counts)
+        self.writer = self.capacity = self.char_capacity = None      # made for the first frame's size (that of the written PNGs)
         self.fetcher = AsyncMaskFetcher()
 
     def submit(self, tag, mask_dev, k):
         """-> the (tag, record) pairs that have arrived.  `mask_dev` must stay untouched until its record was delivered: it is
         encoded again should its events not fit."""
         if self.writer is None:
-            from .rle import TrackWriter, default_capacity
+            from .rle import TrackWriter, default_capacity, default_char_capacity
             self.writer, self.capacity = TrackWriter(*mask_dev.shape), default_capacity(*mask_dev.shape)
+            self.char_capacity = default_char_capacity(*mask_dev.shape)
         rec = ops.rle_encode(mask_dev, k, self.capacity, wait=False)
+        if self.counts == 'compressed':
+            from .rle import META
+            srec = ops.rle_compress(rec, *mask_dev.shape, k, self.capacity, self.char_capacity, wait=False)
+            return self.fetcher.submit((tag, mask_dev, k, self.capacity, self.char_capacity),
+                                       torch.cat((rec[:k * META].view(torch.uint8), srec)))
         return self.fetcher.submit((tag, mask_dev, k, self.capacity), rec.view(torch.uint8))
 
     def drain(self):
@@ -324,6 +335,8 @@ class _TrackLoop:
 
     def finish(self, item, name, mapper):
         from .rle import inverse_labels, split_record
+        if self.counts == 'compressed':
+            return self._finish_compressed(item, name, mapper)
         (_, mask_dev, k, capacity), buf = item
         meta, events = split_record(buf, 1, k, capacity)
         meta, events = meta[0], events[0]
@@ -334,6 +347,25 @@ class _TrackLoop:
             meta, events = meta_all[0], ev_all[0]
             self.capacity = max(self.capacity, 2 * total)            # and the frames to come get room for a video as ragged as this
         self.writer.add_frame(name, meta, events, inverse_labels(mapper, k))
+
+    def _finish_compressed(self, item, name, mapper):
+        from .rle import META, inverse_labels, label_strings, split_string_record
+        (_, mask_dev, k, capacity, char_capacity), buf = item
+        meta = buf[:4 * k * META].view(np.int32).reshape(k, META)
+        str_len, chars = split_string_record(buf[4 * k * META:], 1, k, char_capacity)
+        total, need = int(meta[:, 0].sum()), int(str_len[0].sum())   # need < 0: the events did not fit, no string was made
+        if total > capacity or need > char_capacity:                 # the exact sizes are known now: once more, nothing is cut off
+            if total > capacity:
+                ops.RLE_STATS['retries'] += 1
+                self.capacity = max(self.capacity, 2 * total)        # the frames to come get room for a video as ragged as this
+            else:
+                ops.RLE_STRING_STATS['retries'] += 1
+            rec = ops.rle_encode(mask_dev, k, max(total, 1), wait=False)
+            strings = ops.rle_compress(rec, *mask_dev.shape, k, max(total, 1), max(need, char_capacity))[0]
+            self.char_capacity = max(self.char_capacity, 2 * sum(len(v) for v in strings))
+        else:
+            strings = label_strings(str_len[0], chars[0])
+        self.writer.add_frame(name, meta, None, inverse_labels(mapper, k), strings=strings)
 
     def write(self, masks_out_path):
         return self.writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
@@ -590,8 +622,8 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     outputs = _FrameOutputs(
         vid_reader, mapper, AsyncMaskFetcher(),
         saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
-        tracks=_TrackLoop() if config.get('save_tracks', False) else None, scorer=scorer, compute_iou=compute_iou,
-        save_overlay=save_overlay, masks_out_path=config['masks_out_path'])
+        tracks=_TrackLoop(config.get('tracks_counts', 'list')) if config.get('save_tracks', False) else None, scorer=scorer,
+        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'])
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -813,8 +845,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again
         vid_reader, mapper, AsyncMaskFetcher(),
         saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
-        tracks=_TrackLoop() if config.get('save_tracks', False) else None, scorer=scorer, compute_iou=compute_iou,
-        save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=True)
+        tracks=_TrackLoop(config.get('tracks_counts', 'list')) if config.get('save_tracks', False) else None, scorer=scorer,
+        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=True)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):

@@ -475,11 +475,13 @@ class VideoSession:
         finally:
             saver.close()
 
-    def save_tracks(self, masks_out_path, batch=32):
+    def save_tracks(self, masks_out_path, batch=32, counts='list'):
         """<masks_out_path>/tracks.json (xmem2_amd/rle.py) of the masks as they stand: the frames that have one are encoded from the
         resident `masks` in launches of `batch` frames and only their run boundaries, areas and boxes reach the host; a frame without a
-        mask has null in every track.  Returns the file's path."""
-        from .rle import TrackWriter, inverse_labels
+        mask has null in every track.  counts='compressed': the record stays on the device, is turned into the compressed COCO strings
+        there (`ops.rle_compress`) and those reach the host instead of the events.  Returns the file's path."""
+        from .rle import META, TrackWriter, check_count_form, default_capacity, inverse_labels
+        check_count_form(counts)
         k = len(self.mapper.labels)
         if k == 0:
             raise ValueError('No valid masks provided!')
@@ -491,11 +493,23 @@ class VideoSession:
             chunk = present[i:i + max(1, int(batch))]
             contiguous = chunk == list(range(chunk[0], chunk[-1] + 1))
             dev = self.masks[chunk[0]:chunk[-1] + 1] if contiguous else self.masks[torch.tensor(chunk, device=self.device)]
+            if counts == 'compressed':
+                capacity = default_capacity(*self.shape)
+                rec = ops.rle_encode(dev, k, capacity, wait=False)
+                strings = ops.rle_compress(rec, *self.shape, k, capacity)
+                meta = rec[:len(chunk) * k * META].cpu().numpy().reshape(len(chunk), k, META)
+                for j, t in enumerate(chunk):
+                    if strings[j] is None:                               # its events did not fit: this frame again, at its exact size
+                        total = int(meta[j, :, 0].sum())
+                        strings[j] = ops.rle_compress(ops.rle_encode(dev[j:j + 1], k, total, wait=False), *self.shape, k, total)[0]
+                    encoded[t] = (meta[j], None, strings[j])
+                continue
             meta, events = ops.rle_encode(dev, k)
             for j, t in enumerate(chunk):
-                encoded[t] = (meta[j], events[j])
+                encoded[t] = (meta[j], events[j], None)
         for t, fr in enumerate(self.frames):
-            writer.add_frame(fr.frame, *encoded.get(t, (None, None)), labels=labels)
+            meta, events, strings = encoded.get(t, (None, None, None))
+            writer.add_frame(fr.frame, meta, events, labels=labels, strings=strings)
         return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
 
     def load_tracks(self, path, batch=32):
@@ -590,6 +604,8 @@ def parse_args(argv=None):
     ap.add_argument('--config', default=None, help='JSON dict merged into VIDEO_INFERENCE_CONFIG')
     ap.add_argument('--overlay', action='store_true', help='write overlays next to the masks')
     ap.add_argument('--tracks', action='store_true', help='write <out>/tracks.json, run-length tracks encoded on the device, next to the masks')
+    ap.add_argument('--tracks-counts', default='list', choices=('list', 'compressed'),
+                    help='the counts in tracks.json: uncompressed lists, or the compressed COCO strings built on the device')
     ap.add_argument('--feature-cache-gb', type=float, default=0.0,
                     help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
@@ -620,7 +636,7 @@ def main(argv=None):
         print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
     s.save(args.out, save_overlay=args.overlay)
     if args.tracks:
-        s.save_tracks(args.out)
+        s.save_tracks(args.out, counts=args.tracks_counts)
     return 0
 
 
