@@ -40,7 +40,7 @@ typedef enum {
 
 /* ABI version of this header.  2 (round 4): xmem_conv_desc grew (in_half / out_half / w_half), storage-typed `_t` entry points, plan
  * tiles 23..40.  3 (round 5): no layout change, but the MEANING of w_winograd4 / w_winograd4_split changed - the F(4x4) transforms use the
- * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  Still 5: the f-BRS refinement entry points added (xmem_brs_affine_nhwc, xmem_brs_loss, xmem_relu_gate_nhwc, xmem_relu_gate_outer_nhwc, xmem_brs_param_grad and their workspace sizes): new symbols only, no layout change.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
+ * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  Still 5: the f-BRS refinement entry points added (xmem_brs_affine_nhwc, xmem_brs_loss, xmem_relu_gate_nhwc, xmem_relu_gate_outer_nhwc, xmem_brs_param_grad and their workspace sizes): new symbols only, no layout change.  Still 5: xmem_conv2d_pointwise_pair added, a new symbol only.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
 #define XMEM_ABI_VERSION 5
 int xmem_version(void);
 const char* xmem_last_error_string(int code); /* static string for a status code */
@@ -183,6 +183,18 @@ int xmem_conv2d_shared_input(const xmem_conv_desc* const* descs, int n, void* co
 int xmem_conv2d_nhwc_folded(const xmem_conv_desc* d, const xmem_conv_desc* branch, const void* branch_m, size_t branch_m_bytes,
                             void* workspace, size_t workspace_bytes, void* stream);
 int xmem_conv2d_output_from_m(const xmem_conv_desc* d, const void* m, size_t m_bytes, void* stream);
+
+/* BOTTLENECK PAIR.  A ResNet-50 bottleneck ends in an expand 1x1 (`expand`: Cmid -> 4 Cmid, + residual, relu) and the next block opens with
+ * a reduce 1x1 (`reduce`: 4 Cmid -> Cmid', relu) of that output.  This entry point runs both in ONE launch: a workgroup owns 64 pixels,
+ * forms the expand output y chunk by chunk, stores it (expand->out: the next block's residual) and contracts each chunk straight from
+ * LDS into the reduce accumulator; reduce->out receives z.  y is not read back from memory.
+ *   reduce->in == expand->out, reduce->ldin == expand->ldout, reduce->Cin == expand->Cout, same B / H / W (else XMEM_ERR_BAD_ARG).
+ * Taken: fp32 (in_half = out_half = arith = 0), 1x1 / stride 1 / pad 0, expand->Cin in {64, 128, 256}, expand->Cout = 4 Cin,
+ * reduce->Cout in {Cin, 2 Cin} and <= 256, expand->res set (plain, not broadcast) and reduce->res NULL, relu_in 0 and relu_out 1 on
+ * both, and BOTH plans (plan_tile / plan_splitk resolved as xmem_conv2d_nhwc resolves them) a classic direct tile with split-K 1 -
+ * then y and z have the bits of the two xmem_conv2d_nhwc calls.  Anything else returns XMEM_ERR_UNSUPPORTED before any GPU work and
+ * the caller issues those two calls.  No workspace. */
+int xmem_conv2d_pointwise_pair(const xmem_conv_desc* expand, const xmem_conv_desc* reduce, void* stream);
 
 /* Dilated convolution (atrous), the S2M network's DeepLabV3+ (inference/interact/s2m/s2m_resnet.py:17-20 conv3x3 with dilation, the
  * layer4 blocks 1-2 of _make_layer's replace_stride_with_dilation, :138-150; ASPPConv, s2m/_deeplab.py:113-119, rates 6 / 12 / 18).

@@ -74,6 +74,7 @@ _SIGS = {
     'xmem_conv2d_nhwc_folded': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_void_p]),
     'xmem_conv2d_output_from_m': (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'xmem_conv2d_pointwise_pair': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.c_void_p]),
     'xmem_conv2d_dilated_workspace_bytes': (C.c_size_t, [C.POINTER(ConvDesc), C.c_int]),
     'xmem_conv2d_nhwc_dilated': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     'xmem_maxpool3x3s2': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -14,6 +14,7 @@
 // Replaces the nn.Conv2d/BatchNorm2d/ReLU/residual call sites listed in include/xmem_hip.h.
 #include "common.hpp"
 #include "gemm_stream.hpp"
+#include "pointwise_pair.hpp"
 #include <stdlib.h>
 
 // BK (k-depth of a staged tile) is a template parameter: 32 or 64.  LDS rows are padded by 4 floats:
@@ -2009,6 +2010,34 @@ extern "C" int xmem_conv2d_nhwc(const xmem_conv_desc* d, void* workspace, size_t
     }
 #endif
     return pl.splitk > 1 ? launch_splitk_reduce(a, half == 2, s) : rc;
+}
+
+// A bottleneck's expand 1x1 (`e`: + residual, relu) and the next block's reduce 1x1 (`r`: relu, reading e's output) in one launch
+// (csrc/pointwise_pair.hip).  Both plans are resolved exactly as xmem_conv2d_nhwc would resolve them: the pair kernel gives the bits of
+// the classic direct tiles with split-K 1 and of nothing else, so any other plan is the caller's cue to run the two layers separately.
+extern "C" int xmem_conv2d_pointwise_pair(const xmem_conv_desc* e, const xmem_conv_desc* r, void* stream) {
+    int rc = validate(e);
+    if (rc != XMEM_OK) return rc;
+    if ((rc = validate(r)) != XMEM_OK) return rc;
+    if (r->in != e->out || r->ldin != e->ldout || r->Cin != e->Cout || r->B != e->B || r->H != e->H || r->W != e->W) return XMEM_ERR_BAD_ARG;
+    for (const xmem_conv_desc* d : {e, r}) {
+        if (d->in_half || d->out_half || d->arith != 0) return XMEM_ERR_UNSUPPORTED;                 // fp32 only
+        if (d->KH != 1 || d->KW != 1 || d->pad != 0 || d->stride != 1) return XMEM_ERR_UNSUPPORTED;
+        if (d->relu_in || !d->relu_out || d->res_broadcast) return XMEM_ERR_UNSUPPORTED;
+    }
+    if (!e->res || r->res) return XMEM_ERR_UNSUPPORTED;
+    if (!pointwise_pair_supported(e->Cin, e->Cout, r->Cout)) return XMEM_ERR_UNSUPPORTED;
+    if ((((uintptr_t)e->in) & 15) != 0 || e->ldres >= (1 << 23) || (double)e->B * e->H * e->W >= 2.0e9) return XMEM_ERR_UNSUPPORTED;
+    for (const xmem_conv_desc* d : {e, r}) {
+        const Plan pl = make_plan(d, d->plan_tile);
+        if (pl.form != DIRECT || pl.splitk != 1 || pl.ring || pl.generic || pl.split) return XMEM_ERR_UNSUPPORTED;
+    }
+    PairArgs a;
+    a.A = e->in; a.W1 = e->w; a.scale1 = e->scale; a.shift1 = e->shift; a.res = e->res;
+    a.W2 = r->w; a.scale2 = r->scale; a.shift2 = r->shift; a.y = e->out; a.z = r->out;
+    a.M = e->B * e->H * e->W; a.K1 = e->Cin; a.N1 = e->Cout; a.N2 = r->Cout;
+    a.lda = e->ldin; a.ldres = e->ldres; a.ldy = e->ldout; a.ldz = r->ldout;
+    return pointwise_pair_launch(a, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t xmem_conv2d_shared_input_workspace_bytes(const xmem_conv_desc* const* descs, int n) {

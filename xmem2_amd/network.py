@@ -32,6 +32,10 @@ MAX_STAGES = 160
 # too few waves to cover the latency of their loads, the mask head, hidden_update_gather and copy_channels stay three launches
 # (NOT MEASURED yet: placed between the 240p map, 405 pixels, and the 480p one, 1 620; profiles/r07_decoder_tail.txt)
 FUSED_TAIL_MIN_PIXELS = 512
+# pixels (batch x h x w) from which a bottleneck's expand 1x1 and the next block's reduce 1x1 run as one launch (ops.conv2d_pointwise_pair):
+# a pair workgroup owns 64 pixels whatever the channel counts, so a small map is a small grid (batch 1 at 1/16 resolution: 26 workgroups
+# on 256 CUs).  Set from the isolated timings of profiles/r11_bottleneck_pairs.txt.
+FUSED_BOTTLENECK_MIN_PIXELS = 25920
 
 
 # stages whose static outputs other stages read in place: the key encoder, and the slot a cached key pass is restored into
@@ -78,6 +82,10 @@ class XMem:
         # branch folded into its last output transform (ops.conv2d_shared / conv2d_folded).  XMEM_SHARED_TRANSFORMS=0 keeps the
         # separate convolutions: an A/B switch, bit-identical either way.  fp32 only; the other precisions always run separately
         self.shared_transforms = os.environ.get('XMEM_SHARED_TRANSFORMS', '1') != '0'
+        # a bottleneck's conv3 (+ residual, relu) and the next block's conv1 (relu) in one launch from fused_bottleneck_min_pixels pixels on
+        # (ops.conv2d_pointwise_pair).  XMEM_FUSED_BOTTLENECK=0 keeps the separate convolutions: an A/B switch, bit-identical either way
+        self.fused_bottleneck = os.environ.get('XMEM_FUSED_BOTTLENECK', '1') != '0'
+        self.fused_bottleneck_min_pixels = FUSED_BOTTLENECK_MIN_PIXELS
         # 'fp32' (default: the parity contract) | 'fp16' (opt-in: the fp16 loop - half activations in HBM, half-operand convolutions
         # on the fp16 MFMA with fp32 accumulation: the counterpart of the reference's autocast loop, run_on_video.py:76; the
         # permanent-memory preload stays fp32 as in run_on_video.py:59-66) | 'fp16w' / 'fp32x' (experiments, ops.PRECISIONS)
@@ -421,10 +429,27 @@ class XMem:
         res = ops.conv2d(x, W[p + '.downsample']) if (p + '.downsample') in W else x
         return ops.conv2d(o, W[p + '.conv2'], res=res, relu_out=True)
 
-    def _stage(self, x, prefix, blocks, fn):
+    def _stage(self, x, prefix, blocks, fn, pre=None, then=None):
+        """The blocks of one ResNet stage.  A bottleneck stage of a network with `fused_bottleneck` walks its blocks so that block b's conv3 and
+        block b + 1's conv1 are one launch (ops.conv2d_pointwise_pair); `then` names the convolution that reads the stage's output next (the
+        following stage's first conv1), which is paired with the last conv3 and returned with the output: -> (x, then(x)), and `pre` is
+        block 0's conv1 output made that way.  A pair the op does not take runs as the two convolutions: the same bits either way."""
+        if fn != self._bottleneck or not getattr(self, 'fused_bottleneck', False):
+            for b in range(blocks):
+                x = fn(x, f'{prefix}.{b}')
+            return x if then is None else (x, None)
+        W = self._w
         for b in range(blocks):
-            x = fn(x, f'{prefix}.{b}')
-        return x
+            p = f'{prefix}.{b}'
+            o = pre if pre is not None else ops.conv2d(x, W[p + '.conv1'], relu_out=True)
+            o = ops.conv2d(o, W[p + '.conv2'], relu_out=True)
+            res = ops.conv2d(x, W[p + '.downsample']) if (p + '.downsample') in W else x
+            follow = f'{prefix}.{b + 1}.conv1' if b + 1 < blocks else then
+            if follow is not None and o.shape[0] * o.shape[1] * o.shape[2] >= self.fused_bottleneck_min_pixels:
+                x, pre = ops.conv2d_pointwise_pair(o, W[p + '.conv3'], res, W[follow])
+            else:
+                x, pre = ops.conv2d(o, W[p + '.conv3'], res=res, relu_out=True), None
+        return x if then is None else (x, pre)
 
     def _group_res(self, g, p, out=None, out_ld=None):
         """GroupResBlock, model/group_modules.py:44-52: conv2(relu(conv1(relu(g)))) + (downsample(g) | g)."""
@@ -500,9 +525,9 @@ class XMem:
         W = self._w
         x = ops.conv2d(image4, W['key_encoder.conv1'], relu_out=True)       # the stem reads the fp32 image in every mode
         x = ops.maxpool3x3s2(x, out_dtype=ops.act_dtype())                # fp16 loop: activations become halfs here
-        f4 = self._stage(x, 'key_encoder.res2', 3, self._bottleneck)
-        f8 = self._stage(f4, 'key_encoder.layer2', 4, self._bottleneck)
-        f16 = self._stage(f8, 'key_encoder.layer3', 6, self._bottleneck)
+        f4, pre = self._stage(x, 'key_encoder.res2', 3, self._bottleneck, then='key_encoder.layer2.0.conv1')
+        f8, pre = self._stage(f4, 'key_encoder.layer2', 4, self._bottleneck, pre=pre, then='key_encoder.layer3.0.conv1')
+        f16 = self._stage(f8, 'key_encoder.layer3', 6, self._bottleneck, pre=pre)
         B, h, w, _ = f16.shape
         ld = _pad4(2 * self.key_dim + 1)
         proj = torch.empty((B, h, w, ld), dtype=torch.float32, device=f16.device)

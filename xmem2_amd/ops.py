@@ -313,7 +313,8 @@ def _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out):
     return d
 
 
-def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, alloc=True, folded=False):
+def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, alloc=True, folded=False,
+               res_ld=None):
     """What comes before the launch of one convolution of either path: the output buffer (`alloc` False: left None for the caller),
     the descriptor with the operands of the precision mode and the plan (conv_plan.choose).  `folded`: the residual arrives inside the
     output transform (conv2d_folded) - planned as the convolution with a residual that it is, the plan tables being keyed by the
@@ -328,6 +329,8 @@ def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out,
         out_ld = out.shape[-1]
     d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
     d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
+    if res is not None and res_ld is not None:
+        d.ldres = res_ld                     # the residual is a channel slice of a wider buffer
     wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
     key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None or folded)}{int(relu_in)}{int(relu_out)}'
     if half:
@@ -357,10 +360,11 @@ def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out,
     return d, out, out_ld, key, plan, wino_ok
 
 
-def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half):
+def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, res_ld=None):
     """One convolution of either path: `_conv_prep`, workspace, launch on the current stream, and the RECORD entry."""
     lib = load()
-    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half)
+    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half,
+                                                    res_ld=res_ld)
     B, Ho, Wo = x.shape[0], (x.shape[1] + 2 * cw.pad - cw.kh) // cw.stride + 1, (x.shape[2] + 2 * cw.pad - cw.kw) // cw.stride + 1
     need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
     ws = workspace(need, x.device, 'conv') if need else None
@@ -411,9 +415,12 @@ def _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, r
 
 
 def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
-           res_broadcast=False, out_dtype=None):
-    """x [B,H,W,C] NHWC (or any buffer whose pixel stride is `in_ld`) -> out [B,Ho,Wo,Cout]."""
+           res_broadcast=False, out_dtype=None, res_ld=None):
+    """x [B,H,W,C] NHWC (or any buffer whose pixel stride is `in_ld`) -> out [B,Ho,Wo,Cout].  `res_ld`: the pixel stride of a residual
+    that is a channel slice of a wider buffer (fp32 direct and Winograd forms; default: its last dimension)."""
     _req(x, 'conv2d input', half_ok=True)
+    if res_ld is not None and res is not None and res_ld != res.shape[-1] and (x.dtype == torch.float16 or cw.dilation != 1):
+        raise RuntimeError('conv2d: a residual with its own pixel stride is taken by the fp32, dilation-1 forms only')
     if x.dtype == torch.float16:
         return _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype)
     if out_dtype is not None and out_dtype != torch.float32:
@@ -426,7 +433,7 @@ def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False
     if cin != cw.cin:
         raise RuntimeError(f'conv2d: weight expects Cin={cw.cin}, got {cin}')
     ldin = in_ld if in_ld is not None else x.shape[3]
-    return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False)
+    return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False, res_ld=res_ld)
 
 
 # ---- shared Winograd transforms (include/xmem_hip.h: SHARED WINOGRAD TRANSFORMS) -------------------------------------------------
@@ -521,6 +528,57 @@ def conv2d_folded(x, cw, branch, out=None, out_ld=None, relu_in=False, relu_out=
     check(rc)
     SHARED_STATS['folded'] += 1
     return out
+
+
+# ---- bottleneck pair (include/xmem_hip.h: BOTTLENECK PAIR) -----------------------------------------------------------------------
+# conv2d_pointwise_pair: a bottleneck's expand 1x1 (+ residual, relu) and the next block's reduce 1x1 (relu) in one launch; the bits of
+# the two conv2d calls under the same plans, and exactly those calls wherever the library declines, outside fp32 and while RECORD is on.
+PAIR_STATS = {'pair': 0, 'separate': 0}          # calls that took the pair kernel / calls issued as two convolutions
+
+
+def _pixel_strided(t):
+    """(tensor, pixel stride) of a residual: a channel slice of a dense NHWC buffer is read in place, any other view is copied once."""
+    B, H, W, Cc = t.shape
+    ld = t.stride(2)
+    if t.stride(3) == 1 and ld >= Cc and t.stride(1) == W * ld and t.stride(0) == H * W * ld:
+        return t, ld
+    t = t.contiguous()
+    return t, Cc
+
+
+def conv2d_pointwise_pair(o, cw_expand, res, cw_reduce, y=None, y_ld=None, z=None, z_ld=None, in_ld=None, plans=(None, None),
+                          res_broadcast=False):
+    """o [B,H,W,Cmid] (pixel stride `in_ld`), res [B,H,W,4 Cmid] (fp32: a channel slice of a wider buffer is read in place) ->
+    y = relu(conv1x1(o, cw_expand) + res) [B,H,W,4 Cmid], z = relu(conv1x1(y, cw_reduce)) [B,H,W,Cmid'].  `y` / `z` with `y_ld` / `z_ld`:
+    output buffers and their pixel strides, as conv2d's `out` / `out_ld`; `plans`: conv2d's `plan` of the two layers; `res_broadcast` as
+    in conv2d (always two launches)."""
+    _req(o, 'conv2d_pointwise_pair input', half_ok=True)
+    res_ld = None
+    if res is not None and o.dtype == torch.float32 and res.dim() == 4:
+        res, res_ld = _pixel_strided(res)
+    fusable = o.dtype == torch.float32 and _PRECISION == 'fp32' and RECORD is None and res is not None and res.dtype == torch.float32 \
+        and not res_broadcast and all(cw.dilation == 1 and cw.stride == 1 for cw in (cw_expand, cw_reduce))
+    if not fusable:
+        PAIR_STATS['separate'] += 1
+        yy = conv2d(o, cw_expand, out=y, out_ld=y_ld, res=res, relu_out=True, in_ld=in_ld, plan=plans[0], res_broadcast=res_broadcast,
+                    res_ld=res_ld)
+        zz = conv2d(yy, cw_reduce, out=z, out_ld=z_ld, relu_out=True, in_ld=y_ld, plan=plans[1])
+        return yy, zz
+    lib = load()
+    ldin = in_ld if in_ld is not None else o.shape[3]
+    de, yy, yy_ld, _, _, _ = _conv_prep(o, cw_expand, cw_expand.cin, ldin, y, y_ld, torch.float32, res, False, True, False, plans[0], False,
+                                        res_ld=res_ld)
+    dr, zz, zz_ld, _, _, _ = _conv_prep(yy, cw_reduce, cw_reduce.cin, yy_ld, z, z_ld, torch.float32, None, False, True, False, plans[1], False)
+    rc = lib.xmem_conv2d_pointwise_pair(C.byref(de), C.byref(dr), stream_ptr())
+    if rc == _lib.UNSUPPORTED:
+        # (yy / zz were allocated above when the caller gave none: the separate calls fill the same buffers)
+        PAIR_STATS['separate'] += 1
+        conv2d(o, cw_expand, out=yy, out_ld=yy_ld, res=res, relu_out=True, in_ld=in_ld, plan=plans[0], res_ld=res_ld)
+        conv2d(yy, cw_reduce, out=zz, out_ld=zz_ld, relu_out=True, in_ld=yy_ld, plan=plans[1])
+        return yy, zz
+    check(rc)
+    PAIR_STATS['pair'] += 1
+    return yy, zz
 
 
 def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
