@@ -120,8 +120,7 @@ def test_mask_head_gather_rejects_what_it_cannot_run():
 
 def _plan_info(x, cw, plan):
     from xmem2_amd import _lib, ops
-    d = ops._conv_desc(x, cw, cw.cin, x.shape[3], x, x.shape[3], None, False, False)
-    d.plan_tile, d.plan_splitk = plan
+    d = ops.ConvCall(x=x, cw=cw, out=x, plan=plan).d
     info = _lib.ConvPlanInfo()
     assert _lib.load().xmem_conv2d_plan_info(ctypes.byref(d), ctypes.byref(info)) == 0
     return info

@@ -187,17 +187,16 @@ def _fastest(lib, d, dev, plans, **timing):
     return best, best_t
 
 
-def _tune_conv(lib, d, dev, f4_operand, incumbent=None):
-    """Time the candidate plans for this descriptor; returns the fastest (or `incumbent` unless beaten by RETUNE_MARGIN).
-    `f4_operand()` points `d` at the F(4x4) operand of a layer that has the F(2x2) one."""
-    Ho = (d.H + 2 * d.pad - d.KH) // d.stride + 1
-    Wo = (d.W + 2 * d.pad - d.KW) // d.stride + 1
-    M, K = d.B * Ho * Wo, d.KH * d.KW * d.Cin
+def _tune_conv(lib, call, incumbent=None):
+    """Time the candidate plans for this call's descriptor; returns the fastest (or `incumbent` unless beaten by RETUNE_MARGIN).
+    `call.f4_operand()` points the descriptor at the F(4x4) operand of a layer that has the F(2x2) one."""
+    d, dev = call.d, call.x.device
+    M, K = d.B * call.Ho * call.Wo, d.KH * d.KW * d.Cin
     forms = ['direct']
     if d.w_winograd and d.ldout % 4 == 0 and (not d.res or d.ldres % 4 == 0):
         forms += ['f2', 'f2_fused']
-        if Ho * Wo >= 256:          # F(4x4,3x3): the same GEMM tiles over 36 positions
-            f4_operand()
+        if call.Ho * call.Wo >= 256:          # F(4x4,3x3): the same GEMM tiles over 36 positions
+            call.f4_operand()
             forms.append('f4')
     plans = []
     for code, c in sorted(CODES.items()):
@@ -242,9 +241,9 @@ def _tune_stream(lib, d, dev, plan):
     return best
 
 
-def choose(lib, d, key, plan, dev, precision, cout, has_winograd, wino_ok, pixels, f4_operand):
-    """(code, split-K) of one conv2d call, with `d` pointed at the F(4x4) operand (`f4_operand()`) when the plan reads it.  The plan
-    is, in this order:
+def choose(lib, call, plan):
+    """(code, split-K) of one conv2d call (`call`: its ops.ConvCall, `plan`: what the caller asked for), with the call's descriptor
+    pointed at the F(4x4) operand (`call.f4_operand()`) when the plan reads it.  The plan is, in this order:
     1. the caller's plan, taken literally (tests, tools, the fp16w mode);
     2. a CONV_FORM attribution form (fp32 mode);
     3. the plan table of the mode (the shipped conv_plans*.json, then the plans this process chose before);
@@ -252,33 +251,34 @@ def choose(lib, d, key, plan, dev, precision, cout, has_winograd, wino_ok, pixel
        TUNE_STREAM tries the streaming-GEMM variants of a Winograd plan;
     5. the deterministic heuristic: same shape -> same plan -> same summation order on every machine.
     CONV_FORM 'f2' then runs the GEMM tile of an F(4x4) plan under F(2x2).  Steps 3 and 5 are `tabled_or_heuristic`."""
-    half, split = bool(d.in_half), d.arith == 1
-    fp32 = not half and precision == 'fp32'
+    d, key, has_winograd = call.d, call.key, call.cw.wu is not None
+    half, split = call.half, d.arith == 1
+    fp32 = not half and call.precision == 'fp32'
     explicit = plan is not None or (fp32 and CONV_FORM in _DIRECT_FORMS)
     capturing = torch.cuda.is_current_stream_capturing()
     if explicit:
         plan = tuple(plan) if plan is not None else _DIRECT_FORMS[CONV_FORM]
     else:
         mode = 'fp16' if half else 'fp32x' if split else 'fp32'
-        tune = AUTOTUNE and cout > 1 and not capturing
-        plan, tabled = tabled_or_heuristic(key, mode, AUTOTUNE, has_winograd, wino_ok, pixels)
+        tune = AUTOTUNE and call.cw.cout > 1 and not capturing
+        plan, tabled = tabled_or_heuristic(key, mode, AUTOTUNE, has_winograd, call.wino_ok, call.B * call.Ho * call.Wo)
         if tabled and tune and fp32 and RETUNE_MARGIN > 0 and key not in _retuned:
             _retuned.add(key)                     # tools: the tabled plan against its candidates, replaced only when clearly beaten
             if reads_f4_operand(plan[0]) and has_winograd:
-                f4_operand()
-            new_plan = _tune_conv(lib, d, dev, f4_operand, incumbent=plan)
+                call.f4_operand()
+            new_plan = _tune_conv(lib, call, incumbent=plan)
             if new_plan != plan:
                 plan = TABLES[mode].chosen[key] = new_plan
         if not tabled:
             if tune:
-                plan = _tune_conv_half(lib, d, dev) if half else _tune_conv(lib, d, dev, f4_operand)
+                plan = _tune_conv_half(lib, d, call.x.device) if half else _tune_conv(lib, call)
             TABLES[mode].chosen[key] = plan
         if CONV_FORM == 'f2' and reads_f4_operand(plan[0]):
             plan = (as_f2(plan[0]), plan[1])
     d.w_winograd4 = None
     if not half and reads_f4_operand(plan[0]) and has_winograd:
-        f4_operand()
+        call.f4_operand()
     if TUNE_STREAM and not (explicit or half or split) and plan[0] in _STREAM_VARIANTS and key not in _stream_checked and not capturing:
         _stream_checked.add(key)
-        plan = FP32.chosen[key] = _tune_stream(lib, d, dev, plan)
+        plan = FP32.chosen[key] = _tune_stream(lib, d, call.x.device, plan)
     return plan

@@ -55,7 +55,6 @@ def release_scope(scope):
 # closure for every call of one (eager) frame; time_recorded() then times each distinct launch back to back between
 # two HIP events (torch events record on the current stream, which is the stream every kernel here is launched on).
 RECORD = None
-PROFILE = None          # kept for compatibility: any non-None value also forces the eager (non-graph) path
 # EVENT_TAP = [] makes the memory-readout launches (which stay eager between the captured stages) bracket themselves with
 # HIP events ON THEIR LAUNCH STREAM inside whatever region is running - bench.py's instrumented pass of the timed region.
 EVENT_TAP = None
@@ -77,7 +76,7 @@ def _tap_end(kind, e0, flop):
 
 
 def eager_only():
-    return RECORD is not None or PROFILE is not None
+    return RECORD is not None
 
 
 def time_recorded(records, reps=10):
@@ -285,63 +284,62 @@ def winograd_weights(w):
 
 # ---- convolutions ---------------------------------------------------------------------------------------------
 # Which plan (tile / algorithm / split-K) a call runs under is decided in conv_plan.py: plan tables, tuner, heuristic.
-conv_executed_mfma_flops = conv_plan.executed_mfma_flops
+class ConvCall:
+    """One prepared convolution, built once per call from keyword arguments (conv2d's, under its names): the operands, the epilogue, the
+    descriptor `d` handed to the library, and what is derived from them exactly once - the geometry, `wino_ok`, the plan key (the string
+    that indexes conv_plans*.json and names the RECORD entry) and the plan.  Every entry point below builds its calls from this.
+    `dilation` None: the plain entry point, with the operands of the precision mode and the plan of conv_plan.choose; an integer: the
+    dilated direct form (`plan` as given, None = the library's heuristic; `flags` passed on).  `folded`: the residual arrives inside the
+    output transform (conv2d_folded) - keyed and planned as the convolution with a residual that it is.  `alloc` False: a missing `out`
+    stays None until `alloc_out`."""
+    __slots__ = ('x', 'cin', 'ldin', 'cw', 'out', 'out_ld', 'out_dtype', 'res', 'res_ld', 'res_broadcast', 'relu_in', 'relu_out', 'dilation',
+                 'flags', 'half', 'folded', 'precision', 'd', 'B', 'H', 'W', 'Ho', 'Wo', 'wino_ok', 'key', 'plan', 'need', 'ws')
 
+    def __init__(self, *, x, cw, cin=None, in_ld=None, out=None, out_ld=None, out_dtype=torch.float32, res=None, res_ld=None, res_broadcast=False,
+                 relu_in=False, relu_out=False, plan=None, half=False, folded=False, dilation=None, flags=0, alloc=True):
+        B, H, W, dense_ld = x.shape
+        cin, ldin = cw.cin if cin is None else cin, dense_ld if in_ld is None else in_ld
+        self.x, self.cw, self.cin, self.ldin, self.out, self.out_dtype = x, cw, cin, ldin, out, out_dtype
+        self.res, self.res_broadcast, self.relu_in, self.relu_out = res, res_broadcast, relu_in, relu_out
+        self.dilation, self.flags, self.half, self.folded, self.precision = dilation, flags, half, folded, _PRECISION
+        self.B, self.H, self.W, self.need, self.ws = B, H, W, 0, None            # need, ws: the workspace `run` takes
+        dil = 1 if dilation is None else dilation
+        self.Ho = (H + 2 * cw.pad - dil * (cw.kh - 1) - 1) // cw.stride + 1
+        self.Wo = (W + 2 * cw.pad - dil * (cw.kw - 1) - 1) // cw.stride + 1
+        out_ld = self.out_ld = cw.cout if out is None else out.shape[-1] if out_ld is None else out_ld
+        d = self.d = ConvDesc()
+        d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = B, H, W, cin, ldin
+        d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
+        d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
+        d.res = res.data_ptr() if res is not None else None
+        # `res_ld`: the residual is a channel slice of a wider buffer; `res_broadcast`: res [1,Ho,Wo,C] added to every batch element
+        self.res_ld = d.ldres = 0 if res is None else res_ld if res_ld is not None else res.shape[-1]
+        d.res_broadcast = int(bool(res_broadcast and res is not None))
+        d.out = out.data_ptr() if out is not None else None; d.ldout = out_ld
+        d.relu_in, d.relu_out = int(relu_in), int(relu_out)
+        self.wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
+        key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad}{"" if dilation is None else f"d{dilation}"} ' \
+              f'r{int(res is not None or folded)}{int(relu_in)}{int(relu_out)}'
+        self.key = f'h{key}o{int(out_dtype == torch.float16)}' if half else key
+        if alloc and out is None:
+            self.alloc_out()
+        if dilation is None:
+            self.plan = conv_plan.choose(load(), self, self._mode_operands(plan))
+        else:
+            self.plan = tuple(plan) if plan is not None else (conv_plan.HEURISTIC, 0)
+        d.plan_tile, d.plan_splitk = self.plan
 
-def _f4_operand(cw, d):
-    """Point `d` at the F(4x4,3x3) operand of `cw` (and at its split form in 'fp32x'), built on first use."""
-    if cw.wu4 is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('conv2d: the F(4x4) operand must be built before graph capture (run the stage eagerly once)')
-        cw.wu4 = winograd4_weights(cw.w)
-    d.w_winograd4 = cw.wu4.data_ptr()
-    if d.arith == 1:
-        cw.ensure_split()
-        d.w_winograd4_split = cw.wu4_sp.data_ptr()
-
-
-def _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out):
-    """The descriptor fields every convolution entry point takes: operands, geometry, epilogue."""
-    d = ConvDesc()
-    d.inp = x.data_ptr(); d.B, d.H, d.W, d.Cin, d.ldin = x.shape[0], x.shape[1], x.shape[2], cin, ldin
-    d.w = cw.w.data_ptr(); d.Cout, d.KH, d.KW, d.stride, d.pad = cw.cout, cw.kh, cw.kw, cw.stride, cw.pad
-    d.scale = cw.scale.data_ptr(); d.shift = cw.shift.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.ldres = res.shape[-1] if res is not None else 0
-    d.out = out.data_ptr() if out is not None else None; d.ldout = out_ld
-    d.relu_in, d.relu_out = int(relu_in), int(relu_out)
-    return d
-
-
-def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, alloc=True, folded=False,
-               res_ld=None):
-    """What comes before the launch of one convolution of either path: the output buffer (`alloc` False: left None for the caller),
-    the descriptor with the operands of the precision mode and the plan (conv_plan.choose).  `folded`: the residual arrives inside the
-    output transform (conv2d_folded) - planned as the convolution with a residual that it is, the plan tables being keyed by the
-    epilogue too.  -> (d, out, out_ld, key, plan, wino_ok)"""
-    lib = load()
-    B, H, W = x.shape[0], x.shape[1], x.shape[2]
-    Ho = (H + 2 * cw.pad - cw.kh) // cw.stride + 1
-    Wo = (W + 2 * cw.pad - cw.kw) // cw.stride + 1
-    if out is None:
-        out, out_ld = (torch.empty((B, Ho, Wo, cw.cout), dtype=out_dtype, device=x.device) if alloc else None), cw.cout
-    elif out_ld is None:
-        out_ld = out.shape[-1]
-    d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
-    d.res_broadcast = int(bool(res_broadcast and res is not None))   # res [1,Ho,Wo,C] added to every batch element
-    if res is not None and res_ld is not None:
-        d.ldres = res_ld                     # the residual is a channel slice of a wider buffer
-    wino_ok = out_ld % 4 == 0 and d.ldres % 4 == 0
-    key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad} r{int(res is not None or folded)}{int(relu_in)}{int(relu_out)}'
-    if half:
-        d.in_half, d.out_half, d.w_half = 1, int(out.dtype == torch.float16), cw.half().data_ptr()
-        key = f'h{key}o{d.out_half}'
-    else:
+    def _mode_operands(self, plan):
+        """Point the descriptor at the operands of the precision mode -> `plan`, or the plan the 'fp16w' mode puts in its place."""
+        d, cw = self.d, self.cw
+        if self.half:
+            d.in_half, d.out_half, d.w_half = 1, int(self.out_dtype == torch.float16), cw.half().data_ptr()
+            return plan
         d.w_winograd = cw.wu.data_ptr() if cw.wu is not None else None
-        if _PRECISION == 'fp16w' and cw.wu_f16 is not None and plan is None and wino_ok:
+        if self.precision == 'fp16w' and cw.wu_f16 is not None and plan is None and self.wino_ok:
             d.w_winograd_f16 = cw.wu_f16.data_ptr()
             plan = (conv_plan.F2_F16, 1)         # the library falls back to the fp32 Winograd tile if its own conditions fail
-        if _PRECISION == 'fp32x' and cw.cout > 1:
+        if self.precision == 'fp32x' and cw.cout > 1:
             # split-operand arithmetic for every GEMM-shaped path (the Cout = 1 mask head is a GEMV on the fp32 VALU)
             if cw.sp_shift is None or (cw.wu4 is not None and cw.wu4_sp is None):
                 if torch.cuda.is_current_stream_capturing():
@@ -354,33 +352,60 @@ def _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out,
             d.w_winograd_split = cw.wu_sp.data_ptr() if cw.wu_sp is not None else None
             d.w_winograd4_split = cw.wu4_sp.data_ptr() if cw.wu4_sp is not None else None    # taken only by an F(4x4) plan
             d.scale = cw.scale_sp.data_ptr()
-    plan = conv_plan.choose(lib, d, key, plan, x.device, _PRECISION, cw.cout, cw.wu is not None, wino_ok, B * Ho * Wo,
-                            lambda: _f4_operand(cw, d))
-    d.plan_tile, d.plan_splitk = plan
-    return d, out, out_ld, key, plan, wino_ok
+        return plan
+
+    def f4_operand(self):
+        """Point the descriptor at the F(4x4,3x3) operand of the weights (and at its split form in 'fp32x'), built on first use."""
+        d, cw = self.d, self.cw
+        if cw.wu4 is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('conv2d: the F(4x4) operand must be built before graph capture (run the stage eagerly once)')
+            cw.wu4 = winograd4_weights(cw.w)
+        d.w_winograd4 = cw.wu4.data_ptr()
+        if d.arith == 1:
+            cw.ensure_split()
+            d.w_winograd4_split = cw.wu4_sp.data_ptr()
+
+    def alloc_out(self):
+        """A fresh output buffer of the convolution's own shape (the caller gave none), entered into the descriptor -> out."""
+        self.out = torch.empty((self.B, self.Ho, self.Wo, self.cw.cout), dtype=self.out_dtype, device=self.x.device)
+        self.d.out = self.out.data_ptr()
+        return self.out
+
+    def workspace_bytes(self):
+        lib, d = load(), C.byref(self.d)
+        return lib.xmem_conv2d_workspace_bytes(d) if self.dilation is None else lib.xmem_conv2d_dilated_workspace_bytes(d, self.dilation)
+
+    def launch(self):
+        """The plain or the dilated entry point on the current stream, with the workspace `run` took: re-launchable -> status."""
+        if self.dilation is None:
+            return load().xmem_conv2d_nhwc(C.byref(self.d), ptr(self.ws), self.need, stream_ptr())
+        return load().xmem_conv2d_nhwc_dilated(C.byref(self.d), self.dilation, self.flags, ptr(self.ws), self.need, stream_ptr())
+
+    def run(self):
+        """Output buffer, workspace, launch, and the RECORD entry -> out."""
+        if self.out is None:
+            self.alloc_out()
+        self.need = self.workspace_bytes()
+        self.ws = workspace(self.need, self.x.device, 'conv') if self.need else None
+        check(self.launch())
+        if RECORD is not None:
+            self.record(self.launch)
+        return self.out
+
+    def record(self, launch):
+        """The RECORD entry of this convolution, `launch` being what runs it again (bench.py and tools/*_table.py read the entries)."""
+        cw, plan = self.cw, self.plan
+        info = dict(dilation=self.dilation) if self.dilation is not None else \
+            dict(relu_in=bool(self.relu_in), relu_out=bool(self.relu_out), in_ld=self.ldin, cin=self.cin, out_ld=self.out_ld,
+                 res_broadcast=bool(self.res_broadcast), plan=tuple(plan),
+                 executed_mfma_flops=conv_plan.executed_mfma_flops(self.B, self.Ho, self.Wo, self.cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad,
+                                                                   plan[0], bool(self.d.w_winograd) and self.wino_ok, half=self.half))
+        RECORD.append(('conv', self.key, 2.0 * self.B * self.Ho * self.Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch,
+                       (self.x, self.out, self.res, cw, self.ws, info)))
 
 
-def _conv_run(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half, res_ld=None):
-    """One convolution of either path: `_conv_prep`, workspace, launch on the current stream, and the RECORD entry."""
-    lib = load()
-    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cin, ldin, out, out_ld, out_dtype, res, relu_in, relu_out, res_broadcast, plan, half,
-                                                    res_ld=res_ld)
-    B, Ho, Wo = x.shape[0], (x.shape[1] + 2 * cw.pad - cw.kh) // cw.stride + 1, (x.shape[2] + 2 * cw.pad - cw.kw) // cw.stride + 1
-    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
-    ws = workspace(need, x.device, 'conv') if need else None
-    launch = lambda: lib.xmem_conv2d_nhwc(C.byref(d), ptr(ws), need, stream_ptr())
-    check(launch())
-    if RECORD is not None:
-        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch,
-                       (x, out, res, cw, ws, dict(relu_in=bool(relu_in), relu_out=bool(relu_out), in_ld=ldin, cin=cin, out_ld=out_ld,
-                                                  res_broadcast=bool(res_broadcast), plan=tuple(plan),
-                                                  executed_mfma_flops=conv_plan.executed_mfma_flops(
-                                                      B, Ho, Wo, cin, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, plan[0],
-                                                      bool(d.w_winograd) and wino_ok, half=half)))))
-    return out
-
-
-def _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype):
+def _conv2d_half(x, cw, *, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype):
     """The fp16 loop's convolution: x [B,H,W,C] halfs (pixel stride in_ld halfs), half weights, direct implicit GEMM on the fp16
     MFMA, fp32 accumulation + epilogue; output (and residual) halfs, or float32 with out_dtype=torch.float32 (key projection,
     mask head).  Input channels beyond the layer's own (a buffer padded to a multiple of 8) must be zero: the half weights are
@@ -411,7 +436,8 @@ def _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, r
         raise RuntimeError('conv2d (half): out buffer dtype does not match out_dtype')
     if res is not None and res.dtype != odt:
         raise RuntimeError('conv2d (half): the residual must have the output storage type')
-    return _conv_run(x, cw, cin_h, ldin, out, out_ld, odt, res, relu_in, relu_out, res_broadcast, plan, half=True)
+    return ConvCall(x=x, cw=cw, cin=cin_h, in_ld=ldin, out=out, out_ld=out_ld, out_dtype=odt, res=res, res_broadcast=res_broadcast,
+                    relu_in=relu_in, relu_out=relu_out, plan=plan, half=True).run()
 
 
 def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
@@ -422,18 +448,18 @@ def conv2d(x, cw, out=None, out_ld=None, res=None, relu_in=False, relu_out=False
     if res_ld is not None and res is not None and res_ld != res.shape[-1] and (x.dtype == torch.float16 or cw.dilation != 1):
         raise RuntimeError('conv2d: a residual with its own pixel stride is taken by the fp32, dilation-1 forms only')
     if x.dtype == torch.float16:
-        return _conv2d_half(x, cw, out, out_ld, res, relu_in, relu_out, in_ld, cin, plan, res_broadcast, out_dtype)
+        return _conv2d_half(x, cw, out=out, out_ld=out_ld, res=res, relu_in=relu_in, relu_out=relu_out, in_ld=in_ld, cin=cin, plan=plan,
+                            res_broadcast=res_broadcast, out_dtype=out_dtype)
     if out_dtype is not None and out_dtype != torch.float32:
         raise RuntimeError('conv2d: a float32 input gives a float32 output (the fp16 loop converts at the max-pool after the stems)')
     if cw.dilation != 1:
         if res_broadcast:
             raise RuntimeError('conv2d: a dilated convolution takes no broadcast residual')
         return conv2d_dilated(x, cw, out=out, out_ld=out_ld, res=res, relu_in=relu_in, relu_out=relu_out, in_ld=in_ld, cin=cin, plan=plan)
-    cin = cin if cin is not None else cw.cin
-    if cin != cw.cin:
+    if cin is not None and cin != cw.cin:
         raise RuntimeError(f'conv2d: weight expects Cin={cw.cin}, got {cin}')
-    ldin = in_ld if in_ld is not None else x.shape[3]
-    return _conv_run(x, cw, cin, ldin, out, out_ld, torch.float32, res, relu_in, relu_out, res_broadcast, plan, half=False, res_ld=res_ld)
+    return ConvCall(x=x, cw=cw, in_ld=in_ld, out=out, out_ld=out_ld, res=res, res_ld=res_ld, res_broadcast=res_broadcast,
+                    relu_in=relu_in, relu_out=relu_out, plan=plan).run()
 
 
 # ---- shared Winograd transforms (include/xmem_hip.h: SHARED WINOGRAD TRANSFORMS) -------------------------------------------------
@@ -445,17 +471,16 @@ SHARED_STATS = {'shared_input': 0, 'folded': 0, 'separate': 0}      # calls that
 
 
 class DeferredConv:
-    """A convolution of `conv2d_shared` that stopped after its position GEMMs: its descriptor and its M, for `conv2d_folded`."""
-    __slots__ = ('d', 'm', 'm_bytes', 'shape', 'keep')
+    """A convolution of `conv2d_shared` that stopped after its position GEMMs: its call and its M, for `conv2d_folded`."""
+    __slots__ = ('call', 'm', 'm_bytes')
 
-    def __init__(self, d, m, m_bytes, shape, keep):
-        self.d, self.m, self.m_bytes, self.shape, self.keep = d, m, m_bytes, shape, keep
+    def __init__(self, call, m, m_bytes):
+        self.call, self.m, self.m_bytes = call, m, m_bytes
 
     def finish(self):
         """The convolution's own output transform (the fold did not apply) -> its output tensor."""
-        out = torch.empty(self.shape, dtype=torch.float32, device=self.m.device)
-        self.d.out, self.d.ldout = out.data_ptr(), self.shape[3]
-        check(load().xmem_conv2d_output_from_m(C.byref(self.d), ptr(self.m), self.m_bytes, stream_ptr()))
+        out = self.call.alloc_out()
+        check(load().xmem_conv2d_output_from_m(C.byref(self.call.d), ptr(self.m), self.m_bytes, stream_ptr()))
         return out
 
 
@@ -470,40 +495,34 @@ def conv2d_shared(x, convs, in_ld=None, cin=None, defer=None):
         SHARED_STATS['separate'] += 1
         return separate()
     lib = load()
-    ldin = in_ld if in_ld is not None else x.shape[3]
-    preps = []
+    calls = []
     for kw in convs:
         cw = kw['cw']
-        c = cin if cin is not None else cw.cin
-        if c != cw.cin:
-            raise RuntimeError(f'conv2d_shared: weight expects Cin={cw.cin}, got {c}')
-        preps.append(_conv_prep(x, cw, c, ldin, kw.get('out'), kw.get('out_ld'), torch.float32, kw.get('res'), kw.get('relu_in', False),
-                                kw.get('relu_out', False), kw.get('res_broadcast', False), kw.get('plan'), False, alloc=False))
-    n = len(preps)
-    descs = (C.POINTER(ConvDesc) * n)(*[C.pointer(p[0]) for p in preps])
-    placeholder = x.data_ptr()           # the size query reads no `out`; a descriptor without one is invalid
-    for p in preps:
-        if p[1] is None:
-            p[0].out = placeholder
+        if cin is not None and cin != cw.cin:
+            raise RuntimeError(f'conv2d_shared: weight expects Cin={cw.cin}, got {cin}')
+        calls.append(ConvCall(x=x, cw=cw, in_ld=in_ld, out=kw.get('out'), out_ld=kw.get('out_ld'), res=kw.get('res'),
+                              res_broadcast=kw.get('res_broadcast', False), relu_in=kw.get('relu_in', False),
+                              relu_out=kw.get('relu_out', False), plan=kw.get('plan'), alloc=False))
+    n = len(calls)
+    descs = (C.POINTER(ConvDesc) * n)(*[C.pointer(c.d) for c in calls])
+    for c in calls:
+        if c.out is None:
+            c.d.out = x.data_ptr()       # a placeholder: the size query reads no `out`; a descriptor without one is invalid
     need = lib.xmem_conv2d_shared_input_workspace_bytes(descs, n)
     if not need:
         SHARED_STATS['separate'] += 1
         return separate()
-    B, Ho, Wo = x.shape[0], x.shape[1], x.shape[2]
-    outs, m, m_bytes = [], None, 0
+    outs = []
     dm, dmb = (C.c_void_p * n)(), (C.c_size_t * n)()
-    for i, (d, out, out_ld, key, plan, wino_ok) in enumerate(preps):
-        if i == defer and out is None:
-            m_bytes = lib.xmem_conv2d_m_bytes(C.byref(d))
+    for i, c in enumerate(calls):
+        if i == defer and c.out is None:
+            m_bytes = lib.xmem_conv2d_m_bytes(C.byref(c.d))
             m = workspace(m_bytes, x.device, 'conv_m')       # a buffer of its own: the convolutions in between reuse 'conv'
             dm[i], dmb[i] = m.data_ptr(), m_bytes
-            d.out = m.data_ptr()                             # never written
-            outs.append(DeferredConv(d, m, m_bytes, (B, Ho, Wo, convs[i]['cw'].cout), (x, convs[i]['cw'], convs[i].get('res'))))
-            continue
-        if out is None:
-            out = torch.empty((B, Ho, Wo, convs[i]['cw'].cout), dtype=torch.float32, device=x.device)
-            d.out = out.data_ptr()
-        outs.append(out)
+            c.d.out = m.data_ptr()                           # never written
+            outs.append(DeferredConv(c, m, m_bytes))
+        else:
+            outs.append(c.out if c.out is not None else c.alloc_out())
     ws = workspace(need, x.device, 'conv')
     check(lib.xmem_conv2d_shared_input(descs, n, dm, dmb, ptr(ws), need, stream_ptr()))
     SHARED_STATS['shared_input'] += 1
@@ -515,19 +534,17 @@ def conv2d_folded(x, cw, branch, out=None, out_ld=None, relu_in=False, relu_out=
     transform is then formed inside this convolution's (one launch, the branch result never stored), or already a tensor."""
     if not isinstance(branch, DeferredConv):
         return conv2d(x, cw, out=out, out_ld=out_ld, res=branch, relu_in=relu_in, relu_out=relu_out, plan=plan)
-    lib = load()
     _req(x, 'conv2d_folded input')
-    d, out, out_ld, key, plan, wino_ok = _conv_prep(x, cw, cw.cin, x.shape[3], out, out_ld, torch.float32, None, relu_in, relu_out,
-                                                    False, plan, False, folded=True)
-    need = lib.xmem_conv2d_workspace_bytes(C.byref(d))
+    call = ConvCall(x=x, cw=cw, out=out, out_ld=out_ld, relu_in=relu_in, relu_out=relu_out, plan=plan, folded=True)
+    need = call.workspace_bytes()
     ws = workspace(need, x.device, 'conv') if need else None
-    rc = lib.xmem_conv2d_nhwc_folded(C.byref(d), C.byref(branch.d), ptr(branch.m), branch.m_bytes, ptr(ws), need, stream_ptr())
+    rc = load().xmem_conv2d_nhwc_folded(C.byref(call.d), C.byref(branch.call.d), ptr(branch.m), branch.m_bytes, ptr(ws), need, stream_ptr())
     if rc == _lib.UNSUPPORTED:
         SHARED_STATS['separate'] += 1
-        return conv2d(x, cw, out=out, out_ld=out_ld, res=branch.finish(), relu_in=relu_in, relu_out=relu_out, plan=plan)
+        return conv2d(x, cw, out=call.out, out_ld=call.out_ld, res=branch.finish(), relu_in=relu_in, relu_out=relu_out, plan=call.plan)
     check(rc)
     SHARED_STATS['folded'] += 1
-    return out
+    return call.out
 
 
 # ---- bottleneck pair (include/xmem_hip.h: BOTTLENECK PAIR) -----------------------------------------------------------------------
@@ -564,21 +581,18 @@ def conv2d_pointwise_pair(o, cw_expand, res, cw_reduce, y=None, y_ld=None, z=Non
                     res_ld=res_ld)
         zz = conv2d(yy, cw_reduce, out=z, out_ld=z_ld, relu_out=True, in_ld=y_ld, plan=plans[1])
         return yy, zz
-    lib = load()
-    ldin = in_ld if in_ld is not None else o.shape[3]
-    de, yy, yy_ld, _, _, _ = _conv_prep(o, cw_expand, cw_expand.cin, ldin, y, y_ld, torch.float32, res, False, True, False, plans[0], False,
-                                        res_ld=res_ld)
-    dr, zz, zz_ld, _, _, _ = _conv_prep(yy, cw_reduce, cw_reduce.cin, yy_ld, z, z_ld, torch.float32, None, False, True, False, plans[1], False)
-    rc = lib.xmem_conv2d_pointwise_pair(C.byref(de), C.byref(dr), stream_ptr())
+    e = ConvCall(x=o, cw=cw_expand, in_ld=in_ld, out=y, out_ld=y_ld, res=res, res_ld=res_ld, relu_out=True, plan=plans[0])
+    r = ConvCall(x=e.out, cw=cw_reduce, in_ld=e.out_ld, out=z, out_ld=z_ld, relu_out=True, plan=plans[1])
+    rc = load().xmem_conv2d_pointwise_pair(C.byref(e.d), C.byref(r.d), stream_ptr())
     if rc == _lib.UNSUPPORTED:
-        # (yy / zz were allocated above when the caller gave none: the separate calls fill the same buffers)
+        # (e.out / r.out were allocated above when the caller gave none: the separate calls fill the same buffers)
         PAIR_STATS['separate'] += 1
-        conv2d(o, cw_expand, out=yy, out_ld=yy_ld, res=res, relu_out=True, in_ld=in_ld, plan=plans[0], res_ld=res_ld)
-        conv2d(yy, cw_reduce, out=zz, out_ld=zz_ld, relu_out=True, in_ld=yy_ld, plan=plans[1])
-        return yy, zz
+        conv2d(o, cw_expand, out=e.out, out_ld=e.out_ld, res=res, relu_out=True, in_ld=in_ld, plan=plans[0], res_ld=res_ld)
+        conv2d(e.out, cw_reduce, out=r.out, out_ld=r.out_ld, relu_out=True, in_ld=e.out_ld, plan=plans[1])
+        return e.out, r.out
     check(rc)
     PAIR_STATS['pair'] += 1
-    return yy, zz
+    return e.out, r.out
 
 
 def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_in=False, relu_out=False, in_ld=None, cin=None, plan=None,
@@ -588,31 +602,13 @@ def conv2d_dilated(x, cw, dilation=None, out=None, out_ld=None, res=None, relu_i
     the library's heuristic); tap_skip=False keeps every tap (measurement only: the same bits)."""
     _req(x, 'conv2d_dilated input')
     dil = int(cw.dilation if dilation is None else dilation)
-    cin = cin if cin is not None else cw.cin
-    if cin != cw.cin:
+    if cin is not None and cin != cw.cin:
         raise RuntimeError(f'conv2d_dilated: weight expects Cin={cw.cin}, got {cin}')
-    ldin = in_ld if in_ld is not None else x.shape[3]
-    lib = load()
-    B, H, W = x.shape[0], x.shape[1], x.shape[2]
-    Ho = (H + 2 * cw.pad - dil * (cw.kh - 1) - 1) // cw.stride + 1
-    Wo = (W + 2 * cw.pad - dil * (cw.kw - 1) - 1) // cw.stride + 1
-    if Ho <= 0 or Wo <= 0:
-        raise RuntimeError(f'conv2d_dilated: empty output for a {H}x{W} input (pad {cw.pad}, dilation {dil})')
-    if out is None:
-        out, out_ld = torch.empty((B, Ho, Wo, cw.cout), dtype=torch.float32, device=x.device), cw.cout
-    elif out_ld is None:
-        out_ld = out.shape[-1]
-    d = _conv_desc(x, cw, cin, ldin, out, out_ld, res, relu_in, relu_out)
-    d.plan_tile, d.plan_splitk = tuple(plan) if plan is not None else (0, 0)
-    flags = 0 if tap_skip else _lib.DILATED_NO_TAP_SKIP
-    need = lib.xmem_conv2d_dilated_workspace_bytes(C.byref(d), dil)
-    ws = workspace(need, x.device, 'conv') if need else None
-    launch = lambda: lib.xmem_conv2d_nhwc_dilated(C.byref(d), dil, flags, ptr(ws), need, stream_ptr())
-    check(launch())
-    if RECORD is not None:
-        key = f'{B}x{H}x{W}x{cin}/{ldin}->{cw.cout}/{out_ld} k{cw.kh}s{cw.stride}p{cw.pad}d{dil} r{int(res is not None)}{int(relu_in)}{int(relu_out)}'
-        RECORD.append(('conv', key, 2.0 * B * Ho * Wo * cw.cout * cw.kh * cw.kw * cw.cin_true, launch, (x, out, res, cw, ws, dict(dilation=dil))))
-    return out
+    call = ConvCall(x=x, cw=cw, in_ld=in_ld, out=out, out_ld=out_ld, res=res, relu_in=relu_in, relu_out=relu_out, plan=plan,
+                    dilation=dil, flags=0 if tap_skip else _lib.DILATED_NO_TAP_SKIP, alloc=False)
+    if call.Ho <= 0 or call.Wo <= 0:
+        raise RuntimeError(f'conv2d_dilated: empty output for a {call.H}x{call.W} input (pad {cw.pad}, dilation {dil})')
+    return call.run()
 
 
 _HIPRT = None
@@ -740,11 +736,7 @@ def mask_head_gather(g16, g8, g4, cw, hidden, g4d, cat, cat_off):
     check(launch())
     if RECORD is not None:
         # the mask head's own entry (key, FLOPs, plan) as conv2d writes it: the survey of the convolutions still counts the layer
-        H, W = 4 * h, 4 * w
-        key = f'{K}x{H}x{W}x{c4}/{c4}->1/1 k3s1p1 r010'
-        RECORD.append(('conv', key, 2.0 * K * H * W * 9 * cw.cin_true, launch,
-                       (g4, logits, None, cw, None, dict(relu_in=True, relu_out=False, in_ld=c4, cin=c4, out_ld=1, res_broadcast=False,
-                                                         plan=(conv_plan.HEURISTIC, 0), executed_mfma_flops=0.0))))
+        ConvCall(x=g4, cw=cw, out=logits, relu_in=True, plan=(conv_plan.HEURISTIC, 0)).record(launch)
     return logits
 
 
