@@ -24,15 +24,14 @@ import argparse
 import json
 import os
 import sys
-import weakref
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, stages
 from .arch import BN_EPS, click_state_dict_spec
-from .network import XMem
+from .hipnet import HipNet, check_state_dict
 
 NORM_RADIUS = 260.0             # fbrs_controller.py:8
 ASPP_RATES = (12, 24, 36)       # deeplab_v3.py:43
@@ -53,35 +52,48 @@ def _ceil_half(n):
     return (n - 1) // 2 + 1
 
 
-class ClickNet:
+def run_click_stage(cache, forward, image, points, cap, with_flip):
+    """The stage of `cache` (a StageCache) for the geometry of `image` [3,h,w] and `with_flip`, captured from forward(image, clicks,
+    counts, with_flip) when the cache does not hold it, replayed on `image` and `points` -> its static output.
+    points [2n,2] (row, col) as get_points_nd lays one clicks list out (n positive then n negative entries, (-1, -1) = padding) fill the
+    stage's click buffers: clicks [2,cap,2], padded with -1, and counts [2] = (n, n)."""
+    pts = np.asarray(points, dtype=np.float32).reshape(2, -1, 2)
+    n = pts.shape[1]
+    host = np.full((2, cap, 2), -1.0, np.float32)
+    host[:, :n] = pts
+    clicks, counts = torch.from_numpy(host), torch.from_numpy(np.array([n, n], np.int32))
+    key = (int(image.shape[-2]), int(image.shape[-1]), bool(with_flip))
+    st = cache.lookup(key)
+    if st is None:
+        dev = image.device
+        st = cache.put(key, stages.capture(lambda *a: forward(*a, with_flip), (image.clone(), clicks.to(dev), counts.to(dev))))
+    return st.replay((image, clicks, counts))
+
+
+def grown_capacity(cap, n):
+    """`cap` doubled until it holds n clicks per polarity.  The caller drops its captured graphs when it grows: they hold the old buffers."""
+    while cap < n:
+        cap *= 2
+    return cap
+
+
+class ClickNet(HipNet):
     """DistMapsModel(DeepLabV3Plus(resnet50), SepConvHead) on HIP kernels (fp32)."""
 
-    _conv_w = XMem._conv_w
-    _bottleneck = XMem._bottleneck
-    _stage = XMem._stage
+    _synthetic = 'synthetic_click_state_dict'
+    ignored_keys = ('aspp_dropout',)
 
     def __init__(self, model_path=None, device=None):
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        super().__init__(torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device()),
+                         max_stages=lambda: MAX_GEOMETRIES)
         self.deeplab_ch = 128
-        self._sd = None
-        self._w = {}
-        self._graphs = OrderedDict()   # (h, w, with_flip) -> (graph, static inputs, static output), least recently used first
+        self._graphs = self._stages    # (h, w, with_flip) -> Stage, least recently used first
         self._brs = {}                 # insertion mode -> the f-BRS engine with its own captured graphs (click_brs.engine_for)
         self._cap = CLICK_CAPACITY
-        self.captures = 0
-        self._scope = ops.new_scope()
-        weakref.finalize(self, ops.release_scope, self._scope)
         if model_path is not None:
             self.load_weights(model_path)
 
     # ---- weights ----------------------------------------------------------------------------------
-    def load_weights(self, src):
-        """A checkpoint path or a state dict (load_is_model, fbrs/inference/utils.py:21-37)."""
-        if isinstance(src, (str, bytes)) or hasattr(src, '__fspath__'):
-            src = torch.load(src, map_location='cpu', weights_only=True)
-        self.load_state_dict(src)
-        return self
-
     def load_state_dict(self, sd, strict=True):
         """As load_deeplab_is_model (fbrs/inference/utils.py:67-100): the backbone is identified by its parameter count, deeplab_ch is
         read from aspp.project.0.weight, `aspp_dropout` and num_batches_tracked are ignored."""
@@ -97,37 +109,14 @@ class ClickNet:
         ch = int(proj[0].shape[0])
         if ch % 8:
             raise NotImplementedError(f'ClickNet: deeplab_ch = {ch} is not a multiple of 8')
-        spec = state_dict_spec(ch)
-        ignored = lambda k: k == 'aspp_dropout' or k.endswith('num_batches_tracked')
         if strict:
-            missing = [k for k in spec if k not in sd and not ignored(k)]
-            unexpected = [k for k in sd if k not in spec and not ignored(k)]
-            if missing or unexpected:
-                raise RuntimeError(f'Error(s) in loading state_dict for ClickNet: missing {missing[:5]}..., unexpected {unexpected[:5]}...')
-        for k, shape in spec.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shape) and not (len(shape) == 0 and sd[k].numel() == 1):
-                raise RuntimeError(f'size mismatch for {k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(shape)}')
+            check_state_dict(sd, state_dict_spec(ch), 'ClickNet', self.ignored_keys)
         self.deeplab_ch = ch
-        self._sd = {k: v.detach().to('cpu') for k, v in sd.items() if k != 'aspp_dropout'}
-        self._graphs.clear()
+        self._adopt(sd)
+
+    def _weights_replaced(self):
+        super()._weights_replaced()
         self._brs.clear()
-        self._upload()
-
-    def state_dict(self):
-        return dict(self._sd) if self._sd is not None else {}
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        if self._sd is not None:
-            self._graphs.clear()
-            self._brs.clear()
-            self._upload()
-        return self
-
-    def eval(self):
-        return self
 
     def _separable(self, W, key, prefix):
         """SeparableConv2d: depthwise weights [C,1,3,3] -> [9][C]; the pointwise convolution carries the BatchNorm (and ReLU)."""
@@ -147,8 +136,6 @@ class ClickNet:
                                torch.zeros(cw.cin_true, device=dev), 1, 0)
 
     def _upload(self):
-        if self.device.type != 'cuda':
-            raise RuntimeError('xmem2_amd.ClickNet runs on an MI355X (HIP) device only; there is no CPU path')
         sd, W = self._sd, {}
         # rgb_conv (is_deeplab_model.py:36-41): Conv(5, 8) -> LeakyReLU -> BN -> Conv(8, 3); the BN is folded into the second convolution
         d = lambda k: sd[k].double()
@@ -192,11 +179,6 @@ class ClickNet:
         h2 = W['head.2']
         W['head.2T'] = (h2.w[0, 0, 0, :h2.cin_true] * h2.scale[0]).contiguous()       # one output channel: its adjoint is an outer product
         self._w = W
-
-    def _need_weights(self):
-        if not self._w:
-            raise RuntimeError('ClickNet: no weights loaded (load_weights(path) or load_state_dict(sd); '
-                               'xmem2_amd.synth.synthetic_click_state_dict gives conditioned synthetic ones)')
 
     # ---- forward (NHWC) -------------------------------------------------------------------------
     def features(self, x):
@@ -263,37 +245,12 @@ class ClickNet:
         clicks list out: n positive then n negative entries, (-1, -1) = padding -> prob [h,w], sigmoid of the (flip-averaged) logits.
         The returned tensor is the graph's static buffer: valid until the next call at the same geometry."""
         self._need_weights()
-        pts = np.asarray(points, dtype=np.float32).reshape(2, -1, 2)
-        n = pts.shape[1]
+        n = np.asarray(points).size // 4
         if n > self._cap:                      # grow the click buffers: every captured graph holds the old ones
-            while self._cap < n:
-                self._cap *= 2
+            self._cap = grown_capacity(self._cap, n)
             self._graphs.clear()
-        host = np.full((2, self._cap, 2), -1.0, np.float32)
-        host[:, :n] = pts
-        host_clicks, host_counts = torch.from_numpy(host), torch.from_numpy(np.array([n, n], np.int32))
-        h, w = int(image.shape[-2]), int(image.shape[-1])
-        key = (h, w, bool(with_flip))
-        st = self._graphs.get(key)
         with ops.ws_scope(f'@click#{self._scope}#'):
-            if st is None:
-                while len(self._graphs) >= MAX_GEOMETRIES:
-                    self._graphs.popitem(last=False)
-                static_in = (image.clone(), host_clicks.to(self.device), host_counts.to(self.device))
-                self._forward(*static_in, with_flip)          # warm-up: sizes every workspace and picks the plans
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static_out = self._forward(*static_in, with_flip)
-                st = self._graphs[key] = (graph, static_in, static_out)
-                self.captures += 1
-            else:
-                self._graphs.move_to_end(key)
-            graph, static_in, static_out = st
-            for dst, src in zip(static_in, (image, host_clicks, host_counts)):
-                dst.copy_(src)
-            graph.replay()
-        return static_out
+            return run_click_stage(self._graphs, self._forward, image, points, self._cap, with_flip)
 
 
 # ---- the predictor's host logic (fbrs/utils/misc.py, fbrs/inference/transforms/zoom_in.py) ----------------------------

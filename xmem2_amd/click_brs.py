@@ -21,13 +21,12 @@ captured graphs of one network and insertion mode, ``FeatureBRSPredictor`` the p
 with the reference controller's defaults.  'f-BRS-A', 'RGB-BRS' and 'DistMap-BRS' need the adjoint of the ASPP or of the whole
 backbone and are not built.
 """
-from collections import OrderedDict
-
 import numpy as np
 import torch
 
-from . import ops
-from .click import BRS_MODES, CLICK_CAPACITY, MAX_GEOMETRIES, NORM_RADIUS, Click, FBRSController, NoBRSPredictor, ZoomIn, get_points_nd
+from . import ops, stages
+from .click import (BRS_MODES, CLICK_CAPACITY, MAX_GEOMETRIES, NORM_RADIUS, Click, FBRSController, NoBRSPredictor, ZoomIn, get_points_nd,
+                    grown_capacity, run_click_stage)
 
 INSERTION_MODES = {'f-BRS-B': 'after_aspp', 'f-BRS-C': 'after_deeplab'}       # predictors/__init__.py:49-53
 LBFGS_DEFAULTS = {'m': 20, 'factr': 0, 'pgtol': 1e-8, 'maxfun': 20}           # predictors/__init__.py:15-20
@@ -172,10 +171,21 @@ class BRSEngine:
             raise NotImplementedError(f'BRSEngine: insertion mode {insertion_mode!r} is not built (after_aspp, after_deeplab)')
         self.net, self.insertion_mode = net, insertion_mode
         self.num_channels = net.deeplab_ch + (32 if insertion_mode == 'after_aspp' else 0)
-        self._features = OrderedDict()      # (h, w, with_flip) -> (graph, static inputs, input_data)
-        self._objectives = OrderedDict()    # (input_data shape, h, w, regulariser) -> _Objective
+        self._features = stages.StageCache(lambda: MAX_GEOMETRIES)      # (h, w, with_flip) -> Stage whose output is input_data
+        self._objectives = stages.StageCache(lambda: MAX_GEOMETRIES)    # (input_data shape, h, w, regulariser) -> _Objective
         self._cap = CLICK_CAPACITY
-        self.captures = 0
+
+    @property
+    def captures(self):
+        """graphs captured so far"""
+        return self._features.captures + self._objectives.captures
+
+    def _grow(self, n):
+        """Room for n clicks per sample: the captured graphs hold the old buffers and go when they grow."""
+        if n > self._cap:
+            self._cap = grown_capacity(self._cap, n)
+            self._features.clear()
+            self._objectives.clear()
 
     def _scope(self):
         return f'@brs#{self.net._scope}#{self.insertion_mode}#'
@@ -190,39 +200,10 @@ class BRSEngine:
     def features(self, image, points, with_flip=True):
         """FeatureBRSPredictor._get_head_input (brs.py:121-140): image [3,h,w] at the working size and points [2n,2] as ClickNet.run takes
         them -> input_data [B,h4,w4,C], the graph's static buffer (valid until the next call at this geometry)."""
-        net = self.net
-        net._need_weights()
-        pts = np.asarray(points, dtype=np.float32).reshape(2, -1, 2)
-        n = pts.shape[1]
-        if n > self._cap:
-            while self._cap < n:
-                self._cap *= 2
-            self._features.clear()
-            self._objectives.clear()
-        host = np.full((2, self._cap, 2), -1.0, np.float32)
-        host[:, :n] = pts
-        host_clicks, host_counts = torch.from_numpy(host), torch.from_numpy(np.array([n, n], np.int32))
-        key = (int(image.shape[-2]), int(image.shape[-1]), bool(with_flip))
-        st = self._features.get(key)
+        self.net._need_weights()
+        self._grow(np.asarray(points).size // 4)
         with ops.ws_scope(self._scope()):
-            if st is None:
-                while len(self._features) >= MAX_GEOMETRIES:
-                    self._features.popitem(last=False)
-                static_in = (image.clone(), host_clicks.to(net.device), host_counts.to(net.device))
-                self._features_forward(*static_in, with_flip)       # warm-up: sizes every workspace and picks the plans
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static_out = self._features_forward(*static_in, with_flip)
-                st = self._features[key] = (graph, static_in, static_out)
-                self.captures += 1
-            else:
-                self._features.move_to_end(key)
-            graph, static_in, static_out = st
-            for dst, src in zip(static_in, (image, host_clicks, host_counts)):
-                dst.copy_(src)
-            graph.replay()
-        return static_out
+            return run_click_stage(self._features, self._features_forward, image, points, self._cap, with_flip)
 
     # objective -----------------------------------------------------------------------------------------------------------
     def _objective_forward(self, st, reg_weight, reg_bias_weight):
@@ -254,27 +235,14 @@ class BRSEngine:
         net._need_weights()
         if feat_shape[3] != self.num_channels:
             raise RuntimeError(f'BRSEngine: input_data has {feat_shape[3]} channels, {self.insertion_mode} optimises {self.num_channels}')
-        if num_clicks > self._cap:
-            while self._cap < num_clicks:
-                self._cap *= 2
-            self._features.clear()
-            self._objectives.clear()
+        self._grow(num_clicks)
         key = (tuple(feat_shape), int(H), int(W), float(reg_weight), float(reg_bias_weight))
-        st = self._objectives.get(key)
-        if st is not None:
-            self._objectives.move_to_end(key)
-            return st
-        while len(self._objectives) >= MAX_GEOMETRIES:
-            self._objectives.popitem(last=False)
-        st = _Objective(tuple(feat_shape), int(H), int(W), net.device, self._cap)
-        with ops.ws_scope(self._scope()):
-            self._objective_forward(st, reg_weight, reg_bias_weight)      # warm-up: sizes every workspace and picks the plans
-            torch.cuda.synchronize()
-            st.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(st.graph):
-                self._objective_forward(st, reg_weight, reg_bias_weight)
-        self._objectives[key] = st
-        self.captures += 1
+        st = self._objectives.lookup(key)
+        if st is None:
+            st = _Objective(tuple(feat_shape), int(H), int(W), net.device, self._cap)
+            with ops.ws_scope(self._scope()):
+                st.graph = stages.capture(lambda: self._objective_forward(st, reg_weight, reg_bias_weight), ()).graph
+            self._objectives.put(key, st)
         return st
 
 

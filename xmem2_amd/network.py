@@ -10,20 +10,15 @@ loads unchanged.  Internally nothing is an nn.Module: at load time every convolu
 Public methods take / return NCHW-shaped tensors like the reference (zero-copy permuted views of the
 NHWC buffers); the ``*_nhwc`` methods are the hot path used by ``InferenceCore``.
 """
-import collections
 import os
 import warnings
-import weakref
 
 import torch
 
-from . import ops
-from .arch import BN_EPS, infer_dims, state_dict_spec
+from . import ops, stages
+from .arch import infer_dims, state_dict_spec
+from .hipnet import HipNet, _pad4
 from .ops import ConvWeights
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
 
 
 # captured HIP-graph stages kept before the least recently replayed one is dropped
@@ -61,15 +56,15 @@ def _padc(n):
     return (n + 7) // 8 * 8 if ops.act_dtype() == torch.float16 else _pad4(n)
 
 
-class XMem:
+class XMem(HipNet):
     def __init__(self, config, model_path=None, map_location=None, pretrained_key_encoder=True, pretrained_value_encoder=True):
         """Same signature as model/network.py:18.  `pretrained_*` are accepted for compatibility; torchvision
         ImageNet weights cannot be fetched offline, so a checkpoint (or load_weights) is the only weight source."""
+        # captured stages are bounded by MAX_STAGES and evicted by _evict_lru (_run_stage)
+        super().__init__(torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu'),
+                         max_stages=lambda: MAX_STAGES)
         self.single_object = config.get('single_object', False)
         self.model_path = model_path                 # what a caller's config['model'] is compared with when the network is handed over
-        self.device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
-        self._sd = None
-        self._w = {}
         self._cbam = {}
         # launch-bound stages (61 convolutions + ~40 small kernels per frame) are replayed as HIP graphs
         self.use_graphs = os.environ.get('XMEM_HIP_GRAPHS', '1') != '0'
@@ -92,13 +87,9 @@ class XMem:
         self.precision = config.get('precision', os.environ.get('XMEM_PRECISION', 'fp32'))
         if self.precision not in ops.PRECISIONS:
             raise ValueError(f"config['precision'] must be one of {ops.PRECISIONS}, got {self.precision!r}")
-        self._stages = collections.OrderedDict()     # captured stages, least recently replayed first
-        self._zeros = {}
+        self._zeros = {}                 # zero-filled scratch only (_zero_scratch): nothing of the weights, so it outlives them
         self._owner_free, self._owner_next = [], 0   # owner tokens of the cores driving this network (see acquire_owner)
         self._call_precision = None      # per-call override (InferenceCore preloads permanent memory in fp32)
-        # scratch of the side-stream key-encoder stages is scoped to this instance and released with it
-        self._scope = ops.new_scope()
-        weakref.finalize(self, ops.release_scope, self._scope)
         weights = self.init_hyperparameters(config, model_path, map_location)
         if weights is not None:
             self.load_weights(weights, init_as_zero_if_needed=True)
@@ -128,39 +119,17 @@ class XMem:
             if not init_as_zero_if_needed:
                 torch.nn.init.orthogonal_(pads)
             src_dict[k] = torch.cat([src_dict[k], pads], 1)
-        self.load_state_dict(src_dict)
+        return super().load_weights(src_dict)
 
-    def load_state_dict(self, sd, strict=True):
-        spec = state_dict_spec(self.key_dim, self.value_dim, self.hidden_dim, self.single_object)
-        if strict:
-            missing = [k for k in spec if k not in sd and not k.endswith('num_batches_tracked')]
-            unexpected = [k for k in sd if k not in spec]
-            if missing or unexpected:
-                raise RuntimeError(f'Error(s) in loading state_dict for XMem: missing {missing[:5]}..., unexpected {unexpected[:5]}...')
-            for k, shape in spec.items():
-                if k in sd and tuple(sd[k].shape) != tuple(shape) and not (len(shape) == 0 and sd[k].numel() == 1):
-                    raise RuntimeError(f'size mismatch for {k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(shape)}')
-        self._sd = {k: v.detach().to('cpu') for k, v in sd.items()}
-        if self.device.type == 'cuda':
-            self._upload()
+    def _spec(self):
+        return state_dict_spec(self.key_dim, self.value_dim, self.hidden_dim, self.single_object)
 
-    def state_dict(self):
-        return dict(self._sd) if self._sd is not None else {}
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == 'cuda' and device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        self.device = device
-        if device.type == 'cuda' and self._sd is not None:
-            self._upload()
-        return self
+    def _reupload(self):
+        if self.device.type == 'cuda':          # an XMem may exist on the CPU without uploading (_need_weights)
+            super()._reupload()
 
     def cuda(self, index=None):
         return self.to(torch.device('cuda', index if index is not None else torch.cuda.current_device()))
-
-    def eval(self):
-        return self
 
     def train(self, mode=True):
         if mode:
@@ -168,23 +137,6 @@ class XMem:
         return self
 
     # ---- weight preparation ---------------------------------------------------------------------
-    def _conv_w(self, name, bn=None, stride=1, pad=0):
-        sd = self._sd
-        w = sd[name + '.weight'].float()
-        cout, cin = w.shape[0], w.shape[1]
-        wk = w.permute(0, 2, 3, 1)
-        if cin % 4:
-            wk = torch.nn.functional.pad(wk, (0, _pad4(cin) - cin))
-        if bn is not None:
-            invstd = 1.0 / torch.sqrt(sd[bn + '.running_var'].float() + BN_EPS)
-            scale = invstd * sd[bn + '.weight'].float()
-            shift = sd[bn + '.bias'].float() - sd[bn + '.running_mean'].float() * scale
-        else:
-            scale = torch.ones(cout)
-            shift = sd[name + '.bias'].float() if (name + '.bias') in sd else torch.zeros(cout)
-        dev = self.device
-        return ConvWeights(wk.contiguous().to(dev), scale.contiguous().to(dev), shift.contiguous().to(dev), stride, pad, cin_true=cin)
-
     def _upload(self):
         sd, W = self._sd, {}
         W['key_encoder.conv1'] = self._conv_w('key_encoder.conv1', 'key_encoder.bn1', 2, 3)
@@ -306,37 +258,20 @@ class XMem:
     # ---- HIP-graph staging ------------------------------------------------------------------------
     def _run_stage(self, name, key, inputs, fn, alias=(), mutates=()):
         """Run `fn(*inputs)` eagerly, or capture it once per (name, shapes, flags) into a HIP graph with static
-        input / output buffers and replay it.  Kernels are launched through ctypes on torch's current stream, which
-        is the capturing stream inside torch.cuda.graph, so they are captured like any other launch."""
+        input / output buffers and replay it (stages.py)."""
         prec = self._call_precision or self.precision
         if not self.use_graphs or ops.eager_only() or name in os.environ.get('XMEM_EAGER_STAGES', '').split(','):
             with ops.precision(prec):
                 return fn(*inputs)
         full_key = (name, key, prec) + tuple(tuple(t.shape) if t is not None else None for t in inputs)
-        st = self._stages.get(full_key)
+        st = self._stages.lookup(full_key)
         if st is None:
             # inputs listed in `alias` are themselves stable buffers (outputs of another stage): use them in place
             static_in = [(t if i in alias else t.clone()) if t is not None else None for i, t in enumerate(inputs)]
-            # warm-up: sizes every workspace before the capture.  Inputs the stage updates in place (`mutates`: the hidden
-            # state) are cloned for it, otherwise warm-up + first replay would advance the state twice.
             with ops.precision(prec):
-                fn(*[(t.clone() if (i in mutates and t is not None) else t) for i, t in enumerate(static_in)])
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with ops.CAPTURE_LOCK, torch.cuda.graph(graph):   # no decode thread pins host memory meanwhile
-                    static_out = fn(*static_in)
-            st = (graph, static_in, static_out)
-            while len(self._stages) >= MAX_STAGES:
-                self._evict_lru()
-            self._stages[full_key] = st
-        else:
-            self._stages.move_to_end(full_key)
-        graph, static_in, static_out = st
-        for dst, src in zip(static_in, inputs):
-            if dst is not None and dst.data_ptr() != src.data_ptr():
-                dst.copy_(src)
-        graph.replay()
-        return static_out
+                st = stages.capture(fn, static_in, mutates)
+            self._stages.put(full_key, st, evict=self._evict_lru)
+        return st.replay(inputs)
 
     def _evict_lru(self):
         """Bound the cache (every resolution / object count / slot / owner adds graphs with private pools): drop the least
@@ -399,12 +334,9 @@ class XMem:
         if len(frame_layout) < 6 or batch < 1:
             raise ValueError('restored_key_slot: the layout of key, shrinkage, selection, f16, skip8 and skip4 is required')
         full_key = ('keyr', slot, prec, int(batch), frame_layout)
-        st = self._stages.get(full_key)
+        st = self._stages.lookup(full_key)
         if st is not None:
-            self._stages.move_to_end(full_key)
-            return st[2]
-        while len(self._stages) >= MAX_STAGES:
-            self._evict_lru()
+            return st.outputs
         dev = self.device
         bufs = [torch.empty((shape[0] * batch,) + shape[1:], dtype=dtype, device=dev) for shape, dtype in frame_layout]
         f16, skip8, skip4 = bufs[3], bufs[4], bufs[5]
@@ -412,45 +344,10 @@ class XMem:
         f8 = hole.expand(batch, skip8.shape[1], skip8.shape[2], self._w['decoder.up_16_8.skip_conv'].cin)
         f4 = hole.expand(batch, skip4.shape[1], skip4.shape[2], self._w['decoder.up_8_4.skip_conv'].cin)
         out = (bufs[0], bufs[1], bufs[2], f16, f8, f4, tuple(bufs[4:]))
-        self._stages[full_key] = (None, [], out)
+        self._stages.put(full_key, stages.Stage(None, [], out), evict=self._evict_lru)
         return out
 
     # ---- building blocks (NHWC) -----------------------------------------------------------------
-    def _bottleneck(self, x, p):
-        W = self._w
-        o = ops.conv2d(x, W[p + '.conv1'], relu_out=True)
-        o = ops.conv2d(o, W[p + '.conv2'], relu_out=True)
-        res = ops.conv2d(x, W[p + '.downsample']) if (p + '.downsample') in W else x
-        return ops.conv2d(o, W[p + '.conv3'], res=res, relu_out=True)
-
-    def _basic(self, x, p):
-        W = self._w
-        o = ops.conv2d(x, W[p + '.conv1'], relu_out=True)
-        res = ops.conv2d(x, W[p + '.downsample']) if (p + '.downsample') in W else x
-        return ops.conv2d(o, W[p + '.conv2'], res=res, relu_out=True)
-
-    def _stage(self, x, prefix, blocks, fn, pre=None, then=None):
-        """The blocks of one ResNet stage.  A bottleneck stage of a network with `fused_bottleneck` walks its blocks so that block b's conv3 and
-        block b + 1's conv1 are one launch (ops.conv2d_pointwise_pair); `then` names the convolution that reads the stage's output next (the
-        following stage's first conv1), which is paired with the last conv3 and returned with the output: -> (x, then(x)), and `pre` is
-        block 0's conv1 output made that way.  A pair the op does not take runs as the two convolutions: the same bits either way."""
-        if fn != self._bottleneck or not getattr(self, 'fused_bottleneck', False):
-            for b in range(blocks):
-                x = fn(x, f'{prefix}.{b}')
-            return x if then is None else (x, None)
-        W = self._w
-        for b in range(blocks):
-            p = f'{prefix}.{b}'
-            o = pre if pre is not None else ops.conv2d(x, W[p + '.conv1'], relu_out=True)
-            o = ops.conv2d(o, W[p + '.conv2'], relu_out=True)
-            res = ops.conv2d(x, W[p + '.downsample']) if (p + '.downsample') in W else x
-            follow = f'{prefix}.{b + 1}.conv1' if b + 1 < blocks else then
-            if follow is not None and o.shape[0] * o.shape[1] * o.shape[2] >= self.fused_bottleneck_min_pixels:
-                x, pre = ops.conv2d_pointwise_pair(o, W[p + '.conv3'], res, W[follow])
-            else:
-                x, pre = ops.conv2d(o, W[p + '.conv3'], res=res, relu_out=True), None
-        return x if then is None else (x, pre)
-
     def _group_res(self, g, p, out=None, out_ld=None):
         """GroupResBlock, model/group_modules.py:44-52: conv2(relu(conv1(relu(g)))) + (downsample(g) | g)."""
         W = self._w

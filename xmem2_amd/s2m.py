@@ -10,14 +10,12 @@ over them, and the forward is captured once per (K, H, W) as a HIP graph and rep
 interaction.py:36-51, so the GUI's commit sequence (argmax -> one-hot -> [1:] -> InferenceCore.put_to_permanent_memory,
 gui.py:851-859) runs unchanged on the result.
 """
-import weakref
-
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, stages
 from .arch import s2m_state_dict_spec
-from .network import XMem
+from .hipnet import HipNet
 
 ASPP_RATES = (6, 12, 18)        # output_stride 16 (s2m_network.py:12-13)
 HARD_TEMPERATURE = 1000.0       # aggregate_wbg(hard=True): logits x 1000 (interaction.py:45-47)
@@ -34,65 +32,21 @@ def pad_divide_by_16(h, w):
     return Hp, Wp, (Hp - h) // 2, (Wp - w) // 2
 
 
-class S2M:
+class S2M(HipNet):
     """deeplabv3plus_resnet50(num_classes=1, output_stride=16) on HIP kernels (fp32, the demo's --no_amp arithmetic)."""
 
-    # the ResNet building blocks of network.py: the same BN folding, bottleneck and stage code
-    _conv_w = XMem._conv_w
-    _bottleneck = XMem._bottleneck
-    _stage = XMem._stage
+    _synthetic = 'synthetic_s2m_state_dict'
 
     def __init__(self, model_path=None, device=None):
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        self._sd = None
-        self._w = {}
-        self._graphs = {}
-        self.captures = 0              # graphs captured so far (one per (K, H, W))
-        self._scope = ops.new_scope()
-        weakref.finalize(self, ops.release_scope, self._scope)
+        super().__init__(torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device()))
+        self._graphs = self._stages         # one graph per (K, H, W, ignore_class), unbounded
         if model_path is not None:
             self.load_weights(model_path)
 
-    # ---- weights ----------------------------------------------------------------------------------
-    def load_weights(self, src):
-        """A checkpoint path (torch.load('saves/s2m.pth')) or a state dict."""
-        if isinstance(src, (str, bytes)) or hasattr(src, '__fspath__'):
-            src = torch.load(src, map_location='cpu', weights_only=True)
-        self.load_state_dict(src)
-        return self
-
-    def load_state_dict(self, sd, strict=True):
-        spec = state_dict_spec()
-        if strict:
-            missing = [k for k in spec if k not in sd and not k.endswith('num_batches_tracked')]
-            unexpected = [k for k in sd if k not in spec]
-            if missing or unexpected:
-                raise RuntimeError(f'Error(s) in loading state_dict for S2M: missing {missing[:5]}..., unexpected {unexpected[:5]}...')
-        for k, shape in spec.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shape) and not (len(shape) == 0 and sd[k].numel() == 1):
-                raise RuntimeError(f'size mismatch for {k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(shape)}')
-        self._sd = {k: v.detach().to('cpu') for k, v in sd.items()}
-        self._graphs.clear()
-        self._upload()
-
-    def state_dict(self):
-        return dict(self._sd) if self._sd is not None else {}
-
-    def to(self, device):
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        if self._sd is not None:
-            self._graphs.clear()
-            self._upload()
-        return self
-
-    def eval(self):
-        return self
+    def _spec(self):
+        return state_dict_spec()
 
     def _upload(self):
-        if self.device.type != 'cuda':
-            raise RuntimeError('xmem2_amd.S2M runs on an MI355X (HIP) device only; there is no CPU path')
         W = {}
         W['backbone.conv1'] = self._conv_w('backbone.conv1', 'backbone.bn1', 2, 3)      # 6 channels, padded to the packed 8
         for prefix, blocks, stride in (('backbone.layer1', 3, 1), ('backbone.layer2', 4, 2), ('backbone.layer3', 6, 2),
@@ -118,11 +72,6 @@ class S2M:
         W['head.0'] = self._conv_w(c + 'classifier.0', c + 'classifier.1', 1, 1)
         W['head.3'] = self._conv_w(c + 'classifier.3', None, 1, 0)
         self._w = W
-
-    def _need_weights(self):
-        if not self._w:
-            raise RuntimeError('S2M: no weights loaded (load_weights(path) or load_state_dict(sd); '
-                               'xmem2_amd.synth.synthetic_s2m_state_dict gives conditioned synthetic ones)')
 
     # ---- forward (NHWC) -------------------------------------------------------------------------
     def features(self, x):
@@ -169,22 +118,12 @@ class S2M:
         self._need_weights()
         K, H, W = int(num_objects), int(image.shape[-2]), int(image.shape[-1])
         key = (K, H, W, int(ignore_class))
-        st = self._graphs.get(key)
         with ops.ws_scope(f'@s2m#{self._scope}#'):
+            st = self._graphs.lookup(key)
             if st is None:
-                static_in = (image.clone(), prev_mask.clone(), scr.clone())
-                self._forward(*static_in, K, ignore_class)          # warm-up: sizes every workspace and picks the plans
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static_out = self._forward(*static_in, K, ignore_class)
-                st = self._graphs[key] = (graph, static_in, static_out)
-                self.captures += 1
-            graph, static_in, static_out = st
-            for dst, src in zip(static_in, (image, prev_mask, scr)):
-                dst.copy_(src)
-            graph.replay()
-        return static_out
+                st = self._graphs.put(key, stages.capture(lambda *a: self._forward(*a, K, ignore_class),
+                                                          (image.clone(), prev_mask.clone(), scr.clone())))
+            return st.replay((image, prev_mask, scr))
 
 
 def aggregate_wbg(prob, keep_bg=False, hard=False):
