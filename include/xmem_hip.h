@@ -732,6 +732,28 @@ int xmem_weighted_rows(const float* aff, int P, int n, int count, const float* V
  * out_index receives the kept indices in order, *out_count (device int) their number. */
 int xmem_select_greater(const float* usage, int n, const float* threshold_dev, int32_t* out_index, int32_t* out_count, void* stream);
 
+/* Eviction of a store with several object groups: every arena compacted by the same index of surviving key elements, one launch per
+ * XMEM_COMPACT_MAX_ARENAS arenas (the descriptors travel by value in the kernel arguments).  The groups are suffix-aligned: an arena
+ * of n rows holds the LAST n of the store's N = keep_cap elements, off = N - n (else XMEM_ERR_BAD_ARG).  With keep[0..m) ascending
+ * (xmem_select_greater's out_index) and m = *m_dev read on the device (its out_count, clamped to [0, keep_cap]), arena a moves source
+ * row keep[j] - off to destination row j - j0 for j >= j0, the first j with keep[j] >= off (binary search), and kept[a] (device int32
+ * [n_arenas]) receives the number of rows it keeps, m - j0: all sizes reach the host in one transfer.  An arena of one object's
+ * values is one entry; n = 0 is allowed (its pointers are not looked at, kept = 0).
+ * src / dst: 4-byte aligned; rows whose width is a multiple of 4 floats on 16-byte-aligned bases move as 16-byte vectors.  NOT in
+ * place: a destination that overlaps any source or another destination of the call is XMEM_ERR_BAD_ARG, as are null pointers, negative
+ * counts, off < 0 and width < 1 - all before any GPU work.  Every source and destination row is checked against n on the device: an
+ * index that is not ascending or out of range leaves rows unwritten, never an access outside an arena. */
+#define XMEM_COMPACT_MAX_ARENAS 16
+typedef struct {
+    const float* src;   /* [n][width] rows */
+    float* dst;         /* room for n rows of the same width */
+    int width;          /* floats per row */
+    int n;              /* rows before the compaction */
+    int off;            /* N - n */
+} xmem_compact_arena;
+int xmem_store_compact(const xmem_compact_arena* arenas_host, int n_arenas, const int32_t* keep, const int32_t* m_dev, int keep_cap,
+                       int32_t* kept, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Annotation-candidate selector (inference/frame_selection/frame_selection.py:99-244).
  * ------------------------------------------------------------------------------------------ */

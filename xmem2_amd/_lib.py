@@ -42,6 +42,7 @@ CONV_SHARED_MAX = 3      # include/xmem_hip.h XMEM_CONV_SHARED_MAX: convolutions
 DILATED_NO_TAP_SKIP = 1  # include/xmem_hip.h XMEM_DILATED_NO_TAP_SKIP
 RLE_META = 6             # include/xmem_hip.h XMEM_RLE_META: int32 values per (frame, label) of xmem_rle_encode's meta
 COPY_MAX_SEGMENTS = 16   # include/xmem_hip.h XMEM_COPY_MAX_SEGMENTS: (src, dst, bytes) triples one xmem_copy_segments launch carries
+COMPACT_MAX_ARENAS = 16  # include/xmem_hip.h XMEM_COMPACT_MAX_ARENAS: arena descriptors one xmem_store_compact launch carries
 
 
 class AugDesc(C.Structure):
@@ -58,6 +59,10 @@ class AffinityHint(C.Structure):
 
 class ValueSegment(C.Structure):
     _fields_ = [('value', C.c_void_p), ('n', C.c_int)]
+
+
+class CompactArena(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('width', C.c_int), ('n', C.c_int), ('off', C.c_int)]
 
 
 _SIGS = {
@@ -189,6 +194,7 @@ _SIGS = {
     'xmem_softmax_rows_topk': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'xmem_weighted_rows': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'xmem_select_greater': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'xmem_store_compact': (C.c_int, [C.POINTER(CompactArena), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'xmem_selector_prepare': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),

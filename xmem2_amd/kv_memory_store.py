@@ -7,7 +7,9 @@ geometrically, so an append is a device copy into the tail and the affinity / re
 a store as a (pointer, length) segment - no concatenation ever happens.
 
 Object groups keep the reference's suffix alignment (memory_manager.py:99-120): group g's values belong
-to the LAST ``get_v_size(g)`` keys of the store.
+to the LAST ``get_v_size(g)`` keys of the store.  The least-used eviction (``remove_obsolete_features``) keeps that alignment
+for any number of groups - the reference refuses more than one, so a long video whose objects appear later crashed in mid-stream:
+one kernel (csrc/store_compact.hip) compacts every arena by the same index of surviving keys, each group from its own offset.
 
 Row-major views are exposed for the kernels (``key_rows`` ...); the reference-shaped properties
 (``key`` ``1 x C x N`` ...) are zero-copy transposed views for callers such as the GUI gauges.
@@ -87,15 +89,16 @@ class _Arena:
             pos += b - a
         self.n = pos
 
-    def take(self, index):
-        """Keep rows at int32 device `index` (ascending)."""
-        m = index.numel()
+    def compaction(self):
+        """A fresh buffer of this capacity and the (source rows, destination) pairs, one per leading index, that
+        `ops.store_compact` fills it through: a gather is not safe in place, the caller then hands the buffer to `adopt`."""
+        new = torch.empty_like(self.buf)
         if self.lead:
-            for i in range(self.lead[0]):
-                self.buf[i, :m].copy_(ops.gather_rows(self.buf[i, :self.n], index))
-        else:
-            self.buf[:m].copy_(ops.gather_rows(self.buf[:self.n], index))
-        self.n = m
+            return new, [(self.buf[i, :self.n], new[i]) for i in range(self.lead[0])]
+        return new, [(self.buf[:self.n], new)]
+
+    def adopt(self, buf, n):
+        self.buf, self.n = buf, n
 
 
 class KeyValueMemoryStore:
@@ -295,19 +298,28 @@ class KeyValueMemoryStore:
 
     def remove_obsolete_features(self, max_size: int):
         """Least-used eviction, kv_memory_store.py:160-181: drop every element whose usage is <= the
-        (size-max_size)-th smallest usage."""
-        if self.num_groups > 1:
-            raise NotImplementedError('The current data structure does not support feature removal with '
-                                      'multiple object groups (e.g., some objects start to appear later in the video)')
+        (size-max_size)-th smallest usage - with any number of object groups (the reference refuses more than one).
+
+        Usage comes from group 0, which sees every key.  With `keep` the ascending surviving key elements of the N before, every
+        key-side arena keeps its rows `keep`, and group g (n_g rows, the last n_g keys: offset N - n_g) keeps its rows
+        keep[j] - (N - n_g) for the j with keep[j] >= N - n_g, in that order, for each of its objects: no (key, value) pairing the
+        readout sees changes, a group may end up empty.  All arenas go through ONE `ops.store_compact` call (a launch per 16
+        arena rows of the table) into fresh buffers, and one transfer brings every new row count back."""
         k = self.size - max_size
         usage = self.get_usage_rows()
         vals, _ = ops.topk_1d(usage, k, largest=False)
         index, count = ops.select_greater(usage, vals[k - 1:k])
-        m = int(count.item())
-        index = index[:m]
+        plan, pairs = [], []
         for arena in [self._k, self._use, self._life] + ([self._s] if self._has_s else []) + \
                      ([self._e] if self._has_e else []) + ([self._r16] if self._r16 is not None else []) + list(self._v):
-            arena.take(index)
+            if arena.n == 0:
+                continue                                   # (a group without rows keeps none)
+            new, rows = arena.compaction()
+            plan.append((arena, new, len(pairs)))
+            pairs += rows
+        kept = ops.store_compact(pairs, index, count).tolist()
+        for arena, new, at in plan:
+            arena.adopt(new, kept[at])
 
     def get_usage_rows(self):
         if not self.count_usage:

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib, conv_plan
 from .pil_resize import MAX_SIDE, taps
-from ._lib import AffinityHint, ConvDesc, KeySegment, ValueSegment, check, load, ptr, stream_ptr
+from ._lib import AffinityHint, CompactArena, ConvDesc, KeySegment, ValueSegment, check, load, ptr, stream_ptr
 
 _workspaces = {}
 _retired = {}                  # key -> outgrown buffers that captured HIP graphs may still point into
@@ -1180,6 +1180,31 @@ def select_greater(usage, threshold_dev):
     cnt = torch.empty((1,), dtype=torch.int32, device=usage.device)
     check(load().xmem_select_greater(ptr(usage), n, ptr(threshold_dev), ptr(idx), ptr(cnt), stream_ptr()))
     return idx, cnt
+
+
+def store_compact(arenas, keep, count):
+    """Every arena of a store compacted by one index of surviving key elements (csrc/store_compact.hip), one launch per
+    `_lib.COMPACT_MAX_ARENAS` arenas.  arenas: (src, dst) pairs of contiguous float32 tensors, src [n, C] or [n] holding the LAST n of
+    the store's N = keep.numel() elements, dst of the same row width with room for n rows and not overlapping any src; keep / count:
+    what `select_greater` returned (int32 [N] ascending, int32 [1] on the device).  dst row j - j0 receives src row keep[j] - (N - n)
+    for j0 <= j < count, j0 the first j with keep[j] >= N - n.  Returns the kept row counts, int32 [len(arenas)] on the device."""
+    arenas = list(arenas)
+    n_ar, N = len(arenas), keep.numel()
+    if keep.dtype != torch.int32 or count.dtype != torch.int32 or not keep.is_cuda or not count.is_cuda or not keep.is_contiguous():
+        raise RuntimeError('store_compact: keep and count must be int32 CUDA (HIP) tensors')
+    kept = torch.empty((max(n_ar, 1),), dtype=torch.int32, device=keep.device)
+    arr = (CompactArena * max(n_ar, 1))()
+    for i, (src, dst) in enumerate(arenas):
+        _req(src, f'arena {i} source'); _req(dst, f'arena {i} destination')
+        n = src.shape[0]
+        width = src.shape[1] if src.dim() == 2 else 1
+        if src.dim() not in (1, 2) or dst.dim() != src.dim() or (dst.shape[1] if dst.dim() == 2 else 1) != width or dst.shape[0] < n \
+                or not src.is_contiguous() or not dst.is_contiguous() or n > N:
+            raise RuntimeError(f'store_compact: arena {i}: source {tuple(src.shape)} / destination {tuple(dst.shape)} of a store of {N}')
+        arr[i].src, arr[i].dst = (src.data_ptr(), dst.data_ptr()) if n else (None, None)
+        arr[i].width, arr[i].n, arr[i].off = width, n, N - n
+    check(load().xmem_store_compact(arr, n_ar, ptr(keep), ptr(count), N, ptr(kept), stream_ptr()))
+    return kept[:n_ar]
 
 
 # ---- scribble-to-mask (S2M) ---------------------------------------------------------------------------------
