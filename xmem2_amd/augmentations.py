@@ -138,7 +138,7 @@ def augment_on_device(rgb_u8, mask, subset='best_all'):
     colour augmentations) in the reference's list order, or None for subset 'original_only'."""
     import ctypes as C
     from . import ops
-    from ._lib import AugDesc, check, load, ptr, stream_ptr
+    from ._lib import CONSTANTS, AugDesc, check, load, ptr, stream_ptr
     if not rgb_u8.is_cuda or rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3:
         raise RuntimeError('augment_on_device: expected a device uint8 frame [H, W, 3]')
     H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
@@ -147,7 +147,8 @@ def augment_on_device(rgb_u8, mask, subset='best_all'):
         return None
     n = len(specs)
     descs = (AugDesc * n)()
-    TYPES = dict(brightness=0, posterize=1, gray=2, sharpness=3, blur=4, affine=5)
+    TYPES = {kind: CONSTANTS['XMEM_AUG_' + kind.upper()] for kind in ('brightness', 'posterize', 'gray', 'sharpness', 'affine')}
+    TYPES['blur'] = CONSTANTS['XMEM_AUG_BLUR7']
     geometric = []
     for i, (name, kind, kw) in enumerate(specs):
         descs[i].type = TYPES[kind]

@@ -988,7 +988,8 @@ def nchw_to_nhwc(x):
 # memory readout
 # ---------------------------------------------------------------------------------------------
 
-ROWS16_FLOATS = 72            # one fp16 filter operand row (144 halfs = 288 bytes) counted in floats
+ROWS16_FLOATS = _lib.CONSTANTS['XMEM_ROWS16_HALFS'] // 2      # one fp16 filter operand row (144 halfs = 288 bytes) counted in floats
+MAX_SEGMENTS = _lib.CONSTANTS['XMEM_MAX_SEGMENTS']            # segments one affinity hint describes
 
 
 def affinity_rows16(key, shrinkage, out):
@@ -1030,7 +1031,7 @@ def affinity_topk(segments, qk, qe, top_k, want_sim=False, hint=None):
     if hint is not None:
         h_idx, h_sizes, h_gw = hint
         if h_idx is not None and h_idx.is_cuda and tuple(h_idx.shape[:1]) == (HW,) and h_idx.dtype == torch.int32 \
-                and len(h_sizes) == len(segs) <= 4:
+                and len(h_sizes) == len(segs) <= MAX_SEGMENTS:
             h = AffinityHint()
             h.idx = h_idx.data_ptr(); h.top_k = h_idx.shape[1]; h.n_seg = len(h_sizes)
             for i, n in enumerate(h_sizes):

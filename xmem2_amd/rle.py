@@ -36,7 +36,7 @@ import sys
 
 import numpy as np
 
-META = 6                                        # int32 per (frame, label): events, area, x0, y0, x1, y1 (include/xmem_hip.h XMEM_RLE_META)
+from ._lib import RLE_META as META              # int32 per (frame, label): events, area, x0, y0, x1, y1
 EMPTY_BOX = (0, 0, -1, -1)
 MIN_CAPACITY = 2048
 
