@@ -70,7 +70,7 @@ typedef struct {
     float* out;         int ldout;
     int relu_in, relu_out;
     int plan_tile;      /* PLAN CODE 0..40 (anything else: XMEM_ERR_BAD_ARG): algorithm, GEMM tile (rows = output pixels or Winograd tiles
-                           x output channels), k-tile depth BK and kernel.  The one table behind it is kPlanCodes in csrc/conv_mfma.hip
+                           x output channels), k-tile depth BK and kernel.  The one table behind it is kPlanCodes in csrc/conv_plan.hpp
                            (Python: xmem2_amd/conv_plan.py CODES); xmem_conv2d_plan_info() reports what a descriptor resolves to.
                              0       built-in heuristic: direct form, tile by the number of tiles (128x128, 128x64, else 64x64), BK 32
                              1..6    direct implicit GEMM, {128x128, 128x64, 64x64} x BK {32, 64}

@@ -105,6 +105,42 @@ def test_plan_resolution_matches_the_recorded_table():
     assert len(bad) == 0, f'dilated workspace differs at (layer, dilation, tile, splitk) indices {bad[0]}'
 
 
+def test_planner_alone_under_the_sanitizers_matches_the_recorded_table(tmp_path):
+    """csrc/conv_plan.hpp is free of HIP: tools/conv_plan_sweep.cpp, built by the host compiler with AddressSanitizer and
+    UndefinedBehaviorSanitizer (a stand-alone program), walks the grid of query() over the fixture's layers and must print the
+    recorded plan and workspace of every descriptor - among them plan codes -1, 41 and 42, which validate() has to turn away
+    before kPlanCodes is indexed.  Any sanitizer report ends the program with a non-zero status."""
+    import shutil
+    import subprocess
+    import pytest
+    cxx = next((c for c in (os.environ.get('CXX'), 'g++', 'c++', 'clang++') if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path / 'conv_plan_sweep')
+    subprocess.run([cxx, '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    os.path.join(ROOT, 'tools', 'conv_plan_sweep.cpp'), '-o', exe], check=True)
+    g = np.load(GOLDEN)
+    assert len(g['layers']) == 34
+    rows = '\n'.join(' '.join(str(int(v)) for v in layer) for layer in g['layers']) + '\n'
+    run = subprocess.run([exe], input=rows, capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = run.stdout.split('\n')[:-1]
+    per_layer = g['workspace'][0].size + g['dilated_workspace'][0].size
+    assert len(lines) == len(g['layers']) * per_layer
+    info, ws, dws = [], [], []
+    for line in lines:
+        kind, *vals = line.split()
+        if kind == 'I':
+            info.append(vals[:len(INFO_COLS)])
+            ws.append(vals[len(INFO_COLS)])
+        else:
+            assert kind == 'D'
+            dws.append(vals[0])
+    assert (np.array(info, np.int64).reshape(g['info'].shape) == g['info']).all()
+    assert (np.array(ws, np.int64).reshape(g['workspace'].shape) == g['workspace']).all()
+    assert (np.array(dws, np.int64).reshape(g['dilated_workspace'].shape) == g['dilated_workspace']).all()
+
+
 def _info_of(code, pointwise, half):
     layer = dict(B=2, H=40, W=40, Cin=64, ldin=64, Cout=64, K=1 if pointwise else 3, stride=1, pad=0 if pointwise else 1, ldout=64,
                  ldres=0, out_off=0)

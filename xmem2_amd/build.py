@@ -9,8 +9,9 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
-SOURCES = ['conv_mfma.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip']
-HEADERS = ['common.hpp', 'affinity_common.hpp', 'gemm_stream.hpp', 'pointwise_pair.hpp']
+SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip']
+HEADERS = ['common.hpp', 'host_math.hpp', 'affinity_common.hpp', 'conv_plan.hpp', 'conv_mfma.hpp', 'conv_winograd.hpp', 'gemm_stream.hpp',
+           'pointwise_pair.hpp']
 LIB = os.path.join(CSRC, 'libxmem_hip.so')
 ARCH = 'gfx950'
 EXTRA_FLAGS = {'augment.hip': ['-ffp-contract=off']}      # per-source flags: the augmentation kernel rounds where the host libraries round

@@ -1,7 +1,7 @@
 """Which plan a convolution runs under: the plan codes, the shipped plan tables, the tuner, and the order they are consulted in.
 
 A plan is (code, split-K).  The code is `xmem_conv_desc.plan_tile` (include/xmem_hip.h documents the numbering, kPlanCodes in
-csrc/conv_mfma.hip is the library's table); CODES below is the same table for Python, and everything here that needs the meaning
+csrc/conv_plan.hpp is the library's table); CODES below is the same table for Python, and everything here that needs the meaning
 of a code reads it from there.  tests/test_conv_plan_host.py holds CODES against what the library reports.
 """
 import collections

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <unordered_map>
 #include "../../include/xmem_hip.h"
+#include "host_math.hpp"               // cdiv, align_up
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -33,9 +34,6 @@ static inline int xmem_ensure_dynamic_lds(const void* fn, size_t bytes) {
     cur = bytes;
     return XMEM_OK;
 }
-
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 

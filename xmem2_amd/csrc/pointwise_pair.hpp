@@ -1,5 +1,5 @@
 // A bottleneck's expand 1x1 (+ residual + relu) and the next block's reduce 1x1 (+ relu) in one launch (csrc/pointwise_pair.hip).
-// Internal to the library (not part of the C ABI): the entry point is xmem_conv2d_pointwise_pair in csrc/conv_mfma.hip.
+// Internal to the library (not part of the C ABI): the entry point is xmem_conv2d_pointwise_pair in csrc/conv.hip.
 #pragma once
 #include "common.hpp"
 

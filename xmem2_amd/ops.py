@@ -254,7 +254,7 @@ def split_pack(w, shift=0):
 _WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]])
 
 
-# F(4x4,3x3) with the interpolation points {0, +-3/4, +-3/2, inf} (csrc/conv_mfma.hip: why, and what the transforms look like).
+# F(4x4,3x3) with the interpolation points {0, +-3/4, +-3/2, inf} (csrc/conv_winograd.hip: why, and what the transforms look like).
 # Row i of G = (1, p_i, p_i^2) / N_i with N_i = prod_{k != i} (p_i - p_k) over the finite points; the row of infinity is (0, 0, 1).
 def _wino4_g(a=0.75, b=1.5):
     from fractions import Fraction as Fr
