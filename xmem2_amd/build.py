@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
-SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip']
+SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip', 'components.hip']
 HEADERS = ['common.hpp', 'host_math.hpp', 'affinity_common.hpp', 'conv_plan.hpp', 'conv_mfma.hpp', 'conv_winograd.hpp', 'gemm_stream.hpp',
            'pointwise_pair.hpp']
 LIB = os.path.join(CSRC, 'libxmem_hip.so')
@@ -21,6 +21,8 @@ EXTRA_FLAGS = {'augment.hip': ['-ffp-contract=off']}      # per-source flags: th
 # stream - the memory-readout filter and the split-operand GEMMs do exactly that next to the side-stream key encoder.  With
 # the subtarget feature turned off the same runs are bit-identical to the solo runs.  (The flag reaches the host compilation
 # too, which prints an 'ignoring feature' note - filtered below.)
+INCLUDE = os.path.join(os.path.dirname(CSRC), '..', 'include')
+PUBLIC_HEADERS = ['xmem_hip.h', 'xmem_hip_masks.h']      # the frozen ABI-5 header and the one that declares what came after it
 DEVICE_FLAGS = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 _NOISE = "'-packed-fp32-ops' is not a recognized feature for this target (ignoring feature)"
 
@@ -37,19 +39,20 @@ def needs_build():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    deps.append(os.path.join(os.path.dirname(CSRC), '..', 'include', 'xmem_hip.h'))
+    deps += [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
 def source_digest():
-    """sha256 over the kernel sources + header: profiles recorded for one build are only quoted against the same build."""
+    """sha256 over the kernel sources + headers: profiles recorded for one build are only quoted against the same build."""
     import hashlib
     h = hashlib.sha256()
     for f in sorted(SOURCES + HEADERS):
         with open(os.path.join(CSRC, f), 'rb') as fh:
             h.update(fh.read())
-    with open(os.path.join(os.path.dirname(CSRC), '..', 'include', 'xmem_hip.h'), 'rb') as fh:
-        h.update(fh.read())
+    for f in PUBLIC_HEADERS:
+        with open(os.path.join(INCLUDE, f), 'rb') as fh:
+            h.update(fh.read())
     h.update(' '.join(DEVICE_FLAGS).encode())
     for src in sorted(EXTRA_FLAGS):
         h.update((src + ':' + ' '.join(EXTRA_FLAGS[src])).encode())

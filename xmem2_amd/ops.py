@@ -1836,3 +1836,55 @@ def brs_param_grad(g, x, scale_bias, record, grad, reg_weight=1e-3, reg_bias_wei
     check(lib.xmem_brs_param_grad(ptr(g), ptr(x), B, h, w, Cc, ptr(scale_bias), float(reg_weight), float(reg_bias_weight), ptr(record),
                                   ptr(grad), ptr(ws), need, stream_ptr()))
     return grad
+
+
+# ---- connected components and mask clean-up (csrc/components.hip, include/xmem_hip_masks.h): integer, bit-reproducible --------
+
+def _index_maps(masks, name):
+    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
+        raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor [H,W] or [N,H,W] - xmem2_amd has no CPU path')
+    if masks.numel() == 0:
+        raise RuntimeError(f'{name}: empty input {tuple(masks.shape)}')
+    masks = masks.contiguous()
+    return masks, (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
+
+
+def components(masks, connectivity=8):
+    """Connected components of uint8 maps `masks` [H,W] or [N,H,W] on the device -> (root, area), int32 tensors of that shape:
+    `mask_cleanup.components_host` per frame, bit for bit (a component is a maximal 4- / 8-connected set of pixels of EQUAL value, 0
+    included; root = the row-major index of its first pixel within the frame, area = its size).  A fixed sequence of launches on
+    the current stream, no synchronisation."""
+    from . import _lib_masks
+    if connectivity not in (4, 8):
+        raise ValueError(f'components: connectivity = {connectivity!r} must be 4 or 8')
+    masks, (N, H, W) = _index_maps(masks, 'components')
+    lib = _lib_masks.load()
+    root = torch.empty(masks.shape, dtype=torch.int32, device=masks.device)
+    area = torch.empty(masks.shape, dtype=torch.int32, device=masks.device)
+    nbytes = lib.xmem_components_workspace_bytes(N, H, W)
+    ws = workspace(max(nbytes, 8), masks.device, 'components')
+    check(lib.xmem_components(ptr(masks), N, H, W, int(connectivity), ptr(root), ptr(area), ptr(ws), ws.numel(), stream_ptr()))
+    return root, area
+
+
+def clean_masks(masks, min_area=0, max_hole=0, keep_largest=False, out=None):
+    """`mask_cleanup.clean_host` of every frame of the uint8 index maps `masks` [H,W] or [N,H,W] on the device -> (out, stats):
+    `out` uint8 of that shape (a tensor of the caller's that does not overlap `masks`, or a new one), `stats` int32 [4] or [N,4] on
+    the device (components removed, pixels removed, holes filled, pixels filled).  Objects: 8-connected components smaller than
+    `min_area`, and with `keep_largest` all but the largest of each label, become 0; then enclosed 4-connected holes of at most
+    `max_hole` pixels with one label all around take that label.  One launch sequence on the current stream, no synchronisation."""
+    from . import _lib_masks
+    from .mask_cleanup import parse_cleanup
+    spec = parse_cleanup({'min_area': min_area, 'max_hole': max_hole, 'keep_largest': keep_largest}) or {}
+    masks, (N, H, W) = _index_maps(masks, 'clean_masks')
+    if out is None:
+        out = torch.empty(masks.shape, dtype=torch.uint8, device=masks.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or out.shape != masks.shape or not out.is_contiguous() or out.device != masks.device:
+        raise RuntimeError(f'clean_masks: out must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(masks.shape)} on the masks\' device')
+    lib = _lib_masks.load()
+    stats = torch.empty((N, _lib_masks.CLEAN_STATS) if masks.dim() == 3 else (_lib_masks.CLEAN_STATS,), dtype=torch.int32, device=masks.device)
+    nbytes = lib.xmem_mask_clean_workspace_bytes(N, H, W)
+    ws = workspace(max(nbytes, 8), masks.device, 'mask_clean')
+    check(lib.xmem_mask_clean(ptr(masks), N, H, W, spec.get('min_area', 0), spec.get('max_hole', 0), int(spec.get('keep_largest', False)),
+                              ptr(out), ptr(stats), ptr(ws), ws.numel(), stream_ptr()))
+    return out, stats

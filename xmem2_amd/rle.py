@@ -524,26 +524,86 @@ def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
     return written
 
 
-def main(argv=None):
+def clean_tracks(tracks, spec, batch=32):
+    """A tracks file (or parsed document) with `ops.clean_masks` applied to every frame -> (document, totals of the four counters).
+    Per batch: `TrackReader.masks_device` (dense ids, one per track) -> `ops.clean_masks` -> `ops.rle_encode`; no mask plane reaches
+    the host, and boxes and areas are the encoder's, of the cleaned masks.  `spec`: what `mask_cleanup.parse_cleanup` returns.  The
+    counts are lists, or compressed strings when every entry of the input is one."""
+    import torch
+    from . import ops
+    from .mask_cleanup import STATS
+    reader = TrackReader(tracks)
+    if len(set(reader.labels)) != len(reader.labels):
+        raise ValueError('clean_tracks: two tracks share a label')
+    names = reader.file_names if len(reader.file_names) == len(reader) else [str(t) for t in range(len(reader))]
+    writer = TrackWriter(reader.height, reader.width)
+    k, step = len(reader.labels), max(1, int(batch))
+    totals = torch.zeros(len(STATS), dtype=torch.int64)
+    for i in range(0, len(reader) if k else 0, step):
+        frames = list(range(i, min(i + step, len(reader))))
+        dense, present = reader.masks_device(frames, values='dense', batch=step)
+        cleaned, stats = ops.clean_masks(dense, **spec)
+        meta, events = ops.rle_encode(cleaned, k)                    # waits for the record: the counters have arrived with it
+        totals += stats.sum(0, dtype=torch.int64).cpu()
+        for j, t in enumerate(frames):
+            if present[j]:
+                writer.add_frame(names[t], meta[j], events[j], labels=reader.labels)
+            else:
+                writer.add_frame(names[t])
+    for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
+        writer.add_frame(names[t])
+    for lab in reader.labels:                                        # a track without any entry still has its (empty) row
+        writer._tracks.setdefault(lab, {})
+    doc = writer.to_dict()
+    forms = [is_compressed(c) for segs in reader._segs for c in segs.values()]
+    if forms and all(forms):
+        doc = recode_tracks(doc, 'compressed')
+    return doc, dict(zip(STATS, (int(v) for v in totals.tolist())))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle',
-                                 description='tracks.json -> index PNGs (one per frame), or - with --recode - tracks.json with its '
-                                             'counts in the other form')
+                                 description='tracks.json -> index PNGs (one per frame), or - with --recode and / or --clean - '
+                                             'tracks.json with its counts in the other form and / or its masks cleaned on the device')
     ap.add_argument('--tracks', required=True, help='the tracks.json of one video (counts as lists, compressed strings, or both)')
-    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode the file that is written')
+    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode or --clean the file that is written')
     ap.add_argument('--recode', default=None, choices=COUNT_FORMS,
                     help='write no PNGs: rewrite the file with every counts entry as a list or as the compressed COCO string')
+    ap.add_argument('--clean', default=None, metavar='JSON',
+                    help='write no PNGs: rewrite the file with every mask cleaned, e.g. \'{"min_area": 16, "max_hole": 16}\' '
+                         '(keys min_area, max_hole, keep_largest; needs the GPU); the count form is kept unless --recode names one')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
     args = ap.parse_args(argv)
-    if args.recode is not None:
-        with open(args.tracks) as f:
-            doc = recode_tracks(json.load(f), args.recode)
+    if args.clean is not None:
+        from .mask_cleanup import parse_cleanup
+        try:
+            args.clean = parse_cleanup(json.loads(args.clean))
+        except ValueError as e:                                      # JSONDecodeError is one
+            ap.error(f'--clean: {e}')
+        if args.clean is None:
+            ap.error('--clean: the options given change nothing')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.recode is not None or args.clean is not None:
+        report = {}
+        if args.clean is not None:
+            doc, report['clean'] = clean_tracks(args.tracks, args.clean)
+        else:
+            with open(args.tracks) as f:
+                doc = json.load(f)
+        if args.recode is not None:
+            doc = recode_tracks(doc, args.recode)
+            report['recode'] = args.recode
         if os.path.dirname(args.out):
             os.makedirs(os.path.dirname(args.out), exist_ok=True)
         text = json.dumps(doc, separators=(',', ':'))
         with open(args.out, 'w') as f:
             f.write(text)
-        print(json.dumps({'recode': args.recode, 'bytes': len(text), 'out': args.out}))
+        print(json.dumps(dict(report, bytes=len(text), out=args.out)))
         return 0
     written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty)
     print(json.dumps({'frames': len(written), 'out': args.out}))

@@ -31,6 +31,7 @@ import torch
 from . import ops
 from .configuration import VIDEO_INFERENCE_CONFIG
 from .inference_core import InferenceCore
+from .mask_cleanup import parse_cleanup
 from .mask_mapper import MaskMapper
 from .metrics import InLoopScorer
 from .network import XMem
@@ -300,6 +301,29 @@ def _post_process_gpu(sample, prob):
     return ops.argmax_u8(prob)
 
 
+def _clean_output(spec, out_dev, totals=None):
+    """config['mask_cleanup'] (as `mask_cleanup.parse_cleanup` returns it) on the index mask a frame loop is about to hand on: `out_dev`
+    itself without the option - nothing is loaded or launched for it - else the cleaned mask in a tensor of its own, its four
+    counters added to `totals` on the device.  The probabilities that go back into the memory are not this function's business:
+    propagation is the same with and without the option, only what is written differs."""
+    if spec is None:
+        return out_dev
+    out, stats = ops.clean_masks(out_dev, **spec)
+    if totals is not None:
+        totals.add_(stats)
+    return out
+
+
+def _cleanup_totals(spec, device):
+    """the per-video sum of xmem_mask_clean's counters, kept on the device and fetched once after the loop (None without the option)"""
+    return None if spec is None else torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def _cleanup_report(totals):
+    from .mask_cleanup import STATS
+    return dict(zip(STATS, (int(v) for v in totals.cpu().tolist())))
+
+
 class _TrackLoop:
     """config['save_tracks'] inside a frame loop: one `ops.rle_encode` launch sequence per frame on the compute stream, the record
     delivered through pinned memory one frame behind like the mask (its own AsyncMaskFetcher, fed right before the mask's: when the
@@ -566,6 +590,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     device = _inference_device()
     frames_with_masks = set(frames_with_masks)
     config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
+    cleanup = parse_cleanup(config.get('mask_cleanup'))              # opt-in (default: absent): despeckle / fill holes / keep largest
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
@@ -618,6 +643,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         raise ValueError('No valid masks provided!')
 
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
+    cleaned = _cleanup_totals(cleanup, device)
     # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).
     outputs = _FrameOutputs(
         vid_reader, mapper, AsyncMaskFetcher(),
@@ -644,7 +670,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         skip_add = (ti == 0) if original_memory_mechanism else (msk is not None)
         prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
                               manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
-        return msk is not None, _post_process_gpu(sample, prob)
+        return msk is not None, _clean_output(cleanup, _post_process_gpu(sample, prob), cleaned)
 
     key_batch = max(1, int(config.get('key_batch', 4)))                # frames per batched key-encoder hint
     decoder = FramePrefetcher(vid_reader, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
@@ -656,7 +682,16 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_jf(pd.DataFrame(outputs.stats), scorer)
+    return _with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps)
+
+
+def _with_cleanup(df, totals, say=False):
+    """config['mask_cleanup']: the video's totals of the four counters in `df.attrs['cleanup']` (one transfer, after the loop)"""
+    if totals is not None:
+        df.attrs['cleanup'] = _cleanup_report(totals)
+        if say:
+            print('MASK CLEAN-UP: ' + ', '.join(f'{k.replace("_", " ")} {v}' for k, v in df.attrs['cleanup'].items()))
+    return df
 
 
 def _with_jf(df, scorer):
@@ -783,6 +818,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     import pandas as pd
     config = _merged_config(dict(overwrite_config or {}), masks_out_path)           # on a copy: the caller's dict stays as it is
     passes = parse_ensemble(config.get('ensemble'), config['size'])
+    cleanup = parse_cleanup(config.get('mask_cleanup'))
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
@@ -842,11 +878,12 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
 
     mapper = mappers[0]
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
-    outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again
+    cleaned = _cleanup_totals(cleanup, device)
+    outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again - unless cleaned
         vid_reader, mapper, AsyncMaskFetcher(),
         saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
         tracks=_TrackLoop(config.get('tracks_counts', 'list')) if config.get('save_tracks', False) else None, scorer=scorer,
-        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=True)
+        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):
@@ -885,7 +922,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                 bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
             acc, merged = bufs[shp]
             ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
-        return given, merged
+        return given, _clean_output(cleanup, merged, cleaned)        # cleaned: into a tensor of its own, `merged` is rewritten next frame
 
     key_batch = max(1, int(config.get('key_batch', 4)))
     decoder = EnsembleFramePrefetcher(readers, passes, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
@@ -897,7 +934,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_jf(pd.DataFrame(outputs.stats), scorer)
+    return _with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),

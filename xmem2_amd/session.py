@@ -173,7 +173,7 @@ class _Frame:
 
 class VideoSession:
     def __init__(self, imgs_in_path, masks_in_path=None, overwrite_config=None, network=None):
-        from .run_on_video import _make_network, _set_long_term_count_usage, _working_u8
+        from .run_on_video import _cleanup_totals, _make_network, _set_long_term_count_usage, _working_u8
         if not os.path.isdir(imgs_in_path):
             raise NotADirectoryError(f'imgs_in_path: {imgs_in_path!r} is not a directory of frames')
         if masks_in_path is not None and not os.path.isdir(masks_in_path) and not os.path.isfile(masks_in_path):
@@ -187,6 +187,8 @@ class VideoSession:
         config = VIDEO_INFERENCE_CONFIG.copy()
         config.update(overwrite_config or {})
         self.config = config
+        from .mask_cleanup import parse_cleanup
+        self.cleanup = parse_cleanup(config.get('mask_cleanup'))         # opt-in: every propagated mask is cleaned before it is kept
         self.network = _make_network(config, self.device, network)
         self.imgs_in_path, self.masks_in_path = imgs_in_path, masks_in_path
         reader = _session_reader(imgs_in_path, masks_in_path, size=config['size'], resize_on_device=config.get('resize_on_device', False))
@@ -234,6 +236,7 @@ class VideoSession:
         self.selection = torch.empty((n, gh * gw, ck), dtype=torch.float32, device=self.device)
         self.masks = torch.zeros((n,) + tuple(self.shape), dtype=torch.uint8, device=self.device)   # dense ids (MaskMapper)
         self._present = [False] * n
+        self._cleaned = _cleanup_totals(self.cleanup, self.device)      # the four counters of the clean-up, summed on the device
         self._refs = {}                                                  # frame index -> the annotation's raw H x W index array
         budget = int(config.get('session_feature_cache_bytes', 0))      # opt-in: the key pass of every frame kept on the device
         self._fcache = FeatureCache(n, budget, self.device) if budget > 0 else None
@@ -379,7 +382,7 @@ class VideoSession:
     def propagate(self, start=0, direction='forward', stop=None, manually_curated_masks=False):
         """gui.on_propagation: step over start..stop in `direction` on the memory as it stands; per visited frame the call
         run_on_video's frame loop makes.  Returns the visited frame indices."""
-        from .run_on_video import _post_process_gpu
+        from .run_on_video import _clean_output, _post_process_gpu
         order = visit_order(len(self), start, direction, stop)
         if not self._refs:
             raise ValueError('No valid masks provided!')
@@ -387,6 +390,7 @@ class VideoSession:
         on_device = all(t < self.n_device_frames for t in order)
 
         fcache = getattr(self, '_fcache', None)
+        cleanup, cleaned = getattr(self, 'cleanup', None), getattr(self, '_cleaned', None)
 
         def prefetch(batch):
             # resident frames were complete long ago (synchronised at construction): the pass may start under the current frame
@@ -413,7 +417,7 @@ class VideoSession:
             self.key[t].view(gh, gw, -1).copy_(key[0].permute(1, 2, 0))
             self.shrinkage[t].view(gh, gw).copy_(shr[0, 0])
             self.selection[t].view(gh, gw, -1).copy_(sel[0].permute(1, 2, 0))
-            self.masks[t].copy_(_post_process_gpu(fr, prob))
+            self.masks[t].copy_(_clean_output(cleanup, _post_process_gpu(fr, prob), cleaned))
             self._present[t] = True
         return order
 
@@ -423,6 +427,21 @@ class VideoSession:
             raise ValueError('No valid masks provided!')
         self.core.clear_memory(keep_permanent=True)
         return self.propagate(0, 'forward')
+
+    def clean(self, min_area=0, max_hole=0, keep_largest=False, batch=32):
+        """`ops.clean_masks` on the masks as they stand, `batch` frames per call, in place of what they held; a frame without a mask
+        is all zero and stays so.  Returns the totals {components_removed, pixels_removed, holes_filled, pixels_filled}."""
+        from .mask_cleanup import parse_cleanup
+        from .run_on_video import _cleanup_report
+        spec = parse_cleanup({'min_area': min_area, 'max_hole': max_hole, 'keep_largest': keep_largest})
+        totals = torch.zeros(4, dtype=torch.int64, device=self.device)
+        step = max(1, int(batch))
+        with torch.cuda.device(self.device):
+            for i in range(0, len(self) if spec is not None else 0, step):
+                out, stats = ops.clean_masks(self.masks[i:i + step], **spec)
+                self.masks[i:i + step].copy_(out)
+                totals.add_(stats.sum(0))
+        return _cleanup_report(totals)
 
     # ---- candidates ----------------------------------------------------------------------------------------------------
     def mask_table(self, mask_form='objects'):
@@ -552,7 +571,7 @@ class VideoSession:
         """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
         import pandas as pd
         from .metrics import InLoopScorer
-        from .run_on_video import _stats_row, _with_jf
+        from .run_on_video import _cleanup_report, _stats_row, _with_jf
         host = self._host_masks() if compute_iou else None
         if compute_jf and not self.all_masks_present():
             raise RuntimeError('compute_jf scores the whole video: run propagation on all frames first')
@@ -564,7 +583,10 @@ class VideoSession:
             if scorer is not None and fr.mask is not None:
                 scorer.add(t, fr.mask, self.masks[t], self.mapper)
             rows.append(_stats_row(fr.frame, t in self._refs, compute_iou, host[t] if compute_iou else None, fr.mask))
-        return _with_jf(pd.DataFrame(rows), scorer)
+        df = _with_jf(pd.DataFrame(rows), scorer)
+        if getattr(self, 'cleanup', None) is not None:                                     # what config['mask_cleanup'] did in the propagations so far
+            df.attrs['cleanup'] = _cleanup_report(self._cleaned)
+        return df
 
 
 def _session_reader(imgs_in_path, masks_in_path, size, resize_on_device):
