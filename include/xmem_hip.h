@@ -40,7 +40,7 @@ typedef enum {
 
 /* ABI version of this header.  2 (round 4): xmem_conv_desc grew (in_half / out_half / w_half), storage-typed `_t` entry points, plan
  * tiles 23..40.  3 (round 5): no layout change, but the MEANING of w_winograd4 / w_winograd4_split changed - the F(4x4) transforms use the
- * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  Still 5: the f-BRS refinement entry points added (xmem_brs_affine_nhwc, xmem_brs_loss, xmem_relu_gate_nhwc, xmem_relu_gate_outer_nhwc, xmem_brs_param_grad and their workspace sizes): new symbols only, no layout change.  Still 5: xmem_conv2d_pointwise_pair added, a new symbol only.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
+ * interpolation points (0, +-3/4, +-3/2, inf), a caller must form G g G^T with the matching G (see xmem_conv_desc.w_winograd4).  4: xmem_conv2d_plan_info added, no layout change.  5: the click-to-mask entry points added (xmem_click_*, xmem_depthwise3x3_nhwc, xmem_resize_bilinear_ac*, xmem_mask_bbox, xmem_prob_threshold), no layout change.  Still 5: the f-BRS refinement entry points added (xmem_brs_affine_nhwc, xmem_brs_loss, xmem_relu_gate_nhwc, xmem_relu_gate_outer_nhwc, xmem_brs_param_grad and their workspace sizes): new symbols only, no layout change.  Still 5: xmem_conv2d_pointwise_pair added, a new symbol only.  Still 5: xmem_affinity_plan_info added, a new symbol only.  A caller compiled against another version must not pass structs: check xmem_version() == XMEM_ABI_VERSION at load. */
 #define XMEM_ABI_VERSION 5
 int xmem_version(void);
 const char* xmem_last_error_string(int code); /* static string for a status code */
@@ -635,7 +635,15 @@ int xmem_affinity_rows16(const float* key, const float* shrinkage, int n, void* 
  * order, memory_manager.py:82-83); out indices are positions in that concatenation.
  * qk [HW][C_k]; qe [HW][C_k] or NULL.  top_k in [1, 64], sum(n) >= top_k else XMEM_ERR_TOPK.
  * out_w [HW][top_k] softmax weights exp(v)/sum exp(v) (no max shift, memory_util.py:48-49), sorted by
- * descending similarity; out_idx [HW][top_k]; out_sim (nullable) [HW][top_k] raw similarities. */
+ * descending similarity; out_idx [HW][top_k]; out_sim (nullable) [HW][top_k] raw similarities.
+ * TIE RULE: equal similarities rank by ascending index, both inside the result and at its k-th place (torch.topk leaves
+ *   that order open), so a query's top_k indices are distinct and fully determined by the fp32 similarities.
+ * ZERO RULE: -0.0 and +0.0 are one value.  They tie (lower index first) and out_sim reports +0.0 for either.
+ * NON-FINITE: a similarity of -inf (a key entry whose square overflows) is an ordinary value: it ranks last, by ascending index,
+ *   with weight 0 and out_sim = -inf.  NaN inputs (and operands whose products give NaN, such as inf * 0) are outside the contract.
+ * PATHS: memories of fewer than 256 tiles take one safe select; from 256 tiles on the call runs a bound pass and the wide select
+ *   (xmem_affinity_plan_info reports which).  A tile is 32 rows of ONE segment, so the threshold is not an element count: a single
+ *   segment reaches it at 8161 elements, segments of (1, 1, 1, 8100) elements at 8103. */
 size_t xmem_affinity_topk_workspace_bytes(int n_total, int HW, int top_k);
 int xmem_affinity_topk(const xmem_key_segment* segs_host, int n_seg,
                        const float* qk, const float* qe, int Ck, int HW, int top_k,
@@ -657,8 +665,8 @@ int xmem_affinity_profile_events(void* before_filter, void* after_filter);
 /* Same function with an optional HINT: `idx` are the out_idx [HW][top_k] of an earlier call on the same list of stores (the
  * previous frame of the video), `seg_n` the segment sizes of that call, `grid_w` the width of the stride-16 query grid (0: do not
  * use grid neighbours).  The hint only bounds the k-th similarity from below (any k distinct elements give a valid bound; the
- * previous frame's matches give a tight one): results are bit-identical with and without it.  With a bound (and >= 8192 memory
- * elements) the N x HW contraction runs on the fp16 matrix pipe as a rigorously bounded filter and only the surviving
+ * previous frame's matches give a tight one): results are bit-identical with and without it.  With a bound (and >= 256 tiles
+ * of memory, see PATHS above) the N x HW contraction runs on the fp16 matrix pipe as a rigorously bounded filter and only the surviving
  * candidates are evaluated in fp32, with the arithmetic of the fp32 select (csrc/affinity_filter.hip).
  * hint == NULL behaves as xmem_affinity_topk.  The reference recomputes everything per frame (memory_manager.py:82-120). */
 typedef struct {
@@ -671,6 +679,24 @@ int xmem_affinity_topk_hinted(const xmem_key_segment* segs_host, int n_seg,
                               const xmem_affinity_hint* hint,
                               float* out_w, int32_t* out_idx, float* out_sim,
                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* The pipeline xmem_affinity_topk_hinted would run for segments of seg_n_host[0 .. n_seg) elements (the call launches from the same
+ * numbers).  Host only: no GPU call; hint may be NULL, of a hint only the fields are read, hint->idx is compared with NULL and never
+ * dereferenced.  Respects XMEM_AFFINITY_FILTER16.  Returns XMEM_OK or what the call's validation of these arguments returns. */
+enum { XMEM_AFF_SMALL = 0,                    /* < 256 tiles: safe select + merge */
+       XMEM_AFF_LARGE_SAMPLED = 1,            /* sampled bound pass, wide select, merge */
+       XMEM_AFF_LARGE_HINTED_FP32 = 2,        /* bound from the hint, wide select, merge (XMEM_AFFINITY_FILTER16=0) */
+       XMEM_AFF_LARGE_HINTED_FILTER16 = 3 };  /* bound from the hint, fp16 filter, exact refine */
+typedef struct {
+    int route;                      /* XMEM_AFF_* */
+    int tiles;                      /* 32-row tiles, counted per segment */
+    int splits, tiles_per_split;    /* of the select that runs (safe, wide, or the fp16 filter) */
+    int chunk;                      /* wide select: tiles per chunk dealt round-robin to the splits; 0: contiguous ranges */
+    int bound_stride, bound_splits; /* sampled route: the bound pass visits every bound_stride-th tile in bound_splits splits; else 0 */
+    int list_cap, list_stride;      /* filter route: entries of a candidate list in pass 1 / its allocation (pass 2); else 0 */
+} xmem_affinity_plan;
+int xmem_affinity_plan_info(const int* seg_n_host, int n_seg, int HW, int top_k, const xmem_affinity_hint* hint,
+                            xmem_affinity_plan* out);
 
 /* usage = affinity.sum(dim=2) (memory_util.py:62-63) restricted to [first, first+count) of the index space,
  * accumulated order-independently (64-bit fixed point) and then folded into the store counters as

@@ -33,7 +33,7 @@ const char* xmem_text(const xmem_thing* t, const uint16_t* dev, uint64_t bits);
 #endif
 '''
 STRUCT_SIZES = dict(xmem_conv_desc=208, xmem_conv_plan_info=28, xmem_aug_desc=80, xmem_key_segment=32, xmem_affinity_hint=40,
-                    xmem_value_segment=16, xmem_compact_arena=32)
+                    xmem_affinity_plan=36, xmem_value_segment=16, xmem_compact_arena=32)
 ARITIES = dict(xmem_store_compact=7, xmem_copy_segments=5, xmem_rle_decode=11, xmem_selector_prepare_u8=17, xmem_conv2d_m_bytes=1,
                xmem_conv2d_shared_input_workspace_bytes=2, xmem_conv2d_shared_input=7, xmem_conv2d_nhwc_folded=7, xmem_conv2d_output_from_m=4)
 
@@ -72,7 +72,7 @@ def test_parsed_structs_have_the_compilers_layout(tmp_path):
                    + ''.join(f'    std::printf("%zu\\n", {x});\n' for x in want) + '    return 0;\n}\n')
     subprocess.run([build._hipcc(), '-x', 'c++', '-I', os.path.dirname(HEADER), str(src), '-o', str(exe)], check=True)
     got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert len(want) == 7 + 33 + 7 + 4 + 4 + 5 + 2 + 5 and dict(zip(want, map(int, got))) == want
+    assert len(want) == 8 + 33 + 7 + 4 + 4 + 5 + 9 + 2 + 5 and dict(zip(want, map(int, got))) == want
 
 
 def test_library_is_bound_as_the_header_declares():
@@ -86,7 +86,7 @@ def test_library_is_bound_as_the_header_declares():
 
 def test_frozen_abi_facts():
     from xmem2_amd import _lib, rle
-    assert _lib.EXPORTED_SYMBOLS == tuple(_lib._SIGS) and len(_lib._SIGS) == 102
+    assert _lib.EXPORTED_SYMBOLS == tuple(_lib._SIGS) and len(_lib._SIGS) == 103
     assert {n: C.sizeof(s) for n, s in _lib._STRUCTS.items()} == STRUCT_SIZES
     assert {n: len(_lib._SIGS[n][1]) for n in ARITIES} == ARITIES
     assert _lib.ConvDesc is _lib._STRUCTS['xmem_conv_desc'] and _lib.ConvDesc._fields_[0] == ('inp', C.c_void_p)

@@ -446,6 +446,20 @@ __global__ void affinity_merge_kernel(const u64* __restrict__ part_key, const in
         }
         if (rk < top_k) { sv[rk] = key_val(ke); si[rk] = key_idx(ke); }
     }
+    // Fewer than top_k candidates: the select had no bound (tau = -inf) and its strict test passes every element ABOVE -inf, so
+    // what is missing are exactly the elements whose similarity is -inf (a key entry whose square overflows).  They rank behind
+    // every candidate, lower index first, with weight exp(-inf) = 0.  The caller guarantees >= top_k elements, and at most `total`
+    // of the indices 0 .. top_k-1 are taken: the missing ranks are the lowest unpicked of those (lane j looks at index j).
+    if (total < top_k) {
+        __builtin_amdgcn_wave_barrier();
+        bool open = lane < top_k;
+        for (int r = 0; r < total; ++r) open = open && si[r] != lane;
+        const unsigned long long m = __ballot(open);
+        const int pos = total + __popcll(m & ((1ull << lane) - 1ull));
+        __builtin_amdgcn_wave_barrier();
+        if (open && pos < top_k) { sv[pos] = -INFINITY; si[pos] = lane; }
+        __builtin_amdgcn_wave_barrier();
+    }
     // softmax without max shift (memory_util.py:48-49); DS ops of one wave execute in order
     float s = 0.f;
     for (int r = lane; r < top_k; r += 64) s += expf(sv[r]);
@@ -958,6 +972,22 @@ __global__ __launch_bounds__(256) void affinity_merge16_kernel(const u64* __rest
             }
             if (rk < top_k) { sv[rk] = key_val(ke); si[rk] = key_idx(ke); }
         }
+        // fewer than top_k candidates (only a light list can be that short): the missing ranks are the elements at -inf, lowest
+        // unpicked index first, weight 0 - see affinity_merge_kernel.  Lane l of the group looks at the indices l, l + 16, ...
+        if (total < top_k) {
+            __builtin_amdgcn_wave_barrier();
+            int filled = total;
+            for (int j0 = 0; j0 < top_k; j0 += 16) {
+                const int j = j0 + l;
+                bool open = j < top_k;
+                for (int r = 0; r < total; ++r) open = open && si[r] != j;
+                const unsigned m = (unsigned)(__ballot(open) >> (16 * (g & 3))) & 0xffffu;
+                const int pos = filled + __popc(m & ((1u << l) - 1u));
+                if (open && pos < top_k) { sv[pos] = -INFINITY; si[pos] = j; }
+                filled += __popc(m);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
     }
     // heavy queries of this wave (its four 16-lane groups), one at a time on all 64 lanes
     for (int j = 0; j < 4; ++j) {
@@ -1121,7 +1151,83 @@ WsLayout ws_layout(int HW, int n_total) {
     w.total = w.fcnt_off + align_up((size_t)HW * F16_CS * sizeof(int), 256);
     return w;
 }
+
+// Which pipeline serves a call and with what grid arithmetic: the ONE place that decides it.  xmem_affinity_topk_hinted launches from
+// these numbers and xmem_affinity_plan_info reports them.  seg_n: the caller's segment sizes (validated: none negative, sum >= top_k).
+struct AffRoute {
+    int route, tiles;
+    AffPlan sel;                          // XMEM_AFF_SMALL: the safe select
+    int w_splits, w_tps, w_chunk;         // large routes that run the wide select (sampled, hinted fp32)
+    int R; AffPlan bound;                 // XMEM_AFF_LARGE_SAMPLED: stride and plan of the bound pass
+    int f_nw, f_splits, f_tps, lcap, lstride;   // XMEM_AFF_LARGE_HINTED_FILTER16
+};
+AffRoute aff_route(const int* seg_n, int n_seg, int HW, int top_k, const xmem_affinity_hint* hint) {
+    AffRoute r = {};
+    int tiles = 0, base = 0;
+    for (int i = 0; i < n_seg; ++i) { tiles += cdiv(seg_n[i], AFF_ROWS); base += seg_n[i]; }
+    r.tiles = tiles;
+    if (tiles < 256 || top_k > AFW_CAP) {
+        r.route = XMEM_AFF_SMALL;
+        r.sel = aff_plan(tiles, HW, top_k, false);
+        return r;
+    }
+    const int qt128 = cdiv(HW, AFW_BQ);
+    // one 8-wave workgroup per CU: splits so that query tiles x splits fills (at most) the 256 CUs, >= 8 tiles per wave
+    int sp = 256 / qt128; if (sp < 1) sp = 1;
+    { int maxs = tiles / (8 * AFW_WAVES); if (maxs < 1) maxs = 1; if (sp > maxs) sp = maxs; }
+    if (sp > 32) sp = 32;                              // AFW_GCAP = 32 splits x 64 entries
+    r.w_tps = cdiv(tiles, sp);
+    r.w_splits = cdiv(tiles, r.w_tps);
+    // chunks of ~half a memory frame dealt round-robin to the splits (temporal clusters of good matches would otherwise pile
+    // up in one split's candidate lists), when every split gets >= 16 chunks
+    int sel_chunk = cdiv(HW, AFF_ROWS) / 2; if (sel_chunk < AFW_WAVES) sel_chunk = AFW_WAVES;
+    sel_chunk = cdiv(sel_chunk, AFW_WAVES) * AFW_WAVES;
+    const int n_chunks = cdiv(tiles, sel_chunk);
+    if (n_chunks < 16 * r.w_splits) sel_chunk = 0;
+    r.w_chunk = sel_chunk;
+    if (sel_chunk) r.w_tps = cdiv(n_chunks, r.w_splits) * sel_chunk;
+
+    const bool hinted = hint && hint->idx && hint->top_k >= top_k && hint->top_k <= 64 && hint->n_seg == n_seg;
+    if (!hinted) {
+        // sampled bound pass: every 4th 32-row tile (every 8th for very large chunk-dealt memories)
+        r.route = XMEM_AFF_LARGE_SAMPLED;
+        r.R = 4;
+        if (sel_chunk && tiles >= 8192) r.R = 8;
+        r.bound = aff_plan(cdiv(tiles, r.R), HW, top_k, true, base);
+    } else if (!aff_use_filter16()) {
+        r.route = XMEM_AFF_LARGE_HINTED_FP32;
+    } else {
+        r.route = XMEM_AFF_LARGE_HINTED_FILTER16;
+        aff_filter16_plan(HW, tiles, &r.f_nw, &r.f_splits, &r.f_tps);
+        r.lcap = aff_filter16_list_cap(base); r.lstride = aff_filter16_list_stride(base);
+    }
+    return r;
+}
 }  // namespace
+
+extern "C" int xmem_affinity_plan_info(const int* seg_n_host, int n_seg, int HW, int top_k, const xmem_affinity_hint* hint,
+                                       xmem_affinity_plan* out) {
+    if (!seg_n_host || !out || n_seg <= 0 || n_seg > XMEM_MAX_SEGMENTS || HW <= 0) return XMEM_ERR_BAD_ARG;
+    if (top_k < 1 || top_k > AFF_MAX_TOPK) return XMEM_ERR_UNSUPPORTED;
+    int base = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        if (seg_n_host[i] < 0) return XMEM_ERR_BAD_ARG;
+        base += seg_n_host[i];
+    }
+    if (base < top_k) return XMEM_ERR_TOPK;
+    const AffRoute r = aff_route(seg_n_host, n_seg, HW, top_k, hint);
+    xmem_affinity_plan o = {};
+    o.route = r.route; o.tiles = r.tiles;
+    if (r.route == XMEM_AFF_SMALL) { o.splits = r.sel.splits; o.tiles_per_split = r.sel.tiles_per_split; }
+    else if (r.route == XMEM_AFF_LARGE_HINTED_FILTER16) {
+        o.splits = r.f_splits; o.tiles_per_split = r.f_tps; o.list_cap = r.lcap; o.list_stride = r.lstride;
+    } else {
+        o.splits = r.w_splits; o.tiles_per_split = r.w_tps; o.chunk = r.w_chunk;
+        if (r.route == XMEM_AFF_LARGE_SAMPLED) { o.bound_stride = r.R; o.bound_splits = r.bound.splits; }
+    }
+    *out = o;
+    return XMEM_OK;
+}
 
 extern "C" size_t xmem_affinity_topk_workspace_bytes(int n_total, int HW, int top_k) {
     if (n_total <= 0 || HW <= 0 || top_k <= 0) return 0;
@@ -1174,9 +1280,12 @@ extern "C" int xmem_affinity_topk_hinted(const xmem_key_segment* segs, int n_seg
     int rc;
     a.tau_init = nullptr; a.ovf = nullptr; a.cand_spill = nullptr; a.merge_splits = 0;
 
-    if (tiles < 256 || top_k > AFW_CAP) {
+    int seg_n[XMEM_MAX_SEGMENTS];
+    for (int i = 0; i < n_seg; ++i) seg_n[i] = segs[i].n;
+    const AffRoute rt = aff_route(seg_n, n_seg, HW, top_k, hint);
+    if (rt.route == XMEM_AFF_SMALL) {
         // ---- small memories: one safe pass (worst-case LDS buffers + exact re-rank valve), per-split lists, wave-per-query merge
-        AffPlan pl = aff_plan(tiles, HW, top_k, false);
+        const AffPlan pl = rt.sel;
         a.limit = pl.limit; a.cap = pl.cap; a.splits = pl.splits; a.tiles_per_split = pl.tiles_per_split; a.sub_tiles = pl.sub_tiles;
         a.tile_stride = 1; a.chunk = 0;
         auto kern = affinity_kernel<64, 2>;
@@ -1195,23 +1304,10 @@ extern "C" int xmem_affinity_topk_hinted(const xmem_key_segment* segs, int n_seg
     for (int i = 0; i < XMEM_MAX_SEGMENTS; ++i) w.seg[i] = a.seg[i];
     w.n_seg = ns; w.total_tiles = tiles; w.qk = qk; w.qe = qe; w.HW = HW; w.top_k = top_k;
     w.tau_init = tau0; w.gcand = gcand; w.gcnt = gcnt; w.ovf = ovf;
-    // one 8-wave workgroup per CU: splits so that query tiles x splits fills (at most) the 256 CUs, >= 8 tiles per wave
-    int sp = 256 / qt128; if (sp < 1) sp = 1;
-    { int maxs = tiles / (8 * AFW_WAVES); if (maxs < 1) maxs = 1; if (sp > maxs) sp = maxs; }
-    if (sp > 32) sp = 32;                              // AFW_GCAP = 32 splits x 64 entries
     w.sub_tiles = tiles;
-    w.tiles_per_split = cdiv(tiles, sp);
-    w.splits = cdiv(tiles, w.tiles_per_split);
-    // chunks of ~half a memory frame dealt round-robin to the splits (temporal clusters of good matches would otherwise pile
-    // up in one split's candidate lists), when every split gets >= 16 chunks
-    int sel_chunk = cdiv(HW, AFF_ROWS) / 2; if (sel_chunk < AFW_WAVES) sel_chunk = AFW_WAVES;
-    sel_chunk = cdiv(sel_chunk, AFW_WAVES) * AFW_WAVES;
-    const int n_chunks = cdiv(tiles, sel_chunk);
-    if (n_chunks < 16 * w.splits) sel_chunk = 0;
-    w.chunk = sel_chunk;
-    if (sel_chunk) w.tiles_per_split = cdiv(n_chunks, w.splits) * sel_chunk;
+    w.splits = rt.w_splits; w.tiles_per_split = rt.w_tps; w.chunk = rt.w_chunk;      // aff_route
 
-    const bool hinted = hint && hint->idx && hint->top_k >= top_k && hint->top_k <= 64 && hint->n_seg == n_seg;
+    const bool hinted = rt.route != XMEM_AFF_LARGE_SAMPLED;
     if (hinted) {
         HintArgs h;
         for (int i = 0; i < XMEM_MAX_SEGMENTS; ++i) { h.seg[i] = a.seg[i]; h.old_n[i] = 0; }
@@ -1225,7 +1321,7 @@ extern "C" int xmem_affinity_topk_hinted(const xmem_key_segment* segs, int n_seg
         h.old_seg = n_seg;
         h.hint_idx = hint->idx; h.hint_k = hint->top_k; h.grid_w = hint->grid_w > 0 ? hint->grid_w : 0;
         h.qk = qk; h.qe = qe; h.HW = HW; h.top_k = top_k; h.tau0 = tau0; h.gcnt = gcnt; h.ovf = ovf;
-        const bool use16 = aff_use_filter16();
+        const bool use16 = rt.route == XMEM_AFF_LARGE_HINTED_FILTER16;
         h.qop16 = use16 ? reinterpret_cast<_Float16*>(ws + wl.qop16_off) : nullptr;
         h.qmeta = use16 ? reinterpret_cast<float*>(ws + wl.qmeta_off) : nullptr;
         h.flag1 = use16 ? reinterpret_cast<int*>(ws + wl.flag_off) : nullptr;
@@ -1238,20 +1334,19 @@ extern "C" int xmem_affinity_topk_hinted(const xmem_key_segment* segs, int n_seg
             Filter16Args f;
             for (int i = 0; i < XMEM_MAX_SEGMENTS; ++i) f.seg[i] = a.seg[i];
             f.n_seg = ns; f.total_tiles = tiles; f.qk = qk; f.qe = qe; f.HW = HW; f.top_k = top_k;
-            f.splits = 0; f.tiles_per_split = 0;
+            f.nw = rt.f_nw; f.splits = rt.f_splits; f.tiles_per_split = rt.f_tps;
             f.qop16 = h.qop16; f.qmeta = h.qmeta;
             f.rows16 = reinterpret_cast<_Float16*>(ws + wl.rows16_off);
-            f.tau = tau0; f.gcand32 = reinterpret_cast<int*>(ws + wl.gcand32_off); f.gcnt = h.fcnt; f.cnt_diag = gcnt; f.lcap = aff_filter16_list_cap(base);
-            f.lcap1 = f.lcap; f.lstride = aff_filter16_list_stride(base);
+            f.tau = tau0; f.gcand32 = reinterpret_cast<int*>(ws + wl.gcand32_off); f.gcnt = h.fcnt; f.cnt_diag = gcnt; f.lcap = rt.lcap;
+            f.lcap1 = f.lcap; f.lstride = rt.lstride;
             f.flag1 = h.flag1; f.flag2 = h.flag2; f.only = nullptr; f.flag_out = nullptr;
             f.out_w = out_w; f.out_idx = out_idx; f.out_sim = out_sim;
             return aff_filter16_launch(f, stream);
         }
     } else {
-        // sampled bound pass: every 4th 32-row tile (every 8th for very large chunk-dealt memories)
-        int R = 4;
-        if (sel_chunk && tiles >= 8192) R = 8;
-        AffPlan pa = aff_plan(cdiv(tiles, R), HW, top_k, true, base);
+        // sampled bound pass: every R-th 32-row tile
+        const int R = rt.R;
+        const AffPlan pa = rt.bound;
         a.cap = 0; a.limit = 0; a.splits = pa.splits; a.tiles_per_split = pa.tiles_per_split; a.sub_tiles = pa.sub_tiles;
         a.tile_stride = R; a.chunk = 0;
         hipLaunchKernelGGL((affinity_kernel<64, 0>), dim3(cdiv(HW, AFF_BQ), pa.splits), dim3(256), pa.lds, s, a);

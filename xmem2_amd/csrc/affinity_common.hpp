@@ -35,9 +35,13 @@ template <class P> __device__ __forceinline__ SegDev seg_of_slot(const P& p, int
     return s;
 }
 
-// 64-bit candidate key: larger similarity first, then LOWER memory index (keys are unique because the index is part of them)
+// 64-bit candidate key: larger similarity first, then LOWER memory index (keys are unique because the index is part of them).
+// The two zeros are ONE value: -0.0f is keyed (and handed back by key_val) as +0.0f.  A chain whose terms are all -0 (b_sq = 0, and
+// per channel x = 0 or e = 0 with x k < 0) ends in -0 where a neighbouring row ends in +0; ordered apart, such a tie would go to the
+// row with the +0 instead of the lower index.
 __device__ __forceinline__ unsigned f2ord(float f) {
-    const unsigned u = __float_as_uint(f);
+    const unsigned s = __float_as_uint(f);
+    const unsigned u = s == 0x80000000u ? 0u : s;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float ord2f(unsigned o) {
@@ -74,7 +78,8 @@ struct Filter16Args {
     int n_seg, total_tiles;
     const float* qk; const float* qe;
     int HW, top_k;
-    int splits, tiles_per_split, qtiles;   // set by aff_filter16_launch (qtiles = query tiles of 128)
+    int nw, splits, tiles_per_split;       // from aff_filter16_plan: waves of a filter workgroup (4 | 8), splits, tiles per split
+    int qtiles;                            // set by aff_filter16_launch: query tiles of 64 nw
     const _Float16* qop16;           // [HW][F16_K] query operand rows          } written by the bound kernel
     const float* qmeta;              // [HW][4]   b_sq (select kernels' arithmetic), 0, 0, 0   }
     _Float16* rows16;                // workspace [N + 32][F16_K] for segments whose caller keeps no operand rows (seg[i].rows16 == 0 on entry)
@@ -98,4 +103,5 @@ struct Filter16Args {
 size_t aff_filter16_rows_bytes(int n_total);
 int aff_filter16_list_cap(int n_total);
 int aff_filter16_list_stride(int n_total);
+void aff_filter16_plan(int HW, int total_tiles, int* nw, int* splits, int* tiles_per_split);
 int aff_filter16_launch(Filter16Args a, void* stream);            // rows, filter (lists), tighten, filter, refine

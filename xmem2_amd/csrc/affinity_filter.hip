@@ -631,19 +631,27 @@ extern "C" int xmem_affinity_rows16(const float* key, const float* shrinkage, in
     return xmem_check_launch();
 }
 
-int aff_filter16_launch(Filter16Args a, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// Grid arithmetic of the filter: waves per workgroup, splits of the memory's tiles, tiles per split.
+void aff_filter16_plan(int HW, int total_tiles, int* nw_out, int* splits, int* tiles_per_split) {
     // 8-wave workgroups (512 queries, one per CU) when the query count fills them and the memory is long enough: the rows
     // cross the fabric once per 512 instead of once per 256 queries
-    const int nw = (a.HW >= 2048 && a.total_tiles >= 8192) ? 8 : 4;
+    const int nw = (HW >= 2048 && total_tiles >= 8192) ? 8 : 4;
     const int wgq = 64 * nw, stage = nw, per_xcd = nw == 4 ? 32 * F16_WG_PER_CU : 32;
-    const int qt = cdiv(a.HW, wgq);
+    const int qt = cdiv(HW, wgq);
     // all workgroups of a split resident on one XCD at once when the query tiles allow: 8 x floor(per_xcd / query tiles) splits,
     // whole LDS stages, >= 2 stages per split
     int sp = 8 * (per_xcd / qt); if (sp < 8) sp = 8;
-    { int maxs = a.total_tiles / (2 * stage); if (maxs < 1) maxs = 1; if (sp > maxs) sp = maxs; }
-    a.tiles_per_split = cdiv(cdiv(a.total_tiles, sp), stage) * stage;
-    a.splits = cdiv(a.total_tiles, a.tiles_per_split);
+    { int maxs = total_tiles / (2 * stage); if (maxs < 1) maxs = 1; if (sp > maxs) sp = maxs; }
+    *nw_out = nw;
+    *tiles_per_split = cdiv(cdiv(total_tiles, sp), stage) * stage;
+    *splits = cdiv(total_tiles, *tiles_per_split);
+}
+
+int aff_filter16_launch(Filter16Args a, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // workgroup size and splits: aff_filter16_plan, through the caller (a.nw, a.splits, a.tiles_per_split)
+    const int nw = a.nw;
+    const int qt = cdiv(a.HW, 64 * nw);
     int n_total = 0;
     for (int i = 0; i < a.n_seg; ++i) n_total += a.seg[i].n;
     a.qtiles = qt;
