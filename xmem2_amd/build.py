@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
-SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip', 'components.hip']
+SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip', 'components.hip', 'polygons.hip']
 HEADERS = ['common.hpp', 'host_math.hpp', 'affinity_common.hpp', 'conv_plan.hpp', 'conv_mfma.hpp', 'conv_winograd.hpp', 'gemm_stream.hpp',
            'pointwise_pair.hpp']
 LIB = os.path.join(CSRC, 'libxmem_hip.so')
@@ -22,7 +22,7 @@ EXTRA_FLAGS = {'augment.hip': ['-ffp-contract=off']}      # per-source flags: th
 # the subtarget feature turned off the same runs are bit-identical to the solo runs.  (The flag reaches the host compilation
 # too, which prints an 'ignoring feature' note - filtered below.)
 INCLUDE = os.path.join(os.path.dirname(CSRC), '..', 'include')
-PUBLIC_HEADERS = ['xmem_hip.h', 'xmem_hip_masks.h']      # the frozen ABI-5 header and the one that declares what came after it
+PUBLIC_HEADERS = ['xmem_hip.h', 'xmem_hip_masks.h', 'xmem_hip_polygons.h']      # the frozen ABI-5 header and the two that declare what came after it
 DEVICE_FLAGS = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 _NOISE = "'-packed-fp32-ops' is not a recognized feature for this target (ignoring feature)"
 

@@ -1888,3 +1888,52 @@ def clean_masks(masks, min_area=0, max_hole=0, keep_largest=False, out=None):
     check(lib.xmem_mask_clean(ptr(masks), N, H, W, spec.get('min_area', 0), spec.get('max_hole', 0), int(spec.get('keep_largest', False)),
                               ptr(out), ptr(stats), ptr(ws), ws.numel(), stream_ptr()))
     return out, stats
+
+
+# ---- polygon outlines (csrc/polygons.hip, include/xmem_hip_polygons.h): integer, bit-reproducible ------------------------------
+
+POLY_STATS = {'launches': 0, 'retries': 0}     # calls of xmem_mask_polygons / frames traced again because their corners did not fit
+
+
+def mask_polygons(masks, K, capacity=None, wait=True):
+    """Polygon outlines of the labels 1..K of uint8 index maps `masks` [H,W] or [B,H,W] on the device: `polygons.record_host` per
+    frame, word for word (xmem2_amd/polygons.py has the definition).  `capacity`: corners per frame there is room for (default
+    `polygons.default_capacity`).  wait=True: returns (meta int32 [B,K,2] = corners, rings per label, list of B uint32 arrays: the
+    frame's corner words of label 1, 2, ... back to back, x | y << 16 | first of its ring << 31) on the HOST; a frame whose corners did
+    not fit is traced again with exactly its size.  wait=False: one launch sequence on the current stream and no synchronisation;
+    returns the int32 device tensor `polygons.split_record(., B, K, capacity)` takes apart, whose true counts tell the caller which
+    frames to trace again."""
+    from . import _lib_polygons, polygons
+    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
+        raise RuntimeError('masks: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
+    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= 254):
+        raise ValueError(f'mask_polygons: K = {K!r} must be an integer in 1..254')
+    masks = masks.contiguous()
+    B, H, W = (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
+    if B == 0 or H == 0 or W == 0:
+        raise RuntimeError(f'mask_polygons: empty input {tuple(masks.shape)}')
+    capacity = polygons.default_capacity(H, W) if capacity is None else int(capacity)
+    if not 1 <= capacity <= _lib_polygons.MAX_CAPACITY:
+        raise ValueError(f'mask_polygons: capacity = {capacity} must be in 1..{_lib_polygons.MAX_CAPACITY}')
+    lib = _lib_polygons.load()
+    rec = torch.empty(B * K * polygons.META + B * capacity, dtype=torch.int32, device=masks.device)
+    nbytes = lib.xmem_mask_polygons_workspace_bytes(B, H, W, K, capacity)
+    ws = workspace(max(nbytes, 8), masks.device, 'polygons')
+    POLY_STATS['launches'] += 1
+    check(lib.xmem_mask_polygons(ptr(masks), B, H, W, K, capacity, ptr(rec), C.c_void_p(rec.data_ptr() + 4 * B * K * polygons.META),
+                                 ptr(ws), ws.numel(), stream_ptr()))
+    if not wait:
+        return rec
+    meta, corners = polygons.split_record(rec.cpu().numpy(), B, K, capacity)
+    out = []
+    for b in range(B):
+        total = int(meta[b, :, 0].sum())
+        if total > capacity:                                  # the counts are the true ones: once more, with room for all of them
+            POLY_STATS['retries'] += 1
+            meta_b, words_b = mask_polygons(masks[b:b + 1], K, capacity=total)
+            if (meta_b[0] != meta[b]).any():
+                raise RuntimeError('mask_polygons: a frame traced again gave other counts')
+            out.append(words_b[0])
+        else:
+            out.append(corners[b, :total].copy())
+    return meta.copy(), out

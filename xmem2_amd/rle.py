@@ -23,6 +23,9 @@ to the count two before, every value as little-endian groups of 5 bits with a co
 `pycocotools.mask.decode` takes.  The device builds the strings from the event record (`ops.rle_compress`: per count a function of
 four neighbouring events, then a scan) and reads them back into the record (`ops.rle_decompress`); every reader here takes both
 forms, also mixed in one file.  A frame in which a label has no pixel, or which has no mask at all, carries null in all three lists.
+With config['tracks_polygons'] an entry also holds "polygons": [[x0, y0, x1, y1, ...], ...], its outline as rings of lattice corners
+(xmem2_amd/polygons.py, traced by `ops.mask_polygons`), and the video "polygons": {"tolerance": t, "fill": "evenodd"}; no reader here
+needs the key.
 `python -m xmem2_amd.rle --tracks F --out DIR` is the way back to index PNGs (`--recode` rewrites a file in the other form);
 `TrackReader` is the way back without them: counts to events per event (`events_from_counts`), events to label maps
 on the device (`ops.rle_decode`) - for scoring (`metrics.compute_metrics`), as annotations (`run_on_video.VideoReader`) and for
@@ -228,15 +231,21 @@ class TrackWriter:
     """One video's tracks.  Frames are added in order; a track is opened when its label is first named and has null wherever the
     label was not known yet, had no pixel, or the frame had no mask."""
 
-    def __init__(self, height, width):
+    def __init__(self, height, width, polygons=None):
+        """`polygons`: config['tracks_polygons'] (None: the file is what it is without the option; xmem2_amd/polygons.py)."""
+        from .polygons import parse_polygons
         self.height, self.width = int(height), int(width)
         self.file_names = []
         self._tracks = collections.OrderedDict()                     # label in the annotation PNGs -> {frame index: (counts, bbox, area)}
+        self.polygons = parse_polygons(polygons)
+        self._rings = {}                                             # (label, frame index) -> the entry's rings as flat integer lists
 
-    def add_frame(self, file_name, meta=None, events=None, labels=None, strings=None):
+    def add_frame(self, file_name, meta=None, events=None, labels=None, strings=None, polygons=None):
         """`meta` [K, META] and the frame's packed `events` as `ops.rle_encode` gives them (`events` holding all of them), `labels`
         the annotation's label of every row (default 1..K; `inverse_labels`).  Without `meta` the frame has no mask.  `strings`: the
-        rows' compressed counts as `ops.rle_compress` gives them; they are written in place of the lists and `events` is not read."""
+        rows' compressed counts as `ops.rle_compress` gives them; they are written in place of the lists and `events` is not read.
+        `polygons`: (meta [K, 2], packed corner words) of the frame as `ops.mask_polygons` gives them; a writer made with the option
+        needs them for every frame that has a mask, and simplifies each ring with its tolerance."""
         t = len(self.file_names)
         self.file_names.append(str(file_name))
         if meta is None:
@@ -248,9 +257,19 @@ class TrackWriter:
         if strings is not None and len(strings) != len(meta):
             raise ValueError(f'add_frame: {len(meta)} label rows, {len(strings)} strings')
         rows = label_events(meta, events) if strings is None else strings
-        for lab, row, ev in zip(labels, meta, rows):
+        if (polygons is None) != (self.polygons is None):
+            raise ValueError('add_frame: a frame\'s polygons are given exactly when the writer was made with the option')
+        rings = [None] * len(meta)
+        if polygons is not None:
+            from . import polygons as poly
+            if len(polygons[0]) != len(meta):
+                raise ValueError(f'add_frame: {len(meta)} label rows, polygons of {len(polygons[0])}')
+            rings = poly.label_flat(*polygons, tolerance=self.polygons['tolerance'])
+        for lab, row, ev, rr in zip(labels, meta, rows, rings):
             track = self._tracks.setdefault(lab, {})
             area = int(row[1])
+            if area and rr is not None:
+                self._rings[(lab, t)] = rr
             if area:
                 x0, y0, x1, y1 = (int(v) for v in row[2:6])
                 counts = counts_from_events(ev, self.height, self.width) if strings is None else str(ev)
@@ -266,24 +285,32 @@ class TrackWriter:
         if tuple(mask.shape) != (self.height, self.width):
             raise ValueError(f'add_mask: expected {(self.height, self.width)}, got {tuple(mask.shape)}')
         k = int(mask.max()) if k is None else int(k)
+        from . import polygons as poly
         if k == 0:
-            return self.add_frame(file_name, np.zeros((0, META), np.int32), np.zeros(0, np.uint32), [])
+            return self.add_frame(file_name, np.zeros((0, META), np.int32), np.zeros(0, np.uint32), [],
+                                  polygons=None if self.polygons is None else (np.zeros((0, poly.META), np.int32), np.zeros(0, np.uint32)))
         meta, events = record_host(mask, k)
         strings = None
         if counts == 'compressed':
             strings = [compress_counts(counts_from_events(ev, self.height, self.width)) for ev in label_events(meta, events)]
-        return self.add_frame(file_name, meta, events, labels=labels, strings=strings)
+        return self.add_frame(file_name, meta, events, labels=labels, strings=strings,      # on the host, so are the rings
+                              polygons=None if self.polygons is None else poly.record_host(mask, k))
 
     def to_dict(self):
         T, size = len(self.file_names), [self.height, self.width]
         anns = []
         for n, (lab, track) in enumerate(self._tracks.items(), start=1):
             seg = [{'size': size, 'counts': track[t][0]} if t in track else None for t in range(T)]
+            if self.polygons is not None:
+                for t in track:
+                    seg[t]['polygons'] = self._rings[(lab, t)]
             anns.append({'id': n, 'video_id': 1, 'category_id': 1, 'label': lab, 'segmentations': seg,
                          'bboxes': [track[t][1] if t in track else None for t in range(T)],
                          'areas': [track[t][2] if t in track else None for t in range(T)]})
-        return {'videos': [{'id': 1, 'height': self.height, 'width': self.width, 'length': T, 'file_names': list(self.file_names)}],
-                'categories': [{'id': 1, 'name': 'object'}], 'annotations': anns}
+        video = {'id': 1, 'height': self.height, 'width': self.width, 'length': T, 'file_names': list(self.file_names)}
+        if self.polygons is not None:                                # simplified rings are lossy: the file says how it was written
+            video['polygons'] = {'tolerance': self.polygons['tolerance'], 'fill': 'evenodd'}
+        return {'videos': [video], 'categories': [{'id': 1, 'name': 'object'}], 'annotations': anns}
 
     def write(self, path):
         """Write the file (`path`: the file, or a directory that gets tracks.json); returns the file's path."""
@@ -561,20 +588,59 @@ def clean_tracks(tracks, spec, batch=32):
     return doc, dict(zip(STATS, (int(v) for v in totals.tolist())))
 
 
+def polygon_tracks(tracks, spec=True, batch=32):
+    """A tracks file (or parsed document) with the `polygons` key added to every entry (replaced where there was one) -> document.
+    Per batch: `TrackReader.masks_device` (dense ids, one per track) -> `ops.mask_polygons`; no mask plane reaches the host.
+    Everything else in the file - counts, boxes, areas, the order of the keys - is kept.  `spec`: config['tracks_polygons'].
+    The frames are decoded as label maps, so where two tracks overlap the later one owns the pixels (as in `read_tracks`); the
+    files this project writes have no overlap."""
+    from . import ops
+    from . import polygons as poly
+    spec = poly.parse_polygons(spec)
+    if spec is None:
+        raise ValueError('polygon_tracks: the option is off')
+    reader = TrackReader(tracks)
+    if isinstance(tracks, dict):
+        doc = json.loads(json.dumps(tracks))                         # a deep copy that keeps the order of the keys
+    else:
+        with open(tracks) as f:
+            doc = json.load(f)
+    if len(set(reader.labels)) != len(reader.labels):
+        raise ValueError('polygon_tracks: two tracks share a label')
+    k, step = len(reader.labels), max(1, int(batch))
+    for i in range(0, len(reader) if k else 0, step):
+        frames = list(range(i, min(i + step, len(reader))))
+        dense, _ = reader.masks_device(frames, values='dense', batch=step)
+        meta, words = ops.mask_polygons(dense, k)
+        for j, t in enumerate(frames):
+            for ann, rings in zip(doc['annotations'], poly.label_flat(meta[j], words[j], spec['tolerance'])):
+                seg = ann['segmentations'][t]
+                if seg is not None:
+                    seg['polygons'] = rings
+    doc['videos'][0]['polygons'] = {'tolerance': spec['tolerance'], 'fill': 'evenodd'}
+    return doc
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle',
-                                 description='tracks.json -> index PNGs (one per frame), or - with --recode and / or --clean - '
-                                             'tracks.json with its counts in the other form and / or its masks cleaned on the device')
+                                 description='tracks.json -> index PNGs (one per frame), or - with --recode, --clean and / or --polygons - '
+                                             'tracks.json with its counts in the other form, its masks cleaned on the device and / or '
+                                             'their polygon outlines added')
     ap.add_argument('--tracks', required=True, help='the tracks.json of one video (counts as lists, compressed strings, or both)')
-    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode or --clean the file that is written')
+    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode, --clean or --polygons the file that is written')
     ap.add_argument('--recode', default=None, choices=COUNT_FORMS,
                     help='write no PNGs: rewrite the file with every counts entry as a list or as the compressed COCO string')
     ap.add_argument('--clean', default=None, metavar='JSON',
                     help='write no PNGs: rewrite the file with every mask cleaned, e.g. \'{"min_area": 16, "max_hole": 16}\' '
                          '(keys min_area, max_hole, keep_largest; needs the GPU); the count form is kept unless --recode names one')
+    ap.add_argument('--polygons', nargs='?', const=0.0, default=None, type=float, metavar='TOL',
+                    help='write no PNGs: rewrite the file with the polygon outlines of every entry added (key "polygons"), traced on '
+                         'the device (needs the GPU); TOL > 0 simplifies every ring (Ramer-Douglas-Peucker, lossy)')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
     args = ap.parse_args(argv)
+    if args.polygons is not None and not (0 <= args.polygons < float('inf')):
+        ap.error('--polygons: the tolerance must be a finite number >= 0')
     if args.clean is not None:
         from .mask_cleanup import parse_cleanup
         try:
@@ -588,13 +654,16 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.recode is not None or args.clean is not None:
+    if args.recode is not None or args.clean is not None or args.polygons is not None:
         report = {}
         if args.clean is not None:
             doc, report['clean'] = clean_tracks(args.tracks, args.clean)
         else:
             with open(args.tracks) as f:
                 doc = json.load(f)
+        if args.polygons is not None:                                # of the cleaned masks, when both are asked for
+            doc = polygon_tracks(doc, {'tolerance': args.polygons})
+            report['polygons'] = doc['videos'][0]['polygons']
         if args.recode is not None:
             doc = recode_tracks(doc, args.recode)
             report['recode'] = args.recode

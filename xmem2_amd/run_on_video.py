@@ -331,12 +331,18 @@ class _TrackLoop:
     whose events did not fit is encoded again when its record arrives, and the capacity of the frames after it grows to twice its size.
     counts='compressed' (config['tracks_counts']): `ops.rle_compress` runs right behind the encoder on the same stream and what
     travels is meta + string lengths + characters, not the events; a frame whose events or characters did not fit is done again at
-    its exact size when its record arrives."""
+    its exact size when its record arrives.
+    polygons (config['tracks_polygons']): `ops.mask_polygons` runs right behind the encoder (and the compressor) on the same stream,
+    its record travels at the end of the same buffer, and a frame whose corners did not fit is traced again when it arrives, the
+    capacity of the frames after it growing to twice its size.  Without the option nothing is loaded or launched for it."""
 
-    def __init__(self, counts='list'):
+    def __init__(self, counts='list', polygons=None):
+        from .polygons import parse_polygons
         from .rle import check_count_form
         self.counts = check_count_form(counts)
-        self.writer = self.capacity = self.char_capacity = None      # made for the first frame's size (that of the written PNGs)
+        self.polygons = parse_polygons(polygons)
+        # made for the first frame's size (that of the written PNGs)
+        self.writer = self.capacity = self.char_capacity = self.poly_capacity = None
         self.fetcher = AsyncMaskFetcher()
 
     def submit(self, tag, mask_dev, k):
@@ -344,24 +350,37 @@ class _TrackLoop:
         encoded again should its events not fit."""
         if self.writer is None:
             from .rle import TrackWriter, default_capacity, default_char_capacity
-            self.writer, self.capacity = TrackWriter(*mask_dev.shape), default_capacity(*mask_dev.shape)
+            self.writer, self.capacity = TrackWriter(*mask_dev.shape, polygons=self.polygons), default_capacity(*mask_dev.shape)
             self.char_capacity = default_char_capacity(*mask_dev.shape)
+            if self.polygons is not None:
+                from .polygons import default_capacity as default_corners
+                self.poly_capacity = default_corners(*mask_dev.shape)
         rec = ops.rle_encode(mask_dev, k, self.capacity, wait=False)
         if self.counts == 'compressed':
             from .rle import META
             srec = ops.rle_compress(rec, *mask_dev.shape, k, self.capacity, self.char_capacity, wait=False)
-            return self.fetcher.submit((tag, mask_dev, k, self.capacity, self.char_capacity),
-                                       torch.cat((rec[:k * META].view(torch.uint8), srec)))
-        return self.fetcher.submit((tag, mask_dev, k, self.capacity), rec.view(torch.uint8))
+            parts, sizes = [rec[:k * META].view(torch.uint8), srec], (self.capacity, self.char_capacity)
+        else:
+            parts, sizes = [rec.view(torch.uint8)], (self.capacity,)
+        if self.polygons is not None:                                # the last 4 (2 k + poly_capacity) bytes of what travels
+            parts.append(ops.mask_polygons(mask_dev, k, self.poly_capacity, wait=False).view(torch.uint8))
+        return self.fetcher.submit((tag, mask_dev, k) + sizes + (self.poly_capacity,),
+                                   torch.cat(parts) if len(parts) > 1 else parts[0])
 
     def drain(self):
         return self.fetcher.drain()
 
     def finish(self, item, name, mapper):
         from .rle import inverse_labels, split_record
+        (_, mask_dev, k, *_sizes, poly_capacity), buf = item
+        rings = None
+        if poly_capacity is not None:
+            from .polygons import META as POLY_META
+            n = 4 * (k * POLY_META + poly_capacity)
+            rings, buf = self._finish_polygons(mask_dev, k, poly_capacity, buf[len(buf) - n:]), buf[:len(buf) - n]
         if self.counts == 'compressed':
-            return self._finish_compressed(item, name, mapper)
-        (_, mask_dev, k, capacity), buf = item
+            return self._finish_compressed((item[0][:-1], buf), name, mapper, rings)
+        capacity = _sizes[0]
         meta, events = split_record(buf, 1, k, capacity)
         meta, events = meta[0], events[0]
         total = int(meta[:, 0].sum())
@@ -370,9 +389,23 @@ class _TrackLoop:
             meta_all, ev_all = ops.rle_encode(mask_dev, k, capacity=total)
             meta, events = meta_all[0], ev_all[0]
             self.capacity = max(self.capacity, 2 * total)            # and the frames to come get room for a video as ragged as this
-        self.writer.add_frame(name, meta, events, inverse_labels(mapper, k))
+        self.writer.add_frame(name, meta, events, inverse_labels(mapper, k), polygons=rings)
 
-    def _finish_compressed(self, item, name, mapper):
+    def _finish_polygons(self, mask_dev, k, capacity, buf):
+        """-> (meta [k, 2], the frame's corner words) of the record that arrived; the frame is traced again when they did not fit"""
+        from .polygons import split_record
+        meta, corners = split_record(buf.view(np.int32), 1, k, capacity)
+        meta, total = meta[0], int(meta[0, :, 0].sum())
+        if total <= capacity:
+            return meta, corners[0, :total]
+        ops.POLY_STATS['retries'] += 1                               # the exact size is known now: once more, nothing is cut off
+        meta_all, words_all = ops.mask_polygons(mask_dev, k, capacity=total)
+        if (meta_all[0] != meta).any():
+            raise RuntimeError('tracks_polygons: a frame traced again gave other counts')
+        self.poly_capacity = max(self.poly_capacity, 2 * total)      # and the frames to come get room for a video as ragged as this
+        return meta_all[0], words_all[0]
+
+    def _finish_compressed(self, item, name, mapper, rings=None):
         from .rle import META, inverse_labels, label_strings, split_string_record
         (_, mask_dev, k, capacity, char_capacity), buf = item
         meta = buf[:4 * k * META].view(np.int32).reshape(k, META)
@@ -389,7 +422,7 @@ class _TrackLoop:
             self.char_capacity = max(self.char_capacity, 2 * sum(len(v) for v in strings))
         else:
             strings = label_strings(str_len[0], chars[0])
-        self.writer.add_frame(name, meta, None, inverse_labels(mapper, k), strings=strings)
+        self.writer.add_frame(name, meta, None, inverse_labels(mapper, k), strings=strings, polygons=rings)
 
     def write(self, masks_out_path):
         return self.writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
@@ -648,7 +681,8 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     outputs = _FrameOutputs(
         vid_reader, mapper, AsyncMaskFetcher(),
         saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
-        tracks=_TrackLoop(config.get('tracks_counts', 'list')) if config.get('save_tracks', False) else None, scorer=scorer,
+        tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
+        scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'])
 
     def hint(samples):
@@ -882,7 +916,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again - unless cleaned
         vid_reader, mapper, AsyncMaskFetcher(),
         saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
-        tracks=_TrackLoop(config.get('tracks_counts', 'list')) if config.get('save_tracks', False) else None, scorer=scorer,
+        tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
+        scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 

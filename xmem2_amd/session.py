@@ -494,24 +494,29 @@ class VideoSession:
         finally:
             saver.close()
 
-    def save_tracks(self, masks_out_path, batch=32, counts='list'):
+    def save_tracks(self, masks_out_path, batch=32, counts='list', polygons=None):
         """<masks_out_path>/tracks.json (xmem2_amd/rle.py) of the masks as they stand: the frames that have one are encoded from the
         resident `masks` in launches of `batch` frames and only their run boundaries, areas and boxes reach the host; a frame without a
         mask has null in every track.  counts='compressed': the record stays on the device, is turned into the compressed COCO strings
-        there (`ops.rle_compress`) and those reach the host instead of the events.  Returns the file's path."""
+        there (`ops.rle_compress`) and those reach the host instead of the events.  `polygons` (config['tracks_polygons']: None, True
+        or {'tolerance': t}): every entry gains its polygon outlines, traced on the device (`ops.mask_polygons`), corners and never a
+        mask reaching the host.  Returns the file's path."""
         from .rle import META, TrackWriter, check_count_form, default_capacity, inverse_labels
         check_count_form(counts)
         k = len(self.mapper.labels)
         if k == 0:
             raise ValueError('No valid masks provided!')
         labels = inverse_labels(self.mapper, k)
-        writer = TrackWriter(*self.shape)
+        writer = TrackWriter(*self.shape, polygons=polygons)
         present = [t for t, p in enumerate(self._present) if p]
-        encoded = {}
+        encoded, rings = {}, {}
         for i in range(0, len(present), max(1, int(batch))):
             chunk = present[i:i + max(1, int(batch))]
             contiguous = chunk == list(range(chunk[0], chunk[-1] + 1))
             dev = self.masks[chunk[0]:chunk[-1] + 1] if contiguous else self.masks[torch.tensor(chunk, device=self.device)]
+            if writer.polygons is not None:
+                pmeta, words = ops.mask_polygons(dev, k)
+                rings.update((t, (pmeta[j], words[j])) for j, t in enumerate(chunk))
             if counts == 'compressed':
                 capacity = default_capacity(*self.shape)
                 rec = ops.rle_encode(dev, k, capacity, wait=False)
@@ -528,7 +533,7 @@ class VideoSession:
                 encoded[t] = (meta[j], events[j], None)
         for t, fr in enumerate(self.frames):
             meta, events, strings = encoded.get(t, (None, None, None))
-            writer.add_frame(fr.frame, meta, events, labels=labels, strings=strings)
+            writer.add_frame(fr.frame, meta, events, labels=labels, strings=strings, polygons=rings.get(t))
         return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
 
     def load_tracks(self, path, batch=32):
@@ -628,6 +633,8 @@ def parse_args(argv=None):
     ap.add_argument('--tracks', action='store_true', help='write <out>/tracks.json, run-length tracks encoded on the device, next to the masks')
     ap.add_argument('--tracks-counts', default='list', choices=('list', 'compressed'),
                     help='the counts in tracks.json: uncompressed lists, or the compressed COCO strings built on the device')
+    ap.add_argument('--tracks-polygons', nargs='?', const=0.0, default=None, type=float, metavar='TOL',
+                    help='with --tracks: add the polygon outlines of every entry, traced on the device; TOL > 0 simplifies the rings (lossy)')
     ap.add_argument('--feature-cache-gb', type=float, default=0.0,
                     help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
@@ -658,7 +665,8 @@ def main(argv=None):
         print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
     s.save(args.out, save_overlay=args.overlay)
     if args.tracks:
-        s.save_tracks(args.out, counts=args.tracks_counts)
+        s.save_tracks(args.out, counts=args.tracks_counts,
+                      polygons=None if args.tracks_polygons is None else {'tolerance': args.tracks_polygons})
     return 0
 
 
