@@ -1937,3 +1937,98 @@ def mask_polygons(masks, K, capacity=None, wait=True):
         else:
             out.append(corners[b, :total].copy())
     return meta.copy(), out
+
+
+# ---- polygons filled back into masks (csrc/polygons_fill.hip, include/xmem_hip_raster.h): integer, bit-reproducible ------------
+
+FILL_STATS = {'launches': 0}                   # calls of xmem_polygons_fill
+FILL_WORKSPACE_CAP = 256 << 20                 # bytes of toggle bit-planes one call may ask for: larger jobs go in chunks of frames and rows
+FILL_MAX_ROWS = 254
+
+
+def fill_edges(edges, plane, N, H, W, R, values=None, frac_bits=8, out=None, overlay=False, check=True):
+    """`xmem_polygons_fill` on a packed edge list: `edges` int32 [E,4] = xa, ya, xb, yb in units of 1 / 2**frac_bits pixel with
+    ya < yb, `plane` int32 [E] = frame * R + row, as `polygons.pack_edges` gives them (host arrays; uploaded once).  `R` may exceed
+    254 and the planes `FILL_WORKSPACE_CAP`: the rows are then layered in chunks, lowest first, each over the ones before it, and the
+    frames go in chunks - every edge still goes up once, sorted by chunk.  Returns what `fill_polygons` returns."""
+    import numpy as np
+    from . import _lib_raster
+    for name, v, low, top in (('N', N, 1, 1 << 30), ('H', H, 1, 16384), ('W', W, 1, 16384), ('R', R, 1, 1 << 20),
+                              ('frac_bits', frac_bits, 0, _lib_raster.MAX_FRAC_BITS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (low <= v <= top):
+            raise ValueError(f'fill_polygons: {name} = {v!r} must be an integer in {low}..{top}')
+    N, H, W, R, frac_bits = int(N), int(H), int(W), int(R), int(frac_bits)
+    edges, plane = np.ascontiguousarray(edges, np.int32).reshape(-1, 4), np.ascontiguousarray(plane, np.int32).reshape(-1)
+    if len(edges) != len(plane):
+        raise ValueError(f'fill_polygons: {len(edges)} edges, {len(plane)} plane indices')
+    if values is None:
+        if R > 255:
+            raise ValueError(f'fill_polygons: {R} rows need a values table, row + 1 does not fit a byte')
+        values = np.arange(1, R + 1)
+    values = np.asarray(values)
+    if values.shape != (R,) or values.dtype.kind not in 'iu' or values.min() < 0 or values.max() > 255:
+        raise ValueError(f'fill_polygons: values must be {R} integers in 0..255')
+    if out is None:
+        if overlay:
+            raise ValueError('fill_polygons: overlay needs the planes to lay over (out)')
+        if not torch.cuda.is_available():
+            raise RuntimeError('fill_polygons: needs an MI355X (HIP) device - xmem2_amd has no CPU path')
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=torch.device('cuda', torch.cuda.current_device()))
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
+        raise RuntimeError(f'fill_polygons: out must be a contiguous uint8 CUDA (HIP) tensor {(N, H, W)} - xmem2_amd has no CPU path')
+    device = out.device
+    lib = _lib_raster.load()
+    per_plane = 4 * H * ((W + 1 + 31) // 32)
+    cap = max(int(FILL_WORKSPACE_CAP), per_plane)
+    rc = min(FILL_MAX_ROWS, R, cap // per_plane)                      # rows, then frames, of one call
+    fc = min(N, 65535, max(1, cap // (per_plane * rc)))
+    n_rc, n_fc = -(-R // rc), -(-N // fc)
+    # an edge whose plane is outside [0, N R) keeps an index no call accepts, and goes with the first call: the device counts it
+    ok = (plane >= 0) & (plane < N * R)
+    f, row = np.where(ok, plane // R, 0), np.where(ok, plane % R, 0)
+    chunk = (row // rc) * n_fc + f // fc
+    local = np.where(ok, (f % fc) * np.minimum(rc, R - row // rc * rc) + row % rc, -1).astype(np.int32)
+    order = np.argsort(chunk, kind='stable')
+    starts = np.searchsorted(chunk[order], np.arange(n_rc * n_fc + 1))
+    E = len(edges)
+    up = torch.from_numpy(np.concatenate([edges[order].reshape(-1), local[order], np.zeros(1, np.int32)])).to(device)
+    table = torch.from_numpy(values.astype(np.uint8)).to(device)
+    status = torch.empty((n_rc * n_fc, _lib_raster.FILL_STATUS), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        for i in range(n_rc):
+            rows = min(rc, R - i * rc)
+            for j in range(n_fc):
+                nf = min(fc, N - j * fc)
+                a, b = int(starts[i * n_fc + j]), int(starts[i * n_fc + j + 1])
+                nbytes = lib.xmem_polygons_fill_workspace_bytes(nf, H, W, rows)
+                ws = workspace(max(nbytes, 8), device, 'polygons_fill')
+                FILL_STATS['launches'] += 1
+                _lib.check(lib.xmem_polygons_fill(C.c_void_p(up.data_ptr() + 16 * a), C.c_void_p(up.data_ptr() + 16 * E + 4 * a), b - a, nf, H, W,
+                                                  rows, frac_bits, C.c_void_p(table.data_ptr() + i * rc), int(bool(overlay) or i > 0),
+                                                  C.c_void_p(out.data_ptr() + j * fc * H * W), C.c_void_p(status.data_ptr() + 8 * (i * n_fc + j)),
+                                                  ptr(ws), ws.numel(), stream_ptr()))
+    status = status[0] if len(status) == 1 else status.sum(0, dtype=torch.int32)
+    if not check:
+        return out, status
+    bad = status.cpu().tolist()
+    if any(bad):
+        raise ValueError(f'fill_polygons: {bad[0]} edges name a plane outside the {N} x {R} there are, {bad[1]} have a coordinate beyond '
+                         f'{_lib_raster.COORD_BOUND} / 2^{frac_bits} pixels; they were skipped')
+    return out
+
+
+def fill_polygons(frames, H, W, values=None, frac_bits=8, out=None, overlay=False, check=True):
+    """Polygons -> uint8 index maps [N,H,W] on the device, `polygons.fill_rows_host` per frame, byte for byte.  `frames`: a list of N
+    frames, each a list of rows, each a list of rings ((x, y) lists or flat lists, ints or floats); R is the longest frame's number
+    of rows.  A row is filled even-odd on its own; a pixel takes values[row] (default row + 1) of the highest row that contains it,
+    else 0 - or, with overlay=True, what `out` held.  The host packs the edges (`polygons.pack_edges`, work per vertex), uploads them
+    once and launches; more than 254 rows, or more bit-planes than `FILL_WORKSPACE_CAP` bytes, go in chunks (`fill_edges`).
+    check=True reads the status (one synchronisation) and raises if an edge was skipped; check=False returns (masks, status int32 [2]
+    on the device) without synchronising."""
+    from . import polygons
+    frames = list(frames)
+    if not frames:
+        raise ValueError('fill_polygons: no frames')
+    R = max(1, max(len(rows) for rows in frames))
+    edges, plane = polygons.pack_edges(frames, R, frac_bits)
+    return fill_edges(edges, plane, len(frames), H, W, R, values=values, frac_bits=frac_bits, out=out, overlay=overlay, check=check)

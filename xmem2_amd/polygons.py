@@ -182,6 +182,98 @@ def fill_host(rings, H, W):
     return (np.cumsum(cross, axis=1)[:, :W] & 1).astype(bool)
 
 
+# ---- the exact fill: fixed point, integer arithmetic (csrc/polygons_fill.hip is held to it bit for bit) ---------------------------
+#
+# Vertices are moved to the grid of 1 / 2**frac_bits pixel first (`quantise`); everything after that is integer.  one = 2**frac_bits.
+# An edge, normalised to ya < yb (horizontal edges take no part), crosses image row r when 2 ya <= (2 r + 1) one < 2 yb - half open,
+# so a vertex that lies exactly on a centre line counts once - and toggles the first column whose centre is at or right of it:
+# c = ceil(num / den), num = 2 xa dy + ((2 r + 1) one - 2 ya) dx - one dy, den = 2 one dy, clipped to [0, W].  A pixel is inside when
+# the running parity of the toggles along its row is odd.  With |v| one <= 2^28 every product stays below 2^62.
+MAX_FRAC_BITS = 8
+COORD_BOUND = 1 << 28        # of a quantised coordinate's magnitude
+
+
+def _frac_bits(frac_bits):
+    if isinstance(frac_bits, (bool, np.bool_)) or not isinstance(frac_bits, (int, np.integer)) or not 0 <= frac_bits <= MAX_FRAC_BITS:
+        raise ValueError(f'frac_bits = {frac_bits!r} must be an integer in 0..{MAX_FRAC_BITS}')
+    return int(frac_bits)
+
+
+def quantise(v, frac_bits=8):
+    """np.rint(v * 2**frac_bits) as int64.  Refuses non-finite values and |v| * 2**frac_bits > 2^28."""
+    one = 1 << _frac_bits(frac_bits)
+    v = np.asarray(v, np.float64)
+    if not np.isfinite(v).all():
+        raise ValueError('quantise: a coordinate is not finite')
+    if v.size and np.abs(v).max() * one > COORD_BOUND:
+        raise ValueError(f'quantise: a coordinate exceeds 2^28 / 2^{frac_bits} pixels')
+    return np.rint(v * one).astype(np.int64)
+
+
+def _ring_edges(ring, frac_bits):
+    """int64 [n, 4] = xa, ya, xb, yb with ya < yb of a ring's edges (its last vertex joins its first), horizontal ones dropped"""
+    p = quantise(np.asarray(ring, np.float64).reshape(-1, 2), frac_bits)
+    q = np.roll(p, -1, axis=0)
+    up = p[:, 1] > q[:, 1]
+    e = np.where(up[:, None], np.concatenate([q, p], 1), np.concatenate([p, q], 1))
+    return e[e[:, 1] != e[:, 3]]
+
+
+def _ceil_div(a, b):
+    return -((-a) // b)
+
+
+def fill_exact_host(rings, H, W, frac_bits=8):
+    """Even-odd fill of rings (lists of (x, y) or flat lists, ints or floats) -> bool [H,W] by the integer rule above.  Rings with
+    fewer than 3 vertices, repeated vertices, self-intersections and vertices outside the plane are all taken as they come."""
+    one = 1 << _frac_bits(frac_bits)
+    H, W = int(H), int(W)
+    parts = [_ring_edges(r, frac_bits) for r in rings if len(r)]
+    e = np.concatenate(parts) if parts else np.zeros((0, 4), np.int64)
+    xa, ya, xb, yb = e.T
+    r0 = np.clip(_ceil_div(2 * ya - one, 2 * one), 0, H)             # the rows are clipped here, none outside the plane is walked
+    r1 = np.clip(_ceil_div(2 * yb - one, 2 * one), 0, H)
+    n = np.maximum(r1 - r0, 0)
+    at = np.repeat(np.arange(len(e)), n)                             # one entry per crossing
+    r = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n) + r0[at]
+    dx, dy = (xb - xa)[at], (yb - ya)[at]
+    num = 2 * xa[at] * dy + ((2 * r + 1) * one - 2 * ya[at]) * dx - one * dy
+    c = np.clip(_ceil_div(num, 2 * one * dy), 0, W)
+    cross = np.bincount(r * (W + 1) + c, minlength=H * (W + 1)).reshape(H, W + 1)
+    return (np.cumsum(cross, axis=1)[:, :W] & 1).astype(bool)
+
+
+def fill_rows_host(rows, H, W, values=None, frac_bits=8, base=None):
+    """uint8 [H,W] from a list of ring lists: row i is filled even-odd on its own, a pixel takes values[i] (default i + 1) of the
+    highest row that contains it, else `base`'s value, or 0 - `rle.decode`'s overlap rule.  A union of polygons (COCO, labelme:
+    several polygons for one object) is one row per polygon with equal values."""
+    values = list(range(1, len(rows) + 1)) if values is None else [int(v) for v in values]
+    if len(values) != len(rows) or any(not 0 <= v <= 255 for v in values):
+        raise ValueError(f'fill_rows_host: values must be {len(rows)} integers in 0..255')
+    out = np.zeros((H, W), np.uint8) if base is None else np.array(base, np.uint8).reshape(H, W)
+    for rings, v in zip(rows, values):
+        out[fill_exact_host(rings, H, W, frac_bits)] = v
+    return out
+
+
+def pack_edges(frames, R, frac_bits=8):
+    """(edges int32 [E, 4] = xa, ya, xb, yb with ya < yb, plane int32 [E] = frame * R + row) of `frames`: a list of frames, each a
+    list of at most R rows, each a list of rings - what `ops.fill_polygons` uploads.  Work per vertex, vectorised per ring."""
+    edges, plane = [], []
+    for f, rows in enumerate(frames):
+        if len(rows) > R:
+            raise ValueError(f'pack_edges: frame {f} has {len(rows)} rows, R = {R}')
+        for i, rings in enumerate(rows):
+            for ring in rings:
+                if len(ring):
+                    e = _ring_edges(ring, frac_bits)
+                    edges.append(e)
+                    plane.append(np.full(len(e), f * R + i, np.int32))
+    if not edges:
+        return np.zeros((0, 4), np.int32), np.zeros(0, np.int32)
+    return np.concatenate(edges).astype(np.int32), np.concatenate(plane)
+
+
 def _segment_distance(p, a, b):
     p, a, b = (np.asarray(v, np.float64) for v in (p, a, b))
     ab = b - a
@@ -259,3 +351,78 @@ def parse_polygons(spec):
         raise ValueError(f'tracks_polygons: tolerance = {t!r} must be None or a finite number >= 0')
     t = float(t)
     return {'tolerance': int(t) if t == int(t) else t}
+
+
+def from_labelme(paths_or_dir, file_names=None):
+    """labelme's per-frame JSON files -> a polygon-only tracks document (xmem2_amd/rle.py reads it: `TrackReader`).  Each file holds
+    `imageHeight`, `imageWidth` and `shapes`: [{label, points [[x, y], ..], shape_type, group_id}], and is named like its frame.
+    `paths_or_dir`: a directory (its *.json, sorted) or a list of files; `file_names`: the video's frames - a frame without a file
+    gets null entries - default: the annotated frames themselves.  A label that parses as an integer in 1..255 keeps its value; the
+    other names get, in sorted order, the smallest values no numeric label took (1..n when there is none) and are recorded in the
+    video entry as `label_names`.  One track per label, ordered by value; the polygons of a label in a frame are the entry's rings,
+    filled each on its own (`"fill": "union"`).  A shape that is no polygon raises ValueError."""
+    import json
+    import os
+    if isinstance(paths_or_dir, (str, os.PathLike)):
+        folder = str(paths_or_dir)
+        paths = [os.path.join(folder, n) for n in sorted(os.listdir(folder)) if n.endswith('.json')]
+    else:
+        paths = [str(p) for p in paths_or_dir]
+    if not paths:
+        raise ValueError('from_labelme: no annotation files')
+    stem = lambda p: os.path.splitext(os.path.basename(p))[0]
+    frames, size = {}, None
+    for path in paths:
+        with open(path) as f:
+            doc = json.load(f)
+        hw = (int(doc['imageHeight']), int(doc['imageWidth']))
+        if size is not None and hw != size:
+            raise ValueError(f'from_labelme: {path} is {hw}, the files before it {size}')
+        size = hw
+        shapes = []
+        for i, shape in enumerate(doc['shapes']):
+            kind = shape.get('shape_type', 'polygon')
+            if kind != 'polygon':
+                raise ValueError(f'from_labelme: {path}, shape {i} ({shape.get("label")!r}) is a {kind!r}, only polygons are read')
+            pts = np.asarray(shape['points'], np.float64)
+            if pts.ndim != 2 or pts.shape[1] != 2 or not np.isfinite(pts).all():
+                raise ValueError(f'from_labelme: {path}, shape {i} ({shape.get("label")!r}): points must be finite [x, y] pairs')
+            shapes.append((str(shape['label']), pts.reshape(-1).tolist()))
+        if stem(path) in frames:
+            raise ValueError(f'from_labelme: two files are named {stem(path)!r}')
+        frames[stem(path)] = shapes
+    if file_names is None:
+        file_names = [stem(p) for p in paths]
+    file_names = [str(n) for n in file_names]
+    stems = [os.path.splitext(n)[0] for n in file_names]
+    stray = sorted(set(frames) - set(stems))
+    if stray:
+        raise ValueError(f'from_labelme: no frame is named like {stray}')
+
+    def numeric(label):
+        try:
+            return int(label) if 1 <= int(label) <= 255 and str(int(label)) == label.strip() else None
+        except ValueError:
+            return None
+    labels = sorted({label for shapes in frames.values() for label, _ in shapes})
+    value = {label: numeric(label) for label in labels if numeric(label) is not None}
+    free = (v for v in range(1, 256) if v not in set(value.values()))
+    names = {}
+    for label in labels:
+        if label not in value:
+            value[label] = next(free, None)
+            if value[label] is None:
+                raise ValueError('from_labelme: more labels than the 255 values of an index mask')
+            names[str(value[label])] = label
+    anns = []
+    for n, label in enumerate(sorted(value, key=value.get), start=1):
+        seg = []
+        for s in stems:
+            rings = [pts for lab, pts in frames.get(s, []) if lab == label]
+            seg.append({'size': list(size), 'polygons': rings} if rings else None)
+        anns.append({'id': n, 'video_id': 1, 'category_id': 1, 'label': value[label], 'segmentations': seg,
+                     'bboxes': [None] * len(stems), 'areas': [None] * len(stems)})
+    video = {'id': 1, 'height': size[0], 'width': size[1], 'length': len(stems), 'file_names': file_names, 'polygons': {'fill': 'union'}}
+    if names:
+        video['label_names'] = names
+    return {'videos': [video], 'categories': [{'id': 1, 'name': 'object'}], 'annotations': anns}

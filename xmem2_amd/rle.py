@@ -219,6 +219,7 @@ def record_host(mask, k):
 
 
 COUNT_FORMS = ('list', 'compressed')            # config['tracks_counts']
+FILL_RULES = ('evenodd', 'union')               # the video entry's polygons.fill: an entry's rings filled together, or each on its own
 
 
 def check_count_form(counts):
@@ -339,6 +340,10 @@ def read_tracks(path):
         doc = json.load(f)
     if len(doc.get('videos', [])) != 1:
         raise ValueError('read_tracks: expected one video per file')
+    if any(seg is not None and 'counts' not in seg and 'polygons' in seg
+           for ann in doc['annotations'] for seg in ann['segmentations']):       # polygon-only entries: the reader that knows them
+        reader = TrackReader(doc)
+        return reader.video, [reader.mask_host(t) for t in range(len(reader))]
     video = doc['videos'][0]
     h, w, T = int(video['height']), int(video['width']), int(video['length'])
     masks = [None] * T
@@ -365,7 +370,12 @@ class TrackReader:
     `mask_host(t)` decodes a frame on the host (few frames: annotations); `masks_device` builds packed records from the counts - work
     per event, never per pixel - and decodes them with `ops.rle_decode`.  Counts may be lists or compressed strings, also mixed in one
     file: a frame whose entries are all strings goes up as bytes and becomes its record on the device (`ops.rle_decompress`), the host
-    doing nothing per character; `mask_host` and `record` read a string with `decompress_counts`."""
+    doing nothing per character; `mask_host` and `record` read a string with `decompress_counts`.
+    An entry may hold `polygons` without `counts` (a polygon-only entry: hand-drawn annotations, `polygons.from_labelme`; its `size`
+    is optional, `bboxes` / `areas` may be null).  The video entry's `polygons.fill` names the rule: 'evenodd' (default: an entry's
+    rings filled together, holes are rings) or 'union' (every ring on its own).  `mask_host` fills such a frame with
+    `polygons.fill_rows_host`, `masks_device` with `ops.fill_polygons`; it has no `record`.  An entry with both keys is read from
+    its counts.  A frame that mixes polygon-only entries with counts entries raises ValueError when it is read."""
 
     def __init__(self, path_or_doc):
         if isinstance(path_or_doc, dict):
@@ -380,21 +390,33 @@ class TrackReader:
         self.file_names = [str(n) for n in self.video.get('file_names', [])]
         h, w, T = self.height, self.width, self.length
         self.labels, self._segs = [], []                             # per annotation: its label, {frame index: counts}
+        self._polys = []                                             # per annotation: {frame index: rings} of its polygon-only entries
+        self.fill = (self.video.get('polygons') or {}).get('fill', 'evenodd')
+        if self.fill not in FILL_RULES:
+            raise ValueError(f'read_tracks: polygons.fill = {self.fill!r}, known: {FILL_RULES}')
         for ann in doc['annotations']:
             lab = int(ann['label'])
             if not (1 <= lab <= 255):
                 raise ValueError(f'read_tracks: label {lab} does not fit an index PNG')
-            if not (len(ann['segmentations']) == len(ann['bboxes']) == len(ann['areas']) == T):
+            per_frame = [ann['segmentations']] + [v for v in (ann.get('bboxes'), ann.get('areas')) if v is not None]
+            polygon_only = [seg is not None and 'counts' not in seg and 'polygons' in seg for seg in ann['segmentations']]
+            if any(len(v) != T for v in per_frame) or (len(per_frame) != 3 and not any(polygon_only)):
                 raise ValueError(f'read_tracks: track {ann["id"]} does not have one entry per frame')
-            segs = {}
+            segs, polys = {}, {}
             for t, seg in enumerate(ann['segmentations']):
                 if seg is None:
                     continue
-                if list(seg['size']) != [h, w]:
+                if ('size' in seg or not polygon_only[t]) and list(seg['size']) != [h, w]:
                     raise ValueError(f'read_tracks: track {ann["id"]}, frame {t}: size {seg["size"]} is not the video\'s {[h, w]}')
-                segs[t] = seg['counts']
+                if polygon_only[t]:                                  # an entry with both keys is read from its counts
+                    polys[t] = seg['polygons']
+                else:
+                    segs[t] = seg['counts']
             self.labels.append(lab)
             self._segs.append(segs)
+            self._polys.append(polys)
+        self._polygon_frames = {t for polys in self._polys for t in polys}
+        self._mixed = {t for t in self._polygon_frames if any(t in segs for segs in self._segs)}      # refused when they are read
         self._index = {}
         for t, name in enumerate(self.file_names):
             self._index.setdefault(os.path.splitext(name)[0], t)
@@ -411,7 +433,31 @@ class TrackReader:
     def has_mask(self, t):
         """True when any track has an entry for frame t."""
         t = self._frame(t)
-        return any(t in segs for segs in self._segs)
+        return t in self._polygon_frames or any(t in segs for segs in self._segs)
+
+    def has_polygons(self, t=None):
+        """True when frame t - without t: any frame - is read from polygon-only entries."""
+        return bool(self._polygon_frames) if t is None else self._frame(t) in self._polygon_frames
+
+    def _unmixed(self, t):
+        if t in self._mixed:
+            raise ValueError(f'TrackReader: frame {t} mixes polygon-only entries with counts entries; the two forms are not layered')
+        return t
+
+    def polygon_rows(self, t):
+        """(rows, values) of a polygon frame for `polygons.fill_rows_host` / `ops.fill_polygons`: under 'evenodd' one row per
+        annotation (its rings filled together, holes being rings), under 'union' one row per ring, each filled on its own; `values`
+        holds every row's annotation (0-based), so a later annotation wins where tracks overlap, as with counts."""
+        t = self._unmixed(self._frame(t))
+        rows, owner = [], []
+        for a, polys in enumerate(self._polys):
+            rings = polys.get(t)
+            if rings is None:
+                continue
+            for row in ([[r] for r in rings] if self.fill == 'union' else [rings]):
+                rows.append(row)
+                owner.append(a)
+        return rows, owner
 
     def frame_index(self, name_or_stem):
         """The index of the frame whose file name, or file name without extension, is given; None when there is none."""
@@ -422,7 +468,11 @@ class TrackReader:
 
     def mask_host(self, t):
         """uint8 [H, W] holding the annotations' labels, as `read_tracks` gives it; None for a frame without any entry."""
-        t = self._frame(t)
+        t = self._unmixed(self._frame(t))
+        if t in self._polygon_frames:
+            from .polygons import fill_rows_host
+            rows, owner = self.polygon_rows(t)
+            return fill_rows_host(rows, self.height, self.width, values=[self.labels[a] for a in owner])
         mask = None
         for lab, segs in zip(self.labels, self._segs):
             if t in segs:
@@ -434,7 +484,9 @@ class TrackReader:
     def record(self, t):
         """(meta int32 [n, META], packed uint32 events) of frame t with one row per annotation, in the layout `ops.rle_encode`
         writes; of `meta` only field 0, the number of events, is filled."""
-        t = self._frame(t)
+        t = self._unmixed(self._frame(t))
+        if t in self._polygon_frames:
+            raise ValueError(f'TrackReader: frame {t} holds polygons, not counts: it has no record (`masks_device` fills it)')
         meta = np.zeros((len(self.labels), META), np.int32)
         ev = []
         for a, segs in enumerate(self._segs):
@@ -447,12 +499,19 @@ class TrackReader:
 
     def masks_device(self, frames=None, device=None, values='label', batch=32):
         """(uint8 [n, H, W] on the device, present bool [n]) of `frames` (default: all), decoded in launches of `batch` frames.
-        values='label': the annotations' labels; 'dense': 1..n in file order.  A frame without any entry is all zero, not present."""
+        values='label': the annotations' labels; 'dense': 1..n in file order; or a list of one value in 0..255 per annotation.  A
+        frame without any entry is all zero, not present.  Frames of polygon-only entries are filled by `ops.fill_polygons`."""
         import torch
         from . import ops
-        if values not in ('label', 'dense'):
-            raise ValueError(f"values must be 'label' or 'dense', got {values!r}")
-        frames = list(range(self.length)) if frames is None else [self._frame(t) for t in frames]
+        if isinstance(values, str):
+            if values not in ('label', 'dense'):
+                raise ValueError(f"values must be 'label', 'dense' or a list of one value per track, got {values!r}")
+            per_track = list(self.labels) if values == 'label' else list(range(1, len(self.labels) + 1))
+        else:
+            per_track = [int(v) for v in values]
+            if len(per_track) != len(self.labels) or any(not 0 <= v <= 255 for v in per_track):
+                raise ValueError(f'values must be {len(self.labels)} integers in 0..255')
+        frames = [self._unmixed(self._frame(t)) for t in (range(self.length) if frames is None else frames)]
         n_rows = len(self.labels)
         if n_rows > 254:
             raise ValueError(f'masks_device: {n_rows} tracks, at most 254 fit a launch')
@@ -463,18 +522,20 @@ class TrackReader:
         out = torch.zeros((len(frames), self.height, self.width), dtype=torch.uint8, device=device)
         if n_rows == 0 or not frames:
             return out, present
-        table = torch.tensor(self.labels, dtype=torch.uint8, device=device) if values == 'label' else None
+        table = None if values == 'dense' else torch.tensor(per_track, dtype=torch.uint8, device=device)
         step = max(1, int(batch))
         with torch.cuda.device(device):
             for i in range(0, len(frames), step):
                 chunk, dst = frames[i:i + step], out[i:i + step]
                 comp = [j for j, t in enumerate(chunk) if self._all_compressed(t)]
-                plain = [j for j in range(len(chunk)) if j not in set(comp)]
-                for idx, decode_group in ((plain, self._decode_lists), (comp, self._decode_strings)):
+                poly = [j for j, t in enumerate(chunk) if t in self._polygon_frames]
+                plain = [j for j in range(len(chunk)) if j not in set(comp) | set(poly)]
+                groups = ((plain, self._decode_lists, table), (comp, self._decode_strings, table), (poly, self._fill_polygons, per_track))
+                for idx, decode_group, row_values in groups:
                     if not idx:
                         continue
                     whole = len(idx) == len(chunk)
-                    got = decode_group([chunk[j] for j in idx], table, dst if whole else None)
+                    got = decode_group([chunk[j] for j in idx], row_values, dst if whole else None)
                     if not whole:                                    # a batch that mixes both forms: each group lands in its frames
                         dst[torch.tensor(idx, device=device)] = got
         return out, present
@@ -503,6 +564,19 @@ class TrackReader:
         capacity = record.numel() // len(frames) - n_rows * META
         return ops.rle_decode(record, self.height, self.width, n_rows, capacity, values=table, out=out)
 
+    def _fill_polygons(self, frames, per_track, out):
+        """One `ops.fill_polygons` for the frames: every annotation owns a fixed run of rows - one under 'evenodd', under 'union' as
+        many as its longest ring list among these frames -, so one values table serves all of them; the host packs per vertex."""
+        from . import ops
+        union = self.fill == 'union'
+        per = [[[] if polys.get(t) is None else [[r] for r in polys[t]] if union else [polys[t]] for t in frames] for polys in self._polys]
+        width = [max(len(rows) for rows in of_track) for of_track in per]
+        if not any(width):
+            width[0] = 1
+        batch = [[row for of_track, n in zip(per, width) for row in of_track[j] + [[]] * (n - len(of_track[j]))] for j in range(len(frames))]
+        values = [v for v, n in zip(per_track, width) for _ in range(n)]
+        return ops.fill_polygons(batch, self.height, self.width, values=values, out=out)
+
 
 # what `ops.rle_decompress` says about a row (include/xmem_hip.h, xmem_rle_decompress)
 STRING_STATUS = {1: 'the compressed counts are malformed', 2: 'the counts do not describe a plane of the video\'s size',
@@ -516,7 +590,7 @@ def recode_tracks(doc, counts):
     doc = json.loads(json.dumps(doc))                                # a deep copy that keeps the order of the keys
     for ann in doc.get('annotations', []):
         for seg in ann.get('segmentations', []):
-            if seg is None:
+            if seg is None or 'counts' not in seg:                   # a polygon-only entry has nothing to recode
                 continue
             have = seg['counts']
             if counts == 'compressed' and not is_compressed(have):
@@ -621,13 +695,107 @@ def polygon_tracks(tracks, spec=True, batch=32):
     return doc
 
 
+def _load_doc(tracks):
+    if isinstance(tracks, dict):
+        return json.loads(json.dumps(tracks))                        # a deep copy that keeps the order of the keys
+    with open(tracks) as f:
+        return json.load(f)
+
+
+def verify_polygons(tracks, batch=32):
+    """Do the `polygons` of a tracks file (or parsed document) describe its `counts`?  For the entries that have both keys, per
+    batch: the polygons are filled (`ops.fill_polygons`, one dense id per track, by the file's fill rule) and the counts decoded
+    (`TrackReader.masks_device`), both on the device, and scored with the J&F count kernel (`ops.jf_counts`); only the counts table
+    reaches the host.  Returns {'tolerance': what the file says, 'tracks': [{'id', 'label', 'frames', 'differ', 'min_iou',
+    'mean_iou'}], 'frames': compared, 'differ': frames in which any track differs}: the measurement of what a tolerance costs.
+    Both sides are label maps, so where two tracks overlap the later one owns the pixels on either side."""
+    import torch
+    from . import ops
+    doc = _load_doc(tracks)
+    reader = TrackReader(doc)
+    anns, k, step = doc['annotations'], len(reader.labels), max(1, int(batch))
+    if k > 254:
+        raise ValueError(f'verify_polygons: {k} tracks, at most 254 fit a launch')
+    union = reader.fill == 'union'
+    both = [[t for t, seg in enumerate(ann['segmentations']) if seg is not None and 'counts' in seg and 'polygons' in seg] for ann in anns]
+    todo = sorted({t for ts in both for t in ts})
+    ious = [[] for _ in anns]
+    bad_frames = set()
+    for i in range(0, len(todo), step):
+        frames = todo[i:i + step]
+        want, _ = reader.masks_device(frames, values='dense', batch=step)
+        per = [[[] if t not in both[a] else [[r] for r in ann['segmentations'][t]['polygons']] if union else [ann['segmentations'][t]['polygons']]
+                for t in frames] for a, ann in enumerate(anns)]
+        width = [max(1, max(len(rows) for rows in of_track)) for of_track in per]
+        rows = [[row for of_track, n in zip(per, width) for row in of_track[j] + [[]] * (n - len(of_track[j]))] for j in range(len(frames))]
+        got = ops.fill_polygons(rows, reader.height, reader.width, values=[a + 1 for a, n in enumerate(width) for _ in range(n)])
+        counts = ops.jf_counts(want, got, 0)[:, 1:k + 1, :3].cpu().numpy().astype(np.int64)      # gt_area, pred_area, inter
+        for j, t in enumerate(frames):
+            for a in range(k):
+                if t in both[a]:
+                    g, p, n = (int(v) for v in counts[j, a])
+                    ious[a].append(1.0 if g + p - n == 0 else n / (g + p - n))
+                    if not (g == p == n):
+                        bad_frames.add(t)
+    tracks_out = []
+    for ann, lab, v in zip(anns, reader.labels, ious):
+        tracks_out.append({'id': ann.get('id'), 'label': lab, 'frames': len(v), 'differ': sum(x < 1.0 for x in v),
+                           'min_iou': min(v) if v else None, 'mean_iou': float(np.mean(v)) if v else None})
+    tolerance = (doc['videos'][0].get('polygons') or {}).get('tolerance')
+    return {'tolerance': tolerance, 'fill': reader.fill, 'tracks': tracks_out, 'frames': len(todo), 'differ': len(bad_frames)}
+
+
+def counts_from_polygons(tracks, batch=32):
+    """A tracks file (or parsed document) with `counts` (lists), `size`, `bboxes` and `areas` written for every polygon-only entry ->
+    document.  Per batch: `TrackReader.masks_device` (dense ids; the polygon frames are filled by `ops.fill_polygons`) ->
+    `ops.rle_encode`; no mask plane reaches the host.  The `polygons` key and everything else is kept.  The frames are label maps, so
+    where two tracks overlap the later one owns the pixels."""
+    from . import ops
+    doc = _load_doc(tracks)
+    reader = TrackReader(doc)
+    if len(set(reader.labels)) != len(reader.labels):
+        raise ValueError('counts_from_polygons: two tracks share a label')
+    h, w, k, step = reader.height, reader.width, len(reader.labels), max(1, int(batch))
+    todo = [t for t in range(len(reader)) if reader.has_polygons(t)]
+    for ann in doc['annotations']:
+        for key in ('bboxes', 'areas'):
+            if ann.get(key) is None:
+                ann[key] = [None] * len(reader)
+    for i in range(0, len(todo), step):
+        frames = todo[i:i + step]
+        dense, _ = reader.masks_device(frames, values='dense', batch=step)
+        meta, events = ops.rle_encode(dense, k)
+        for j, t in enumerate(frames):
+            for ann, row, ev in zip(doc['annotations'], meta[j], label_events(meta[j], events[j])):
+                seg = ann['segmentations'][t]
+                if seg is None:
+                    continue
+                x0, y0, x1, y1 = (int(v) for v in row[2:6])
+                ann['segmentations'][t] = dict({'size': [h, w], 'counts': counts_from_events(ev, h, w)},
+                                               **{key: v for key, v in seg.items() if key not in ('size', 'counts')})
+                ann['bboxes'][t] = [x0, y0, x1 - x0 + 1, y1 - y0 + 1] if int(row[1]) else [0, 0, 0, 0]
+                ann['areas'][t] = int(row[1])
+    return doc
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle',
                                  description='tracks.json -> index PNGs (one per frame), or - with --recode, --clean and / or --polygons - '
                                              'tracks.json with its counts in the other form, its masks cleaned on the device and / or '
                                              'their polygon outlines added')
-    ap.add_argument('--tracks', required=True, help='the tracks.json of one video (counts as lists, compressed strings, or both)')
-    ap.add_argument('--out', required=True, help='directory the PNGs are written to; with --recode, --clean or --polygons the file that is written')
+    ap.add_argument('--tracks', default=None, help='the tracks.json of one video (counts as lists, compressed strings, or both; '
+                                                   'entries may hold polygons alone)')
+    ap.add_argument('--out', default=None, help='directory the PNGs are written to; with --recode, --clean, --polygons, --from-polygons '
+                                                'or --from-labelme the file that is written')
+    ap.add_argument('--verify-polygons', action='store_true',
+                    help='write nothing: fill the polygons of every entry that has both keys and compare them with its counts, on the '
+                         'device (needs the GPU); prints per track the minimum and mean IoU and the frames that differ, exit status 1 '
+                         'when the file says tolerance 0 and a frame differs')
+    ap.add_argument('--from-polygons', action='store_true',
+                    help='write no PNGs: rewrite the file with counts, boxes and areas for every polygon-only entry, filled and encoded '
+                         'on the device (needs the GPU); the count form is a list unless --recode names one')
+    ap.add_argument('--from-labelme', default=None, metavar='DIR',
+                    help='in place of --tracks: a directory of labelme per-frame JSON files; writes the polygon-only tracks file --out')
     ap.add_argument('--recode', default=None, choices=COUNT_FORMS,
                     help='write no PNGs: rewrite the file with every counts entry as a list or as the compressed COCO string')
     ap.add_argument('--clean', default=None, metavar='JSON',
@@ -641,6 +809,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.polygons is not None and not (0 <= args.polygons < float('inf')):
         ap.error('--polygons: the tolerance must be a finite number >= 0')
+    if (args.tracks is None) == (args.from_labelme is None):
+        ap.error('exactly one of --tracks and --from-labelme is needed')
+    if args.out is None and not args.verify_polygons:
+        ap.error('--out is needed')
+    if args.from_labelme is not None and (args.verify_polygons or args.from_polygons or args.clean or args.recode or args.polygons is not None):
+        ap.error('--from-labelme writes the polygon-only file and nothing else: run the other steps on that file')
     if args.clean is not None:
         from .mask_cleanup import parse_cleanup
         try:
@@ -654,11 +828,28 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.recode is not None or args.clean is not None or args.polygons is not None:
+    if args.verify_polygons:
+        report = verify_polygons(args.tracks)
+        print(json.dumps(report))
+        return 1 if report['tolerance'] == 0 and report['differ'] else 0
+    if args.from_labelme is not None:
+        from .polygons import from_labelme
+        doc = from_labelme(args.from_labelme)
+        if os.path.dirname(args.out):
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        text = json.dumps(doc, separators=(',', ':'))
+        with open(args.out, 'w') as f:
+            f.write(text)
+        print(json.dumps({'frames': doc['videos'][0]['length'], 'tracks': len(doc['annotations']), 'bytes': len(text), 'out': args.out}))
+        return 0
+    if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons:
         report = {}
+        if args.from_polygons:                                       # first: what follows reads counts
+            doc = counts_from_polygons(args.tracks)
+            report['from_polygons'] = True
         if args.clean is not None:
-            doc, report['clean'] = clean_tracks(args.tracks, args.clean)
-        else:
+            doc, report['clean'] = clean_tracks(doc if args.from_polygons else args.tracks, args.clean)
+        elif not args.from_polygons:
             with open(args.tracks) as f:
                 doc = json.load(f)
         if args.polygons is not None:                                # of the cleaned masks, when both are asked for

@@ -562,6 +562,10 @@ class VideoSession:
         with torch.cuda.device(self.device):
             for i in range(0, len(present), step):
                 chunk = present[i:i + step]
+                if any(reader.has_polygons(t) for t in chunk):                     # polygon-only entries: filled, not decoded
+                    got, _ = reader.masks_device(chunk, device=self.device, values=dense.tolist(), batch=step)
+                    self.masks[torch.tensor(chunk, device=self.device)] = got
+                    continue
                 records = [reader.record(t) for t in chunk]
                 record = (np.stack([m for m, _ in records]), [e for _, e in records])
                 if chunk == list(range(chunk[0], chunk[-1] + 1)):                  # straight into the arena
