@@ -235,25 +235,32 @@ int xmem_augment_frames(const uint8_t* img, const float* mask, int H, int W, int
 /* ------------------------------------------------------------------------------------------
  * Pooling / resampling / gating kernels of the encoders and the decoder.
  * ------------------------------------------------------------------------------------------ */
-/* nn.MaxPool2d(3, stride 2, pad 1), model/resnet.py:123; in [B][H][W][C] -> out [B][Ho][Wo][C] */
+/* nn.MaxPool2d(3, stride 2, pad 1), model/resnet.py:123; in [B][H][W][C] -> out [B][Ho][Wo][C], Ho = (H - 1) / 2 + 1 (the padding is
+ * -inf).  Exact.  Refused with XMEM_ERR_UNSUPPORTED before any GPU work: C % 4 != 0, `in` or `out` off 16 bytes (8 for a half tensor). */
 int xmem_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, void* stream);
 
 /* F.interpolate(scale 2, bilinear, align_corners=False) of g [B][h][w][C] plus the broadcast skip
- * feature [2h][2w][C]: UpsampleBlock, model/modules.py:186-190 + group_modules.py:15-23 */
+ * feature [2h][2w][C] (ONE image, shared by all B): UpsampleBlock, model/modules.py:186-190 + group_modules.py:15-23.
+ * Refused with XMEM_ERR_UNSUPPORTED before any GPU work: C % 4 != 0, `g`, `skip` or `out` off 16 bytes (8 for half tensors). */
 int xmem_upsample2x_add(const float* g, const float* skip, float* out, int B, int h, int w, int C, void* stream);
 
 /* F.interpolate(mode='area') by an integer ratio r (2 or 4), group_modules.py:22-23;
- * in [B][H][W][C] (pixel stride ldin) -> out [B][H/r][W/r][C] (pixel stride ldout) */
+ * in [B][H][W][C] (pixel stride ldin) -> out [B][H/r][W/r][C] (pixel stride ldout); any r >= 1, any C, scalar accesses (no alignment
+ * beyond the element's).  Refused with XMEM_ERR_UNSUPPORTED before any GPU work: H % r != 0 or W % r != 0. */
 int xmem_area_downsample(const float* in, int ldin, float* out, int ldout, int B, int H, int W, int C, int r, void* stream);
 
 /* dst[b][p][dst_off + c] = src[(b % srcB)][p][src_off + c]: builds the channel concatenations of
- * MainToGroupDistributor (group_modules.py:55-82) and torch.cat([g, h], 2) (modules.py:59,89). */
+ * MainToGroupDistributor (group_modules.py:55-82) and torch.cat([g, h], 2) (modules.py:59,89).  Pass the addresses of the first source
+ * and destination channel; a half destination is rounded once.  Refused with XMEM_ERR_UNSUPPORTED before any GPU work: C, ldsrc or
+ * lddst not a multiple of 4, `src` or `dst` off 16 bytes (8 for a half tensor). */
 int xmem_copy_channels(const float* src, int ldsrc, int srcB, float* dst, int lddst, int B, int P, int C, void* stream);
 
 /* The input of HiddenUpdater's three pointwise convolutions as one concatenated tensor, in one launch (model/modules.py:49-57:
  * g16_conv(g[0]) + g8_conv(downsample_groups(g[1], 1/2)) + g4_conv(downsample_groups(g[2], 1/4)), g[2] = cat(g4, logits)):
  * out [K][h][w][ldout] <- [ g16 [K][h][w][c16] | area2(g8 [K][2h][2w][c8]) | area4(g4 [K][4h][4w][c4]) | area4(logits [K][4h][4w][1]) ];
- * channels past c16 + c8 + c4 + 1 are not written.  Same bits as xmem_copy_channels + three xmem_area_downsample calls. */
+ * channels past c16 + c8 + c4 + 1 are not written.  Same bits as xmem_copy_channels + three xmem_area_downsample calls.
+ * Refused with XMEM_ERR_UNSUPPORTED before any GPU work: c16, c8, c4 or ldout not a multiple of 4, ldout < c16 + c8 + c4 + 1, a pointer
+ * off 16 bytes. */
 int xmem_hidden_update_gather(const float* g16, int c16, const float* g8, int c8, const float* g4, int c4, const float* logits,
                               float* out, int ldout, int K, int h, int w, void* stream);
 
@@ -270,7 +277,9 @@ int xmem_mask_head_gather(const float* g16, int c16, const float* g8, int c8, co
 /* CBAM (model/cbam.py:21-77) on g [B][P=H*W][C] and the residual add of FeatureFusionBlock
  * (modules.py:36-39): out = g + CBAM(g).  mlp weights as in the checkpoint: w1 [C/16][C], b1, w2 [C][C/16], b2;
  * spatial 7x7 conv weight sw [2][7][7] (channel 0 = max, 1 = mean), bias sb[1].
- * workspace: xmem_cbam_workspace_bytes(B, H*W, C). */
+ * workspace: xmem_cbam_workspace_bytes(B, H*W, C); nothing past those bytes is written.  Any H, W >= 1 (maps narrower than the gate
+ * included).  Refused before any GPU work: C % 16 != 0 or `g` / `out` off 16 bytes (8 for half tensors) -> XMEM_ERR_UNSUPPORTED; a
+ * workspace that is NULL or too small -> XMEM_ERR_WORKSPACE. */
 size_t xmem_cbam_workspace_bytes(int B, int P, int C);
 int xmem_cbam_residual(const float* g, float* out, int B, int H, int W, int C,
                        const float* w1, const float* b1, const float* w2, const float* b2,
@@ -286,7 +295,8 @@ int xmem_add3(const float* a, const float* b, const float* c, float* y, size_t n
 /* STORAGE-TYPED VARIANTS (the fp16 loop, config['precision'] = 'fp16': activations live in HBM as IEEE halfs, as the tensors of
  * the reference's autocast frame loop do, inference/run_on_video.py:76).  Same kernels, same fp32 arithmetic; `*_half` flags give
  * the storage type of each tensor (0 = float, 1 = half; leading dimensions count elements of that type); a stored value is
- * rounded once, to nearest even.  The plain functions above are the all-float instantiations.  The GRU state stays fp32. */
+ * rounded once, to nearest even.  The plain functions above are the all-float instantiations and refuse what these refuse.  The GRU
+ * state stays fp32. */
 int xmem_maxpool3x3s2_t(const void* in, int in_half, void* out, int out_half, int B, int H, int W, int C, void* stream);
 int xmem_upsample2x_add_t(const void* g, const void* skip, void* out, int half, int B, int h, int w, int C, void* stream);
 int xmem_area_downsample_t(const void* in, int in_half, int ldin, void* out, int out_half, int ldout, int B, int H, int W, int C, int r, void* stream);
@@ -326,14 +336,15 @@ int xmem_logits_to_prob(const float* logits, float* prob, float* prob_padded, in
 int xmem_aggregate_masks(const float* masks, float* prob, int K, int H, int W, void* stream);
 
 /* Given-mask / prediction merge of InferenceCore.step (inference/inference_core.py:117-127):
- * region = sum_k mask_k > 0.5; out_k = mask_k if bit k of valid_bits else (region ? 0 : pred_k).  [K][H][W] each. */
+ * region = sum_k mask_k > 0.5 (the fp32 sum, k ascending); out_k = mask_k if bit k of valid_bits else (region ? 0 : pred_k).
+ * [K][H][W] each, K <= 64. */
 int xmem_merge_masks(const float* pred_no_bg, const float* mask, uint64_t valid_bits, float* out, int K, int H, int W, void* stream);
 
 /* F.interpolate(prob, shape, mode='bilinear', align_corners=False) of _post_process (inference/run_on_video.py:166-168);
  * in [C][Hi][Wi] -> out [C][Ho][Wo] */
 int xmem_resize_bilinear(const float* in, float* out, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
 
-/* torch.argmax(prob, dim=0) -> uint8, inference/run_on_video.py:170-172; prob [C][H][W] */
+/* torch.argmax(prob, dim=0) -> uint8, inference/run_on_video.py:170-172; prob [C][H][W], C <= 255; the first maximal index. */
 int xmem_argmax_u8(const float* prob, uint8_t* out, int C, int H, int W, void* stream);
 
 /* One pass of a test-time ensemble (eval.py --size S [--flip] --save_scores + merge_multi_scale.py), at the ORIGINAL resolution H x W:

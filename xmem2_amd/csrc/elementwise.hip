@@ -75,7 +75,7 @@ __global__ void maxpool3x3s2_kernel(const TI* __restrict__ in, TO* __restrict__ 
 
 extern "C" int xmem_maxpool3x3s2_t(const void* in, int in_half, void* out, int out_half, int B, int H, int W, int C, void* stream) {
     if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0) return XMEM_ERR_BAD_ARG;
-    if (C % 4) return XMEM_ERR_UNSUPPORTED;
+    if (C % 4 || ((uintptr_t)in & (in_half ? 7 : 15)) || ((uintptr_t)out & (out_half ? 7 : 15))) return XMEM_ERR_UNSUPPORTED;
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t total = (size_t)B * Ho * Wo * (C / 4);
 #define F(TI, TO) hipLaunchKernelGGL((maxpool3x3s2_kernel<TI, TO>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const TI*)in, (TO*)out, B, H, W, C, Ho, Wo)
@@ -132,7 +132,7 @@ __global__ void upsample2x_add_kernel(const T* __restrict__ g, const T* __restri
 
 extern "C" int xmem_upsample2x_add_t(const void* g, const void* skip, void* out, int half, int B, int h, int w, int C, void* stream) {
     if (!g || !skip || !out || B <= 0 || h <= 0 || w <= 0 || C <= 0) return XMEM_ERR_BAD_ARG;
-    if (C % 4) return XMEM_ERR_UNSUPPORTED;
+    if (C % 4 || (((uintptr_t)g | (uintptr_t)skip | (uintptr_t)out) & (half ? 7 : 15))) return XMEM_ERR_UNSUPPORTED;
     const size_t total = (size_t)B * 4 * h * w * (C / 4);
     if (half) hipLaunchKernelGGL(upsample2x_add_kernel<_Float16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                                  (const _Float16*)g, (const _Float16*)skip, (_Float16*)out, B, h, w, C);
@@ -476,7 +476,7 @@ extern "C" int xmem_cbam_residual_t(const void* g, void* out, int half, int B, i
                                     const float* w1, const float* b1, const float* w2, const float* b2,
                                     const float* sw, const float* sb, void* workspace, size_t workspace_bytes, void* stream) {
     if (!g || !out || !w1 || !b1 || !w2 || !b2 || !sw || !sb || B <= 0 || H <= 0 || W <= 0 || C <= 0) return XMEM_ERR_BAD_ARG;
-    if (C % 16) return XMEM_ERR_UNSUPPORTED;
+    if (C % 16 || (((uintptr_t)g | (uintptr_t)out) & (half ? 7 : 15))) return XMEM_ERR_UNSUPPORTED;
     const int P = H * W, Cr = C / 16;
     if (!workspace || workspace_bytes < xmem_cbam_workspace_bytes(B, P, C)) return XMEM_ERR_WORKSPACE;
     char* ws = (char*)workspace;
