@@ -2032,3 +2032,70 @@ def fill_polygons(frames, H, W, values=None, frac_bits=8, out=None, overlay=Fals
     R = max(1, max(len(rows) for rows in frames))
     edges, plane = polygons.pack_edges(frames, R, frac_bits)
     return fill_edges(edges, plane, len(frames), H, W, R, values=values, frac_bits=frac_bits, out=out, overlay=overlay, check=check)
+
+
+# ---- signed distances, mattes, trimaps, grow / shrink (csrc/matte.hip, include/xmem_hip_matte.h): integer, bit-reproducible -------
+
+def _matte_labels(name, K, R):
+    from . import _lib_matte
+    for what, v, hi in (('K', K, _lib_matte.MAX_LABELS), ('R', R, _lib_matte.MAX_R)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f'{name}: {what} = {v!r} must be an integer in 1..{hi}')
+
+
+def signed_edt_sq(masks, K, R):
+    """`matte.signed_d2_host(m, k, R)` of every frame of the uint8 index maps `masks` [H,W] or [N,H,W] and every label k = 1..K on the
+    device -> int32 [K,H,W] or [N,K,H,W]: the squared distance to the nearest pixel on the other side of `m == k`, capped at
+    (R + 1)^2, positive inside the label; nothing exists outside the image.  Two launches on the current stream, no synchronisation."""
+    from . import _lib_matte
+    _matte_labels('signed_edt_sq', K, R)
+    masks, (N, H, W) = _index_maps(masks, 'signed_edt_sq')
+    lib = _lib_matte.load()
+    out = torch.empty((N, K, H, W) if masks.dim() == 3 else (K, H, W), dtype=torch.int32, device=masks.device)
+    nbytes = lib.xmem_signed_edt_workspace_bytes(N, H, W, K)
+    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    check(lib.xmem_signed_edt(ptr(masks), N, H, W, K, R, ptr(out), ptr(ws), ws.numel(), stream_ptr()))
+    return out
+
+
+def mask_mattes(masks, K, tables, R):
+    """Look-ups in that distance: `tables` uint8 [T, 2 (R + 1)^2 + 1] on the masks' device (`matte.feather_table`, `matte.trimap_table`,
+    T in 1..4) -> uint8 [T,K,H,W] or [T,N,K,H,W] = tables[t][s2 + (R + 1)^2].  One distance computation serves all T tables and no
+    int32 plane is written.  Two launches on the current stream, no synchronisation."""
+    from . import _lib_matte
+    _matte_labels('mask_mattes', K, R)
+    masks, (N, H, W) = _index_maps(masks, 'mask_mattes')
+    if not torch.is_tensor(tables) or tables.dtype != torch.uint8 or tables.dim() != 2 or tables.device != masks.device:
+        raise RuntimeError('mask_mattes: tables must be a uint8 tensor [T, 2 (R + 1)^2 + 1] on the masks\' device')
+    T, length = tables.shape
+    if not 1 <= T <= _lib_matte.MAX_TABLES or length != 2 * (R + 1) ** 2 + 1:
+        raise ValueError(f'mask_mattes: tables {tuple(tables.shape)}: expected 1..{_lib_matte.MAX_TABLES} rows of {2 * (R + 1) ** 2 + 1} for R = {R}')
+    tables = tables.contiguous()
+    lib = _lib_matte.load()
+    out = torch.empty((T, N, K, H, W) if masks.dim() == 3 else (T, K, H, W), dtype=torch.uint8, device=masks.device)
+    nbytes = lib.xmem_mask_matte_workspace_bytes(N, H, W, K)
+    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    check(lib.xmem_mask_matte(ptr(masks), N, H, W, K, R, ptr(tables), T, ptr(out), ptr(ws), ws.numel(), stream_ptr()))
+    return out
+
+
+def grow_masks(masks, r, out=None):
+    """`matte.grow_host(m, r)` of every frame of the uint8 index maps `masks` [H,W] or [N,H,W] on the device -> `out`, uint8 of that
+    shape (a tensor of the caller's that does not overlap `masks`, or a new one).  r > 0 grows every object by r pixels into the
+    background - objects never eat one another, ties go to the smaller label -, r < 0 shrinks; |r| in 1..127.  Two launches on the
+    current stream, no synchronisation."""
+    from . import _lib_matte
+    from .matte import radius2
+    r2, shrink = radius2(r)
+    if r2 < 1:
+        raise ValueError(f'grow_masks: r = {r!r} changes nothing (|r| must be at least 1)')
+    masks, (N, H, W) = _index_maps(masks, 'grow_masks')
+    if out is None:
+        out = torch.empty(masks.shape, dtype=torch.uint8, device=masks.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or out.shape != masks.shape or not out.is_contiguous() or out.device != masks.device:
+        raise RuntimeError(f'grow_masks: out must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(masks.shape)} on the masks\' device')
+    lib = _lib_matte.load()
+    nbytes = lib.xmem_mask_grow_workspace_bytes(N, H, W)
+    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    check(lib.xmem_mask_grow(ptr(masks), N, H, W, r2, int(shrink), ptr(out), ptr(ws), ws.numel(), stream_ptr()))
+    return out

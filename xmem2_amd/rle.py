@@ -662,6 +662,42 @@ def clean_tracks(tracks, spec, batch=32):
     return doc, dict(zip(STATS, (int(v) for v in totals.tolist())))
 
 
+def grow_tracks(tracks, r, batch=32):
+    """A tracks file (or parsed document) with `ops.grow_masks` applied to every frame -> document: r > 0 grows every object by r
+    pixels into the background, r < 0 shrinks it (`matte.grow_host` has the definition).  Per batch: `TrackReader.masks_device` ->
+    `ops.grow_masks` -> `ops.rle_encode`; no mask plane reaches the host, and counts, boxes and areas are the encoder's, of the grown
+    masks.  The masks are decoded with dense ids in ascending order of the labels, so that a tie between two objects goes to the
+    smaller LABEL as the definition says; the tracks come out in that order.  The counts are lists, or compressed strings when
+    every entry of the input is one."""
+    from . import ops
+    reader = TrackReader(tracks)
+    if len(set(reader.labels)) != len(reader.labels):
+        raise ValueError('grow_tracks: two tracks share a label')
+    names = reader.file_names if len(reader.file_names) == len(reader) else [str(t) for t in range(len(reader))]
+    writer = TrackWriter(reader.height, reader.width)
+    labels = sorted(reader.labels)
+    dense = [labels.index(lab) + 1 for lab in reader.labels]
+    k, step = len(labels), max(1, int(batch))
+    for i in range(0, len(reader) if k else 0, step):
+        frames = list(range(i, min(i + step, len(reader))))
+        masks, present = reader.masks_device(frames, values=dense, batch=step)
+        meta, events = ops.rle_encode(ops.grow_masks(masks, r), k)
+        for j, t in enumerate(frames):
+            if present[j]:
+                writer.add_frame(names[t], meta[j], events[j], labels=labels)
+            else:
+                writer.add_frame(names[t])
+    for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
+        writer.add_frame(names[t])
+    for lab in labels:                                               # a track without any entry still has its (empty) row
+        writer._tracks.setdefault(lab, {})
+    doc = writer.to_dict()
+    forms = [is_compressed(c) for segs in reader._segs for c in segs.values()]
+    if forms and all(forms):
+        doc = recode_tracks(doc, 'compressed')
+    return doc
+
+
 def polygon_tracks(tracks, spec=True, batch=32):
     """A tracks file (or parsed document) with the `polygons` key added to every entry (replaced where there was one) -> document.
     Per batch: `TrackReader.masks_device` (dense ids, one per track) -> `ops.mask_polygons`; no mask plane reaches the host.
@@ -780,12 +816,12 @@ def counts_from_polygons(tracks, batch=32):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog='python -m xmem2_amd.rle',
-                                 description='tracks.json -> index PNGs (one per frame), or - with --recode, --clean and / or --polygons - '
-                                             'tracks.json with its counts in the other form, its masks cleaned on the device and / or '
+                                 description='tracks.json -> index PNGs (one per frame), or - with --recode, --clean, --grow and / or --polygons - '
+                                             'tracks.json with its counts in the other form, its masks cleaned, grown or shrunk on the device and / or '
                                              'their polygon outlines added')
     ap.add_argument('--tracks', default=None, help='the tracks.json of one video (counts as lists, compressed strings, or both; '
                                                    'entries may hold polygons alone)')
-    ap.add_argument('--out', default=None, help='directory the PNGs are written to; with --recode, --clean, --polygons, --from-polygons '
+    ap.add_argument('--out', default=None, help='directory the PNGs are written to; with --recode, --clean, --grow, --polygons, --from-polygons '
                                                 'or --from-labelme the file that is written')
     ap.add_argument('--verify-polygons', action='store_true',
                     help='write nothing: fill the polygons of every entry that has both keys and compare them with its counts, on the '
@@ -801,6 +837,10 @@ def parse_args(argv=None):
     ap.add_argument('--clean', default=None, metavar='JSON',
                     help='write no PNGs: rewrite the file with every mask cleaned, e.g. \'{"min_area": 16, "max_hole": 16}\' '
                          '(keys min_area, max_hole, keep_largest; needs the GPU); the count form is kept unless --recode names one')
+    ap.add_argument('--grow', default=None, type=float, metavar='R',
+                    help='write no PNGs: rewrite the file with every object grown by R pixels into the background, or shrunk by -R '
+                         '(1 <= |R| <= 127; needs the GPU); after --clean when both are given; counts, boxes and areas are those of '
+                         'the new masks')
     ap.add_argument('--polygons', nargs='?', const=0.0, default=None, type=float, metavar='TOL',
                     help='write no PNGs: rewrite the file with the polygon outlines of every entry added (key "polygons"), traced on '
                          'the device (needs the GPU); TOL > 0 simplifies every ring (Ramer-Douglas-Peucker, lossy)')
@@ -813,7 +853,10 @@ def parse_args(argv=None):
         ap.error('exactly one of --tracks and --from-labelme is needed')
     if args.out is None and not args.verify_polygons:
         ap.error('--out is needed')
-    if args.from_labelme is not None and (args.verify_polygons or args.from_polygons or args.clean or args.recode or args.polygons is not None):
+    if args.grow is not None and not 1 <= abs(args.grow) <= 127:
+        ap.error('--grow: 1 <= |R| <= 127 is needed')
+    if args.from_labelme is not None and (args.verify_polygons or args.from_polygons or args.clean or args.recode or args.polygons is not None
+                                          or args.grow is not None):
         ap.error('--from-labelme writes the polygon-only file and nothing else: run the other steps on that file')
     if args.clean is not None:
         from .mask_cleanup import parse_cleanup
@@ -842,7 +885,7 @@ def main(argv=None):
             f.write(text)
         print(json.dumps({'frames': doc['videos'][0]['length'], 'tracks': len(doc['annotations']), 'bytes': len(text), 'out': args.out}))
         return 0
-    if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons:
+    if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons or args.grow is not None:
         report = {}
         if args.from_polygons:                                       # first: what follows reads counts
             doc = counts_from_polygons(args.tracks)
@@ -852,6 +895,9 @@ def main(argv=None):
         elif not args.from_polygons:
             with open(args.tracks) as f:
                 doc = json.load(f)
+        if args.grow is not None:                                    # of the cleaned masks, when both are asked for
+            doc = grow_tracks(doc, args.grow)
+            report['grow'] = args.grow
         if args.polygons is not None:                                # of the cleaned masks, when both are asked for
             doc = polygon_tracks(doc, {'tolerance': args.polygons})
             report['polygons'] = doc['videos'][0]['polygons']

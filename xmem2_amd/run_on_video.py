@@ -428,6 +428,53 @@ class _TrackLoop:
         return self.writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
 
 
+def _parse_mattes(config):
+    """config['mattes'] as `matte.parse_mattes` returns it; None without the key - nothing is imported for it then"""
+    if config.get('mattes') is None:
+        return None
+    from .matte import parse_mattes
+    return parse_mattes(config['mattes'])
+
+
+class _MatteLoop:
+    """config['mattes'] inside a frame loop: one `ops.mask_mattes` launch sequence per frame on the compute stream, right behind the
+    clean-up, on the index mask the loop hands on (cleaned, at the original resolution).  The planes - uint8 [T, K, H, W], one per table
+    (matte, trimap) and label the mapper knows at that frame - are delivered through pinned memory one frame behind like the mask
+    (their own AsyncMaskFetcher) and written by `_AsyncSaver` threads as <masks_out_path>/mattes/<label>/<frame>.png and, with a
+    trimap, <masks_out_path>/trimaps/<label>/<frame>.png, 8-bit mode L, <label> the annotation's label as in tracks.json.  Masks,
+    tracks and what goes back into the memory are not touched.  `saver`: the loop's, or None - then the planes get writers of
+    their own, closed with the loop."""
+
+    def __init__(self, spec, saver, masks_out_path, vid_name=''):
+        from .matte import tables_of
+        self.names, self._tables, self.R = tables_of(spec)
+        self.own_saver = _AsyncSaver(masks_out_path, vid_name) if saver is None else None
+        self.saver = self.own_saver if saver is None else saver
+        self.tables = None                                           # on the device, from the first frame on
+        self.fetcher = AsyncMaskFetcher()
+
+    def submit(self, tag, mask_dev, k):
+        """-> the (tag, planes) pairs that have arrived"""
+        if k == 0:
+            return []
+        if self.tables is None:
+            self.tables = torch.from_numpy(self._tables).to(mask_dev.device)
+        return self.fetcher.submit((tag, k), ops.mask_mattes(mask_dev, k, self.tables, self.R))
+
+    def drain(self):
+        return self.fetcher.drain()
+
+    def finish(self, item, mapper):
+        from .matte import plane_job
+        from .rle import inverse_labels
+        ((sample, _), k), planes = item
+        self.saver.submit(plane_job(self.names, inverse_labels(mapper, k), planes, sample.frame[:-4]))
+
+    def close(self):
+        if self.own_saver is not None:
+            self.own_saver.close()                                   # re-raises a writer's error
+
+
 def _working_u8(src_u8, target_hw, device, flip=False):
     """resize_on_device outside the frame loop (preloads, key extraction): upload a source-size frame (or take a device one) and
     resize it on the current stream."""
@@ -538,13 +585,15 @@ class _FrameOutputs:
     its record arrives, gets a copy."""
 
     def __init__(self, reader, mapper, fetcher, saver=None, tracks=None, scorer=None, compute_iou=False, save_overlay=True,
-                 masks_out_path=None, reused_output=False):
+                 masks_out_path=None, reused_output=False, mattes=None):
         self.reader, self.mapper, self.fetcher, self.saver, self.tracks, self.scorer = reader, mapper, fetcher, saver, tracks, scorer
+        self.mattes = mattes                                         # config['mattes']: a _MatteLoop, None without the option
         self.compute_iou, self.save_overlay, self.masks_out_path, self.reused_output = compute_iou, save_overlay, masks_out_path, reused_output
         # the H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou
         self.need_mask = tracks is None or saver is not None or compute_iou
         self.stats = []
         self._arrived = ((), ())
+        self._matted = ()
 
     @staticmethod
     def _tags(tdone):
@@ -557,10 +606,14 @@ class _FrameOutputs:
         tag = (sample, had_mask)
         tdone = self.tracks.submit(tag, out_dev.clone() if self.reused_output else out_dev, len(self.mapper.labels)) \
             if self.tracks is not None else ()
+        if self.mattes is not None:                                  # fed before the mask: when a frame's mask has arrived, so have its planes
+            self._matted = self.mattes.submit(tag, out_dev, len(self.mapper.labels))
         self._arrived = tdone, (self.fetcher.submit(tag, out_dev) if self.need_mask else self._tags(tdone))
 
     def drain(self):
         tdone = self.tracks.drain() if self.tracks is not None else ()
+        if self.mattes is not None:
+            self._matted = self.mattes.drain()
         self._arrived = tdone, (self.fetcher.drain() if self.need_mask else self._tags(tdone))
 
     def deliver(self, last=False):
@@ -568,6 +621,9 @@ class _FrameOutputs:
         self._arrived = ((), ())
         for item in tdone:
             self.tracks.finish(item, item[0][0][0].frame, self.mapper)
+        for item in self._matted:
+            self.mattes.finish(item, self.mapper)
+        self._matted = ()
         for (sample, had_mask), out_mask in done:
             self.stats.append(_stats_row(sample.frame, had_mask, self.compute_iou, out_mask, sample.mask))
             if self.saver is not None:
@@ -578,8 +634,12 @@ class _FrameOutputs:
             self.tracks.write(self.masks_out_path)
 
     def close(self):
-        if self.saver is not None:
-            self.saver.close()                                       # re-raises a writer's error
+        try:
+            if self.mattes is not None:
+                self.mattes.close()
+        finally:
+            if self.saver is not None:
+                self.saver.close()                                   # re-raises a writer's error
 
 
 def _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame):
@@ -624,6 +684,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     frames_with_masks = set(frames_with_masks)
     config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
     cleanup = parse_cleanup(config.get('mask_cleanup'))              # opt-in (default: absent): despeckle / fill holes / keep largest
+    mattes = _parse_mattes(config)                                   # opt-in (default: absent): feathered mattes / trimaps per label
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
@@ -678,12 +739,13 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
     cleaned = _cleanup_totals(cleanup, device)
     # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).
+    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
     outputs = _FrameOutputs(
-        vid_reader, mapper, AsyncMaskFetcher(),
-        saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
+        vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
-        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'])
+        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
+        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -853,6 +915,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     config = _merged_config(dict(overwrite_config or {}), masks_out_path)           # on a copy: the caller's dict stays as it is
     passes = parse_ensemble(config.get('ensemble'), config['size'])
     cleanup = parse_cleanup(config.get('mask_cleanup'))
+    mattes = _parse_mattes(config)
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
@@ -913,12 +976,13 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     mapper = mappers[0]
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
     cleaned = _cleanup_totals(cleanup, device)
+    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
     outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again - unless cleaned
-        vid_reader, mapper, AsyncMaskFetcher(),
-        saver=_AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None,
+        vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
-        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None)
+        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
+        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):

@@ -443,6 +443,15 @@ class VideoSession:
                 totals.add_(stats.sum(0))
         return _cleanup_report(totals)
 
+    def grow(self, r, batch=32):
+        """`ops.grow_masks` on the masks as they stand, `batch` frames per call, in place of what they held: r > 0 grows every object
+        by r pixels into the background (objects never eat one another, ties go to the smaller dense id), r < 0 shrinks it; |r| in
+        1..127.  A frame without a mask is all zero and stays so."""
+        step = max(1, int(batch))
+        with torch.cuda.device(self.device):
+            for i in range(0, len(self), step):
+                self.masks[i:i + step].copy_(ops.grow_masks(self.masks[i:i + step], r))
+
     # ---- candidates ----------------------------------------------------------------------------------------------------
     def mask_table(self, mask_form='objects'):
         """float32[256] on the host: the selector's mask value of a DENSE id.  'objects': any object 1.0 (the GUI's masks);
@@ -535,6 +544,24 @@ class VideoSession:
             meta, events, strings = encoded.get(t, (None, None, None))
             writer.add_frame(fr.frame, meta, events, labels=labels, strings=strings, polygons=rings.get(t))
         return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
+
+    def save_mattes(self, masks_out_path, batch=32, **spec):
+        """What config['mattes'] writes in a frame loop, of the masks as they stand: <masks_out_path>/mattes/<label>/<frame>.png and,
+        with `trimap`, <masks_out_path>/trimaps/<label>/<frame>.png for every frame that has a mask and every label the mapper knows,
+        made from the resident `masks` in launches of `batch` frames (`ops.mask_mattes`).  `spec`: the keys of config['mattes']
+        (feather, offset, falloff, trimap); none of them is `True`, a feather of 2 pixels.  Returns the number of files."""
+        from .matte import parse_mattes, write_mattes
+        from .rle import inverse_labels
+        spec = parse_mattes(spec or True)
+        k = len(self.mapper.labels)
+        if k == 0:
+            raise ValueError('No valid masks provided!')
+
+        def masks_of(frames):
+            return self.masks[frames[0]:frames[-1] + 1], [self._present[t] for t in frames]
+        with torch.cuda.device(self.device):
+            return write_mattes(masks_of, len(self), [fr.frame[:-4] for fr in self.frames], inverse_labels(self.mapper, k),
+                                masks_out_path, spec, batch)
 
     def load_tracks(self, path, batch=32):
         """The inverse of `save_tracks`: the frames of tracks.json (`path`: the file, or the directory that holds it) that have an
