@@ -20,16 +20,23 @@ class XMemHipError(RuntimeError):
     pass
 
 
-def _read_header():
-    """The one parse of the process: every struct, signature and constant below comes from it (type rules: _header)."""
+def _read_header(path):
+    """(constants, structs, signatures) of one header (type rules: _header).  Each header is parsed once per process, at import."""
     try:
-        with open(HEADER_PATH) as fh:
+        with open(path) as fh:
             return _header.parse(fh.read())
     except OSError as e:
-        raise XMemHipError(f'{HEADER_PATH} cannot be read ({e}): the ctypes binding is derived from it') from e
+        raise XMemHipError(f'{path} cannot be read ({e}): the ctypes binding is derived from it') from e
 
 
-CONSTANTS, _STRUCTS, _SIGS = _read_header()
+def _set_signatures(lib, sigs):
+    for name, (res, args) in sigs.items():
+        fn = getattr(lib, name)      # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+
+
+CONSTANTS, _STRUCTS, _SIGS = _read_header(HEADER_PATH)
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 ConvDesc = _STRUCTS['xmem_conv_desc']
@@ -62,14 +69,34 @@ def load():
             f'{LIB_PATH} not found: the MI355X kernels are not built. Run `python -m xmem2_amd.build` '
             '(or __graft_entry__.build()). xmem2_amd has no CPU / PyTorch fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)      # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    _set_signatures(lib, _SIGS)
     if lib.xmem_version() != ABI_VERSION:
         raise XMemHipError('libxmem_hip.so ABI version mismatch')
     _lib = lib
     return lib
+
+
+def bind_header(file_name):
+    """The binding of a later header of libxmem_hip.so, include/<file_name>: functions and #defines only, since include/xmem_hip.h and
+    what this module derives from it are frozen at its ABI version.  Returns (path, constants, exported symbols, load): that `load()`
+    returns the handle of `load()` above with this header's signatures set on it - once per handle, and again should the handle ever
+    be another.  A `_lib_*` module is one call of this and the constants it lifts out.  (An absolute `file_name` is read as it is.)"""
+    path = os.path.join(_HERE, '..', 'include', file_name)
+    constants, structs, sigs = _read_header(path)
+    if structs:
+        raise XMemHipError(f'{path} declares structs {sorted(structs)}: this header carries functions and #defines only')
+    bound = None
+
+    def load_bound():
+        """`_lib.load()` with this header's signatures set on it (once per handle).  Raises when the library or a symbol is missing."""
+        nonlocal bound
+        lib = load()
+        if bound is not lib:
+            _set_signatures(lib, sigs)
+            bound = lib
+        return lib
+
+    return path, constants, tuple(sigs), load_bound
 
 
 def check(code):

@@ -1,42 +1,11 @@
 """ctypes binding of include/xmem_hip_masks.h, the second header of libxmem_hip.so (connected components, mask clean-up).
 
 include/xmem_hip.h and what `_lib` derives from it are frozen at ABI version 5; what was added after it is declared in a header of
-its own and bound here, by the same reader (`_header.parse`), on the same `CDLL` that `_lib.load()` returns.  `check`, `ptr` and
-`stream_ptr` are `_lib`'s.
+its own and bound by `_lib.bind_header`: the same reader (`_header.parse`), on the same `CDLL` that `_lib.load()` returns.  `check`,
+`ptr` and `stream_ptr` are `_lib`'s.
 """
-import os
-
-from . import _header, _lib
+from . import _lib
 from ._lib import XMemHipError, check, ptr, stream_ptr      # noqa: F401  (the callers' one import)
 
-HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'xmem_hip_masks.h')
-_bound = None
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as fh:
-            constants, structs, sigs = _header.parse(fh.read())
-    except OSError as e:
-        raise XMemHipError(f'{HEADER_PATH} cannot be read ({e}): the ctypes binding is derived from it') from e
-    if structs:
-        raise XMemHipError(f'{HEADER_PATH} declares structs {sorted(structs)}: this header carries functions and #defines only')
-    return constants, sigs
-
-
-CONSTANTS, _SIGS = _read_header()
-EXPORTED_SYMBOLS = tuple(_SIGS)
+HEADER_PATH, CONSTANTS, EXPORTED_SYMBOLS, load = _lib.bind_header('xmem_hip_masks.h')
 CLEAN_STATS = CONSTANTS['XMEM_CLEAN_STATS']                  # int32 counters per frame of xmem_mask_clean's stats
-
-
-def load():
-    """`_lib.load()` with this header's signatures set on it (once per handle).  Raises when the library or a symbol is missing."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        _bound = lib
-    return lib

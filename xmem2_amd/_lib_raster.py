@@ -1,43 +1,9 @@
-"""ctypes binding of include/xmem_hip_raster.h, the fourth header of libxmem_hip.so (polygons filled back into index masks).
-
-As `_lib_polygons`: include/xmem_hip.h and what `_lib` derives from it are frozen at ABI version 5, later entry points are declared
-in headers of their own and bound by the same reader (`_header.parse`) on the same `CDLL` that `_lib.load()` returns.
-"""
-import os
-
-from . import _header, _lib
+"""ctypes binding of include/xmem_hip_raster.h, the fourth header of libxmem_hip.so (polygons filled back into index masks): one call
+of `_lib.bind_header`, as `_lib_masks`."""
+from . import _lib
 from ._lib import XMemHipError, check, ptr, stream_ptr      # noqa: F401  (the callers' one import)
 
-HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'xmem_hip_raster.h')
-_bound = None
-
-
-def _read_header():
-    try:
-        with open(HEADER_PATH) as fh:
-            constants, structs, sigs = _header.parse(fh.read())
-    except OSError as e:
-        raise XMemHipError(f'{HEADER_PATH} cannot be read ({e}): the ctypes binding is derived from it') from e
-    if structs:
-        raise XMemHipError(f'{HEADER_PATH} declares structs {sorted(structs)}: this header carries functions and #defines only')
-    return constants, sigs
-
-
-CONSTANTS, _SIGS = _read_header()
-EXPORTED_SYMBOLS = tuple(_SIGS)
+HEADER_PATH, CONSTANTS, EXPORTED_SYMBOLS, load = _lib.bind_header('xmem_hip_raster.h')
 MAX_FRAC_BITS = CONSTANTS['XMEM_FILL_MAX_FRAC_BITS']
 COORD_BOUND = CONSTANTS['XMEM_FILL_COORD_BOUND']             # of a quantised coordinate's magnitude
 FILL_STATUS = CONSTANTS['XMEM_FILL_STATUS']                  # int32 of xmem_polygons_fill's status: edges skipped for plane, for coordinate
-
-
-def load():
-    """`_lib.load()` with this header's signatures set on it (once per handle).  Raises when the library or a symbol is missing."""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(lib, name)      # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        _bound = lib
-    return lib

@@ -947,12 +947,9 @@ def jf_counts(gt, pred, radius, lut=None, out=None):
     """DAVIS J&F counts of uint8 label maps `gt`, `pred` ([H,W] or [B,H,W], same shape) into int32 `out` [B,256,7] (allocated if None):
     per frame and label k in 1..254 the JF_SLOTS counts, boundaries dilated by the disk of `radius` (0..63).  `lut` (uint8 [256]) maps
     pred's labels first.  `out` is zeroed and filled on the current stream; returns it."""
-    for t, name in ((gt, 'gt'), (pred, 'pred')):
-        if not t.is_cuda or t.dtype != torch.uint8 or t.dim() not in (2, 3):
-            raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
+    gt, pred = _req_u8(gt, 'gt', frames='B'), _req_u8(pred, 'pred', frames='B')
     if tuple(gt.shape) != tuple(pred.shape):
         raise RuntimeError(f'gt and pred differ in shape: {tuple(gt.shape)} != {tuple(pred.shape)}')
-    gt, pred = gt.contiguous(), pred.contiguous()
     B, H, W = (1,) + tuple(gt.shape) if gt.dim() == 2 else tuple(gt.shape)
     if lut is not None:
         if not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (256,):
@@ -1407,11 +1404,48 @@ def click_commit(prev_prob, obj_mask, tar_obj, temperature=1000.0):
 CLICK_RECORD = 8        # int32 values of xmem_next_click's record (include/xmem_hip.h)
 
 
-def _req_u8(t, name, shape=None):
-    if not t.is_cuda or t.dtype != torch.uint8 or (shape is not None and tuple(t.shape) != tuple(shape)):
+def _req_u8(t, name, shape=None, frames=None):
+    """`t`, contiguous: a uint8 device tensor - of `shape`, or with `frames` ('B' or 'N', the letter the message names the leading
+    dimension by) maps [H,W] or [frames,H,W]"""
+    if (not t.is_cuda or t.dtype != torch.uint8 or (shape is not None and tuple(t.shape) != tuple(shape))
+            or (frames is not None and t.dim() not in (2, 3))):
         raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor' + (f' of shape {tuple(shape)}' if shape is not None else '')
-                           + ' - xmem2_amd has no CPU path')
+                           + (f' [H,W] or [{frames},H,W]' if frames is not None else '') + ' - xmem2_amd has no CPU path')
     return t.contiguous()
+
+
+def _map_dims(masks, fn):
+    """(B, H, W) of maps [H,W] or [B,H,W], none of them 0"""
+    if masks.numel() == 0:
+        raise RuntimeError(f'{fn}: empty input {tuple(masks.shape)}')
+    return (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
+
+
+def _index_maps(masks, fn):
+    masks = _req_u8(masks, fn, frames='N')
+    return masks, _map_dims(masks, fn)
+
+
+def _int_arg(fn, name, v, low, top=None, numpy_ok=True):
+    """`v` as an int: an integer, not a bool, in low..top (no `top`: at least `low`).  numpy_ok=False takes Python integers only.
+    Which sites take numpy's is history, not design: rle_encode, mask_polygons and the mattes refuse them, rle_decode,
+    rle_compress, rle_decompress and fill_edges accept them.  Each keeps what it did."""
+    kinds = int
+    if numpy_ok:
+        import numpy as np
+        kinds = (int, np.integer)
+    if isinstance(v, bool) or not isinstance(v, kinds) or not (low <= v and (top is None or v <= top)):
+        raise ValueError(f'{fn}: {name} = {v!r} must be an integer ' + (f'in {low}..{top}' if top is not None else f'of at least {low}'))
+    return int(v)
+
+
+def _out_like(out, masks, fn):
+    """`out` for uint8 maps shaped like `masks`: the caller's tensor, or a new one"""
+    if out is None:
+        return torch.empty(masks.shape, dtype=torch.uint8, device=masks.device)
+    if not out.is_cuda or out.dtype != torch.uint8 or out.shape != masks.shape or not out.is_contiguous() or out.device != masks.device:
+        raise RuntimeError(f'{fn}: out must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(masks.shape)} on the masks\' device')
+    return out
 
 
 def edt_sq(mask, out=None):
@@ -1467,7 +1501,7 @@ def next_click(d2, not_clicked, counts=None, record=None):
         record = torch.empty(CLICK_RECORD, dtype=torch.int32, device=d2.device)
     lib = load()
     nbytes = lib.xmem_next_click_workspace_bytes(H, W)
-    ws = workspace(max(nbytes, 8), d2.device, 'next_click')
+    ws = workspace(nbytes, d2.device, 'next_click')
     check(lib.xmem_next_click(ptr(d2), ptr(not_clicked), ptr(counts), H, W, ptr(record), ptr(ws), ws.numel(), stream_ptr()))
     return record
 
@@ -1478,6 +1512,26 @@ RLE_STATS = {'launches': 0, 'retries': 0}      # calls of xmem_rle_encode / fram
 RLE_STRING_STATS = {'launches': 0, 'retries': 0}       # calls of xmem_rle_compress / frames compressed again: their characters did not fit
 
 
+def _exact_fit(again, stats, split, rec, masks, K, capacity, refusal):
+    """The wait=True tail of rle_encode and mask_polygons: the device record `rec` of `masks` on the host as (meta, list of each
+    frame's words).  The counts in `meta` are the true ones, so a frame whose words did not fit `capacity` goes through `again`
+    (the caller, by its name in this module) once more on its own with room for all of them, and must count the same."""
+    B = masks.shape[0] if masks.dim() == 3 else 1
+    meta, words = split(rec.cpu().numpy(), B, K, capacity)
+    out = []
+    for b in range(B):
+        total = int(meta[b, :, 0].sum())
+        if total > capacity:
+            stats['retries'] += 1
+            meta_b, words_b = again(masks[b:b + 1], K, capacity=total)
+            if (meta_b[0] != meta[b]).any():
+                raise RuntimeError(refusal)
+            out.append(words_b[0])
+        else:
+            out.append(words[b, :total].copy())
+    return meta.copy(), out
+
+
 def rle_encode(masks, K, capacity=None, wait=True):
     """Run boundaries, areas and boxes of the labels 1..K of uint8 label maps `masks` [H,W] or [B,H,W] in the COCO order x * H + y
     (xmem2_amd/rle.py has the definitions).  `capacity`: events per frame there is room for (default `rle.default_capacity`).
@@ -1486,39 +1540,42 @@ def rle_encode(masks, K, capacity=None, wait=True):
     ever cut off.  wait=False: one launch sequence on the current stream and no synchronisation; returns the int32 device tensor
     `rle.split_record(., B, K, capacity)` takes apart, whose true counts tell the caller which frames to encode again."""
     from . import rle
-    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
-        raise RuntimeError('masks: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
-    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= 254):
-        raise ValueError(f'rle_encode: K = {K!r} must be an integer in 1..254')
-    masks = masks.contiguous()
-    B, H, W = (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
-    if B == 0 or H == 0 or W == 0:
-        raise RuntimeError(f'rle_encode: empty input {tuple(masks.shape)}')
+    masks = _req_u8(masks, 'masks', frames='B')
+    K = _int_arg('rle_encode', 'K', K, 1, 254, numpy_ok=False)
+    B, H, W = _map_dims(masks, 'rle_encode')
     capacity = rle.default_capacity(H, W) if capacity is None else int(capacity)
     if capacity < 1:
         raise ValueError(f'rle_encode: capacity = {capacity} must be at least 1')
     lib = load()
     rec = torch.empty(B * K * rle.META + B * capacity, dtype=torch.int32, device=masks.device)
-    nbytes = lib.xmem_rle_workspace_bytes(B, W, K)
-    ws = workspace(max(nbytes, 4), masks.device, 'rle')
+    ws = workspace(lib.xmem_rle_workspace_bytes(B, W, K), masks.device, 'rle')
     RLE_STATS['launches'] += 1
     check(lib.xmem_rle_encode(ptr(masks), B, H, W, K, capacity, ptr(rec), C.c_void_p(rec.data_ptr() + 4 * B * K * rle.META), ptr(ws),
                               ws.numel(), stream_ptr()))
     if not wait:
         return rec
-    meta, events = rle.split_record(rec.cpu().numpy(), B, K, capacity)
-    out = []
-    for b in range(B):
-        total = int(meta[b, :, 0].sum())
-        if total > capacity:                                  # the counts are the true ones: once more, with room for all of them
-            RLE_STATS['retries'] += 1
-            meta_b, ev_b = rle_encode(masks[b:b + 1], K, capacity=total)
-            if (meta_b[0] != meta[b]).any():
-                raise RuntimeError('rle_encode: a frame encoded again gave other counts')
-            out.append(ev_b[0])
-        else:
-            out.append(events[b, :total].copy())
-    return meta.copy(), out
+    return _exact_fit(rle_encode, RLE_STATS, rle.split_record, rec, masks, K, capacity, 'rle_encode: a frame encoded again gave other counts')
+
+
+def _frames_fit(B, fn):
+    if B > 65535:
+        raise ValueError(f'{fn}: {B} frames in one launch, at most 65535')
+
+
+def _record_frames(record, K, capacity, fn):
+    """B of `record`, the int32 device tensor of rle_encode(wait=False) with this `capacity`: a whole number of frames of
+    K * META + capacity words, at most 65535"""
+    from . import rle
+    if not torch.is_tensor(record) or not record.is_cuda or record.dtype != torch.int32 or record.dim() != 1 or not record.is_contiguous():
+        raise RuntimeError('record: expected the contiguous int32 CUDA (HIP) tensor of rle_encode(wait=False) - xmem2_amd has no CPU path')
+    if capacity is None:
+        raise ValueError(f'{fn}: a device record needs the capacity it was encoded with')
+    per_frame = K * rle.META + capacity
+    B = record.numel() // per_frame
+    if B < 1 or B * per_frame != record.numel():
+        raise ValueError(f'{fn}: a record of {record.numel()} words is not a whole number of frames of K = {K}, capacity = {capacity}')
+    _frames_fit(B, fn)
+    return B
 
 
 def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True):
@@ -1531,24 +1588,11 @@ def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True
     check=False returns (masks, status int32 [B] on the device) without synchronising: such a frame is all zero, status 1."""
     import numpy as np
     from . import rle
-    for name, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (1 <= v <= top):
-            raise ValueError(f'rle_decode: {name} = {v!r} must be an integer in 1..{top}')
-    H, W, K = int(H), int(W), int(K)
+    H, W, K = (_int_arg('rle_decode', n, v, 1, top) for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
     if capacity is not None:
-        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 1:
-            raise ValueError(f'rle_decode: capacity = {capacity!r} must be an integer of at least 1')
-        capacity = int(capacity)
+        capacity = _int_arg('rle_decode', 'capacity', capacity, 1)
     if torch.is_tensor(record):
-        if not record.is_cuda or record.dtype != torch.int32 or record.dim() != 1 or not record.is_contiguous():
-            raise RuntimeError('record: expected the contiguous int32 CUDA (HIP) tensor of rle_encode(wait=False) - xmem2_amd has no CPU path')
-        if capacity is None:
-            raise ValueError('rle_decode: a device record needs the capacity it was encoded with')
-        per_frame = K * rle.META + capacity
-        B = record.numel() // per_frame
-        if B < 1 or B * per_frame != record.numel():
-            raise ValueError(f'rle_decode: a record of {record.numel()} words is not a whole number of frames of K = {K}, capacity = {capacity}')
-        device = record.device
+        B, device = _record_frames(record, K, capacity, 'rle_decode'), record.device
     else:
         if not torch.cuda.is_available():
             raise RuntimeError('rle_decode: needs an MI355X (HIP) device - xmem2_amd has no CPU path')
@@ -1568,8 +1612,7 @@ def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True
             ev[b, :n] = e[:n]
         device = values.device if torch.is_tensor(values) and values.is_cuda else torch.device('cuda', torch.cuda.current_device())
         record = torch.from_numpy(buf).to(device)
-    if B > 65535:
-        raise ValueError(f'rle_decode: {B} frames in one launch, at most 65535')
+        _frames_fit(B, 'rle_decode')
     if values is not None:
         if not torch.is_tensor(values):
             v = np.asarray(values)
@@ -1594,13 +1637,6 @@ def rle_decode(record, H, W, K, capacity=None, values=None, out=None, check=True
     return out
 
 
-def _rle_int(name, v, low, top, fn):
-    import numpy as np
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (low <= v <= top):
-        raise ValueError(f'{fn}: {name} = {v!r} must be an integer in {low}..{top}')
-    return int(v)
-
-
 def rle_compress(record, H, W, K, capacity, char_capacity=None, wait=True):
     """The compressed COCO strings (`rle.compress_counts` is the definition) of a record: `record` is the int32 device tensor
     `rle_encode(..., wait=False)` returns, `capacity` the one it was encoded with, `char_capacity` the bytes per frame there is room
@@ -1610,21 +1646,14 @@ def rle_compress(record, H, W, K, capacity, char_capacity=None, wait=True):
     a list of B lists of K str on the HOST ('' for a label without event); a frame whose characters did not fit is compressed again
     with exactly its size; a frame whose events did not fit the record is None - only the masks can be encoded again."""
     from . import rle
-    H, W, K = (_rle_int(n, v, 1, top, 'rle_compress') for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
-    capacity = _rle_int('capacity', capacity, 1, 1 << 28, 'rle_compress')
-    if not torch.is_tensor(record) or not record.is_cuda or record.dtype != torch.int32 or record.dim() != 1 or not record.is_contiguous():
-        raise RuntimeError('record: expected the contiguous int32 CUDA (HIP) tensor of rle_encode(wait=False) - xmem2_amd has no CPU path')
-    per_frame = K * rle.META + capacity
-    B = record.numel() // per_frame
-    if B < 1 or B * per_frame != record.numel():
-        raise ValueError(f'rle_compress: a record of {record.numel()} words is not a whole number of frames of K = {K}, capacity = {capacity}')
-    if B > 65535:
-        raise ValueError(f'rle_compress: {B} frames in one launch, at most 65535')
+    H, W, K = (_int_arg('rle_compress', n, v, 1, top) for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
+    capacity = _int_arg('rle_compress', 'capacity', capacity, 1, 1 << 28)
+    B = _record_frames(record, K, capacity, 'rle_compress')
     char_capacity = rle.default_char_capacity(H, W, capacity) if char_capacity is None \
-        else _rle_int('char_capacity', char_capacity, 1, (1 << 31) - 1, 'rle_compress')
+        else _int_arg('rle_compress', 'char_capacity', char_capacity, 1, (1 << 31) - 1)
     lib = load()
     out = torch.zeros(4 * B * K + B * char_capacity, dtype=torch.uint8, device=record.device)
-    ws = workspace(max(lib.xmem_rle_compress_workspace_bytes(B, K, capacity), 4), record.device, 'rle')
+    ws = workspace(lib.xmem_rle_compress_workspace_bytes(B, K, capacity), record.device, 'rle')
     RLE_STRING_STATS['launches'] += 1
     check(lib.xmem_rle_compress(ptr(record), C.c_void_p(record.data_ptr() + 4 * B * K * rle.META), B, H, W, K, capacity, char_capacity,
                                 ptr(out), C.c_void_p(out.data_ptr() + 4 * B * K), ptr(ws), ws.numel(), stream_ptr()))
@@ -1676,9 +1705,9 @@ def rle_decompress(strings, H, W, K, capacity=None, check=True):
     synchronising: such a row has no events in the record, its neighbours are exact."""
     import numpy as np
     from . import rle
-    H, W, K = (_rle_int(n, v, 1, top, 'rle_decompress') for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
+    H, W, K = (_int_arg('rle_decompress', n, v, 1, top) for n, v, top in (('H', H, 16384), ('W', W, 16384), ('K', K, 254)))
     if capacity is not None:
-        capacity = _rle_int('capacity', capacity, 1, (1 << 31) - 1, 'rle_decompress')
+        capacity = _int_arg('rle_decompress', 'capacity', capacity, 1, (1 << 31) - 1)
     if isinstance(strings, tuple) and len(strings) == 2 and torch.is_tensor(strings[0]):
         chars, ofs = strings
         if not chars.is_cuda or chars.dtype != torch.uint8 or chars.dim() != 1 or not chars.is_contiguous():
@@ -1730,7 +1759,7 @@ def rle_decompress(strings, H, W, K, capacity=None, check=True):
     lib = load()
     record = torch.zeros(B * K * rle.META + B * capacity, dtype=torch.int32, device=device)
     status = torch.empty((B, K), dtype=torch.int32, device=device)
-    ws = workspace(max(lib.xmem_rle_decompress_workspace_bytes(B, K), 4), device, 'rle')
+    ws = workspace(lib.xmem_rle_decompress_workspace_bytes(B, K), device, 'rle')
     with torch.cuda.device(device):
         _lib.check(lib.xmem_rle_decompress(ptr(chars), n_chars, ptr(ofs), B, H, W, K, capacity, ptr(record),
                                            C.c_void_p(record.data_ptr() + 4 * B * K * rle.META), ptr(status), ptr(ws), ws.numel(),
@@ -1840,15 +1869,6 @@ def brs_param_grad(g, x, scale_bias, record, grad, reg_weight=1e-3, reg_bias_wei
 
 # ---- connected components and mask clean-up (csrc/components.hip, include/xmem_hip_masks.h): integer, bit-reproducible --------
 
-def _index_maps(masks, name):
-    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
-        raise RuntimeError(f'{name}: expected a uint8 CUDA (HIP) tensor [H,W] or [N,H,W] - xmem2_amd has no CPU path')
-    if masks.numel() == 0:
-        raise RuntimeError(f'{name}: empty input {tuple(masks.shape)}')
-    masks = masks.contiguous()
-    return masks, (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
-
-
 def components(masks, connectivity=8):
     """Connected components of uint8 maps `masks` [H,W] or [N,H,W] on the device -> (root, area), int32 tensors of that shape:
     `mask_cleanup.components_host` per frame, bit for bit (a component is a maximal 4- / 8-connected set of pixels of EQUAL value, 0
@@ -1861,8 +1881,7 @@ def components(masks, connectivity=8):
     lib = _lib_masks.load()
     root = torch.empty(masks.shape, dtype=torch.int32, device=masks.device)
     area = torch.empty(masks.shape, dtype=torch.int32, device=masks.device)
-    nbytes = lib.xmem_components_workspace_bytes(N, H, W)
-    ws = workspace(max(nbytes, 8), masks.device, 'components')
+    ws = workspace(lib.xmem_components_workspace_bytes(N, H, W), masks.device, 'components')
     check(lib.xmem_components(ptr(masks), N, H, W, int(connectivity), ptr(root), ptr(area), ptr(ws), ws.numel(), stream_ptr()))
     return root, area
 
@@ -1877,14 +1896,10 @@ def clean_masks(masks, min_area=0, max_hole=0, keep_largest=False, out=None):
     from .mask_cleanup import parse_cleanup
     spec = parse_cleanup({'min_area': min_area, 'max_hole': max_hole, 'keep_largest': keep_largest}) or {}
     masks, (N, H, W) = _index_maps(masks, 'clean_masks')
-    if out is None:
-        out = torch.empty(masks.shape, dtype=torch.uint8, device=masks.device)
-    elif not out.is_cuda or out.dtype != torch.uint8 or out.shape != masks.shape or not out.is_contiguous() or out.device != masks.device:
-        raise RuntimeError(f'clean_masks: out must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(masks.shape)} on the masks\' device')
+    out = _out_like(out, masks, 'clean_masks')
     lib = _lib_masks.load()
     stats = torch.empty((N, _lib_masks.CLEAN_STATS) if masks.dim() == 3 else (_lib_masks.CLEAN_STATS,), dtype=torch.int32, device=masks.device)
-    nbytes = lib.xmem_mask_clean_workspace_bytes(N, H, W)
-    ws = workspace(max(nbytes, 8), masks.device, 'mask_clean')
+    ws = workspace(lib.xmem_mask_clean_workspace_bytes(N, H, W), masks.device, 'mask_clean')
     check(lib.xmem_mask_clean(ptr(masks), N, H, W, spec.get('min_area', 0), spec.get('max_hole', 0), int(spec.get('keep_largest', False)),
                               ptr(out), ptr(stats), ptr(ws), ws.numel(), stream_ptr()))
     return out, stats
@@ -1904,39 +1919,22 @@ def mask_polygons(masks, K, capacity=None, wait=True):
     returns the int32 device tensor `polygons.split_record(., B, K, capacity)` takes apart, whose true counts tell the caller which
     frames to trace again."""
     from . import _lib_polygons, polygons
-    if not masks.is_cuda or masks.dtype != torch.uint8 or masks.dim() not in (2, 3):
-        raise RuntimeError('masks: expected a uint8 CUDA (HIP) tensor [H,W] or [B,H,W] - xmem2_amd has no CPU path')
-    if isinstance(K, bool) or not isinstance(K, int) or not (1 <= K <= 254):
-        raise ValueError(f'mask_polygons: K = {K!r} must be an integer in 1..254')
-    masks = masks.contiguous()
-    B, H, W = (1,) + tuple(masks.shape) if masks.dim() == 2 else tuple(masks.shape)
-    if B == 0 or H == 0 or W == 0:
-        raise RuntimeError(f'mask_polygons: empty input {tuple(masks.shape)}')
+    masks = _req_u8(masks, 'masks', frames='B')
+    K = _int_arg('mask_polygons', 'K', K, 1, 254, numpy_ok=False)
+    B, H, W = _map_dims(masks, 'mask_polygons')
     capacity = polygons.default_capacity(H, W) if capacity is None else int(capacity)
     if not 1 <= capacity <= _lib_polygons.MAX_CAPACITY:
         raise ValueError(f'mask_polygons: capacity = {capacity} must be in 1..{_lib_polygons.MAX_CAPACITY}')
     lib = _lib_polygons.load()
     rec = torch.empty(B * K * polygons.META + B * capacity, dtype=torch.int32, device=masks.device)
-    nbytes = lib.xmem_mask_polygons_workspace_bytes(B, H, W, K, capacity)
-    ws = workspace(max(nbytes, 8), masks.device, 'polygons')
+    ws = workspace(lib.xmem_mask_polygons_workspace_bytes(B, H, W, K, capacity), masks.device, 'polygons')
     POLY_STATS['launches'] += 1
     check(lib.xmem_mask_polygons(ptr(masks), B, H, W, K, capacity, ptr(rec), C.c_void_p(rec.data_ptr() + 4 * B * K * polygons.META),
                                  ptr(ws), ws.numel(), stream_ptr()))
     if not wait:
         return rec
-    meta, corners = polygons.split_record(rec.cpu().numpy(), B, K, capacity)
-    out = []
-    for b in range(B):
-        total = int(meta[b, :, 0].sum())
-        if total > capacity:                                  # the counts are the true ones: once more, with room for all of them
-            POLY_STATS['retries'] += 1
-            meta_b, words_b = mask_polygons(masks[b:b + 1], K, capacity=total)
-            if (meta_b[0] != meta[b]).any():
-                raise RuntimeError('mask_polygons: a frame traced again gave other counts')
-            out.append(words_b[0])
-        else:
-            out.append(corners[b, :total].copy())
-    return meta.copy(), out
+    return _exact_fit(mask_polygons, POLY_STATS, polygons.split_record, rec, masks, K, capacity,
+                      'mask_polygons: a frame traced again gave other counts')
 
 
 # ---- polygons filled back into masks (csrc/polygons_fill.hip, include/xmem_hip_raster.h): integer, bit-reproducible ------------
@@ -1953,11 +1951,8 @@ def fill_edges(edges, plane, N, H, W, R, values=None, frac_bits=8, out=None, ove
     frames go in chunks - every edge still goes up once, sorted by chunk.  Returns what `fill_polygons` returns."""
     import numpy as np
     from . import _lib_raster
-    for name, v, low, top in (('N', N, 1, 1 << 30), ('H', H, 1, 16384), ('W', W, 1, 16384), ('R', R, 1, 1 << 20),
-                              ('frac_bits', frac_bits, 0, _lib_raster.MAX_FRAC_BITS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (low <= v <= top):
-            raise ValueError(f'fill_polygons: {name} = {v!r} must be an integer in {low}..{top}')
-    N, H, W, R, frac_bits = int(N), int(H), int(W), int(R), int(frac_bits)
+    N, H, W, R, frac_bits = (_int_arg('fill_polygons', n, v, low, top) for n, v, low, top in (
+        ('N', N, 1, 1 << 30), ('H', H, 1, 16384), ('W', W, 1, 16384), ('R', R, 1, 1 << 20), ('frac_bits', frac_bits, 0, _lib_raster.MAX_FRAC_BITS)))
     edges, plane = np.ascontiguousarray(edges, np.int32).reshape(-1, 4), np.ascontiguousarray(plane, np.int32).reshape(-1)
     if len(edges) != len(plane):
         raise ValueError(f'fill_polygons: {len(edges)} edges, {len(plane)} plane indices')
@@ -2000,8 +1995,7 @@ def fill_edges(edges, plane, N, H, W, R, values=None, frac_bits=8, out=None, ove
             for j in range(n_fc):
                 nf = min(fc, N - j * fc)
                 a, b = int(starts[i * n_fc + j]), int(starts[i * n_fc + j + 1])
-                nbytes = lib.xmem_polygons_fill_workspace_bytes(nf, H, W, rows)
-                ws = workspace(max(nbytes, 8), device, 'polygons_fill')
+                ws = workspace(lib.xmem_polygons_fill_workspace_bytes(nf, H, W, rows), device, 'polygons_fill')
                 FILL_STATS['launches'] += 1
                 _lib.check(lib.xmem_polygons_fill(C.c_void_p(up.data_ptr() + 16 * a), C.c_void_p(up.data_ptr() + 16 * E + 4 * a), b - a, nf, H, W,
                                                   rows, frac_bits, C.c_void_p(table.data_ptr() + i * rc), int(bool(overlay) or i > 0),
@@ -2036,11 +2030,10 @@ def fill_polygons(frames, H, W, values=None, frac_bits=8, out=None, overlay=Fals
 
 # ---- signed distances, mattes, trimaps, grow / shrink (csrc/matte.hip, include/xmem_hip_matte.h): integer, bit-reproducible -------
 
-def _matte_labels(name, K, R):
+def _matte_labels(fn, K, R):
     from . import _lib_matte
-    for what, v, hi in (('K', K, _lib_matte.MAX_LABELS), ('R', R, _lib_matte.MAX_R)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
-            raise ValueError(f'{name}: {what} = {v!r} must be an integer in 1..{hi}')
+    for name, v, top in (('K', K, _lib_matte.MAX_LABELS), ('R', R, _lib_matte.MAX_R)):
+        _int_arg(fn, name, v, 1, top, numpy_ok=False)
 
 
 def signed_edt_sq(masks, K, R):
@@ -2052,8 +2045,7 @@ def signed_edt_sq(masks, K, R):
     masks, (N, H, W) = _index_maps(masks, 'signed_edt_sq')
     lib = _lib_matte.load()
     out = torch.empty((N, K, H, W) if masks.dim() == 3 else (K, H, W), dtype=torch.int32, device=masks.device)
-    nbytes = lib.xmem_signed_edt_workspace_bytes(N, H, W, K)
-    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    ws = workspace(lib.xmem_signed_edt_workspace_bytes(N, H, W, K), masks.device, 'matte')
     check(lib.xmem_signed_edt(ptr(masks), N, H, W, K, R, ptr(out), ptr(ws), ws.numel(), stream_ptr()))
     return out
 
@@ -2073,8 +2065,7 @@ def mask_mattes(masks, K, tables, R):
     tables = tables.contiguous()
     lib = _lib_matte.load()
     out = torch.empty((T, N, K, H, W) if masks.dim() == 3 else (T, K, H, W), dtype=torch.uint8, device=masks.device)
-    nbytes = lib.xmem_mask_matte_workspace_bytes(N, H, W, K)
-    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    ws = workspace(lib.xmem_mask_matte_workspace_bytes(N, H, W, K), masks.device, 'matte')
     check(lib.xmem_mask_matte(ptr(masks), N, H, W, K, R, ptr(tables), T, ptr(out), ptr(ws), ws.numel(), stream_ptr()))
     return out
 
@@ -2090,12 +2081,8 @@ def grow_masks(masks, r, out=None):
     if r2 < 1:
         raise ValueError(f'grow_masks: r = {r!r} changes nothing (|r| must be at least 1)')
     masks, (N, H, W) = _index_maps(masks, 'grow_masks')
-    if out is None:
-        out = torch.empty(masks.shape, dtype=torch.uint8, device=masks.device)
-    elif not out.is_cuda or out.dtype != torch.uint8 or out.shape != masks.shape or not out.is_contiguous() or out.device != masks.device:
-        raise RuntimeError(f'grow_masks: out must be a contiguous uint8 CUDA (HIP) tensor of shape {tuple(masks.shape)} on the masks\' device')
+    out = _out_like(out, masks, 'grow_masks')
     lib = _lib_matte.load()
-    nbytes = lib.xmem_mask_grow_workspace_bytes(N, H, W)
-    ws = workspace(max(nbytes, 8), masks.device, 'matte')
+    ws = workspace(lib.xmem_mask_grow_workspace_bytes(N, H, W), masks.device, 'matte')
     check(lib.xmem_mask_grow(ptr(masks), N, H, W, r2, int(shrink), ptr(out), ptr(ws), ws.numel(), stream_ptr()))
     return out
