@@ -246,13 +246,13 @@ def write_mattes(masks_of, n_frames, stems, labels, out_dir, spec, batch=32):
     no file.  Returns the number of files."""
     import torch
     from . import ops
+    from .rle import batches
     from .run_on_video import _AsyncSaver
     names, tables, R = tables_of(spec)
-    k, step, written = len(labels), max(1, int(batch)), 0
+    k, written = len(labels), 0
     saver, tables_dev = _AsyncSaver(str(out_dir), ''), None
     try:
-        for i in range(0, n_frames if k else 0, step):
-            frames = list(range(i, min(i + step, n_frames)))
+        for frames in batches(range(n_frames if k else 0), batch):
             dense, present = masks_of(frames)
             if not any(present):
                 continue
@@ -272,10 +272,8 @@ def matte_tracks(tracks, out_dir, spec, batch=32):
     """The planes of every entry of a tracks file, decoded on the device (`TrackReader.masks_device`): <label> is the track's label."""
     from .rle import TrackReader
     reader = TrackReader(tracks)
-    if len(set(reader.labels)) != len(reader.labels):
-        raise ValueError('matte_tracks: two tracks share a label')
-    names = reader.file_names if len(reader.file_names) == len(reader) else [str(t) for t in range(len(reader))]
-    stems = [os.path.splitext(n)[0] for n in names]
+    reader.require_unique_labels('matte_tracks')
+    stems = [os.path.splitext(n)[0] for n in reader.frame_names()]
 
     def masks_of(frames):
         return reader.masks_device(frames, values='dense', batch=max(1, int(batch)))

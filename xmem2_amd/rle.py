@@ -228,6 +228,34 @@ def check_count_form(counts):
     return counts
 
 
+def box_xywh(row):
+    """A meta row (events, area, x0, y0, x1, y1 with inclusive corners) -> the file's [x, y, w, h]."""
+    x0, y0, x1, y1 = (int(v) for v in row[2:6])
+    return [x0, y0, x1 - x0 + 1, y1 - y0 + 1]
+
+
+def read_json(path):
+    with open(path) as f:
+        return json.load(f)
+
+
+def write_json(doc, path):
+    """Write `doc` as compact JSON to the file `path`, whose directory is made; returns the text."""
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    text = json.dumps(doc, separators=(',', ':'))                    # dumps, not dump: one pass of the C encoder
+    with open(path, 'w') as f:
+        f.write(text)
+    return text
+
+
+def batches(frames, step):
+    """The sequence `frames` in lists of `step` (at least 1), the last one shorter: what one launch serves."""
+    step = max(1, int(step))
+    for i in range(0, len(frames), step):
+        yield list(frames[i:i + step])
+
+
 class TrackWriter:
     """One video's tracks.  Frames are added in order; a track is opened when its label is first named and has null wherever the
     label was not known yet, had no pixel, or the frame had no mask."""
@@ -240,6 +268,11 @@ class TrackWriter:
         self._tracks = collections.OrderedDict()                     # label in the annotation PNGs -> {frame index: (counts, bbox, area)}
         self.polygons = parse_polygons(polygons)
         self._rings = {}                                             # (label, frame index) -> the entry's rings as flat integer lists
+
+    def open_track(self, label):
+        """The entries {frame index: (counts, bbox, area)} of the track with this label, opened - so far without any - when the label
+        is new: a track that never gets an entry is written with null in every frame."""
+        return self._tracks.setdefault(int(label), {})
 
     def add_frame(self, file_name, meta=None, events=None, labels=None, strings=None, polygons=None):
         """`meta` [K, META] and the frame's packed `events` as `ops.rle_encode` gives them (`events` holding all of them), `labels`
@@ -267,14 +300,13 @@ class TrackWriter:
                 raise ValueError(f'add_frame: {len(meta)} label rows, polygons of {len(polygons[0])}')
             rings = poly.label_flat(*polygons, tolerance=self.polygons['tolerance'])
         for lab, row, ev, rr in zip(labels, meta, rows, rings):
-            track = self._tracks.setdefault(lab, {})
+            track = self.open_track(lab)
             area = int(row[1])
             if area and rr is not None:
                 self._rings[(lab, t)] = rr
             if area:
-                x0, y0, x1, y1 = (int(v) for v in row[2:6])
                 counts = counts_from_events(ev, self.height, self.width) if strings is None else str(ev)
-                track[t] = (counts, [x0, y0, x1 - x0 + 1, y1 - y0 + 1], area)
+                track[t] = (counts, box_xywh(row), area)
 
     def add_mask(self, file_name, mask, k=None, labels=None, counts='list'):
         """A frame from a host index array (dense ids 1..k, default its largest id), encoded on the host; None: a frame without mask.
@@ -317,13 +349,8 @@ class TrackWriter:
         """Write the file (`path`: the file, or a directory that gets tracks.json); returns the file's path."""
         path = str(path)
         if os.path.isdir(path) or not path.endswith('.json'):
-            os.makedirs(path, exist_ok=True)
             path = os.path.join(path, 'tracks.json')
-        elif os.path.dirname(path):
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-        text = json.dumps(self.to_dict(), separators=(',', ':'))      # dumps, not dump: one pass of the C encoder
-        with open(path, 'w') as f:
-            f.write(text)
+        write_json(self.to_dict(), path)
         return path
 
 
@@ -336,8 +363,7 @@ def inverse_labels(mapper, k):
 def read_tracks(path):
     """tracks.json -> (video dict, list of index masks uint8 [H, W] holding the annotations' labels, None for a frame in which no
     track has an entry)."""
-    with open(path) as f:
-        doc = json.load(f)
+    doc = read_json(path)
     if len(doc.get('videos', [])) != 1:
         raise ValueError('read_tracks: expected one video per file')
     if any(seg is not None and 'counts' not in seg and 'polygons' in seg
@@ -364,6 +390,25 @@ def read_tracks(path):
     return video, masks
 
 
+def ring_rows(rings, fill):
+    """An entry's rings as the rows of a fill: under 'evenodd' one row (its rings filled together, holes being rings), under 'union'
+    one row per ring, each filled on its own."""
+    return [[r] for r in rings] if fill == 'union' else [rings]
+
+
+def pack_rows(rings_of, values, fill, least=0):
+    """The rows that let one `ops.fill_polygons` serve a batch of frames -> (rows of every frame, value of every row).
+    rings_of[a][j]: the rings of track a (there is at least one) in frame j, None where it has no polygon; values[a]: what its pixels
+    get.  Every track owns a fixed run of rows in all frames - as many as its longest `ring_rows` list among them and at least
+    `least`, shorter lists padded with [] -, so one values table serves them all; the first track gets a row when nobody has one."""
+    per = [[[] if rings is None else ring_rows(rings, fill) for rings in of_track] for of_track in rings_of]
+    width = [max([least] + [len(rows) for rows in of_track]) for of_track in per]
+    if not any(width):
+        width[0] = 1
+    rows = [[row for of_track, n in zip(per, width) for row in of_track[j] + [[]] * (n - len(of_track[j]))] for j in range(len(per[0]))]
+    return rows, [v for v, n in zip(values, width) for _ in range(n)]
+
+
 class TrackReader:
     """One video's tracks.json, parsed once (`path_or_doc`: the file, or the parsed document) with `read_tracks`'s validation.  The
     annotations are the label rows of a record in file order, so a later annotation wins where tracks overlap, as in `read_tracks`.
@@ -378,11 +423,7 @@ class TrackReader:
     its counts.  A frame that mixes polygon-only entries with counts entries raises ValueError when it is read."""
 
     def __init__(self, path_or_doc):
-        if isinstance(path_or_doc, dict):
-            doc = path_or_doc
-        else:
-            with open(path_or_doc) as f:
-                doc = json.load(f)
+        doc = path_or_doc if isinstance(path_or_doc, dict) else read_json(path_or_doc)
         if len(doc.get('videos', [])) != 1:
             raise ValueError('read_tracks: expected one video per file')
         self.video = doc['videos'][0]
@@ -425,6 +466,15 @@ class TrackReader:
     def __len__(self):
         return self.length
 
+    def frame_names(self):
+        """One name per frame: the video's `file_names`, or the frame numbers where it does not name every frame."""
+        return self.file_names if len(self.file_names) == len(self) else [str(t) for t in range(len(self))]
+
+    def require_unique_labels(self, who):
+        """ValueError, in the name of the tool `who`, for a file that has two tracks with one label: a label map cannot hold them."""
+        if len(set(self.labels)) != len(self.labels):
+            raise ValueError(f'{who}: two tracks share a label')
+
     def _frame(self, t):
         if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not (0 <= t < self.length):
             raise IndexError(f'frame {t!r} is not a frame of these tracks (0..{self.length - 1})')
@@ -445,16 +495,15 @@ class TrackReader:
         return t
 
     def polygon_rows(self, t):
-        """(rows, values) of a polygon frame for `polygons.fill_rows_host` / `ops.fill_polygons`: under 'evenodd' one row per
-        annotation (its rings filled together, holes being rings), under 'union' one row per ring, each filled on its own; `values`
-        holds every row's annotation (0-based), so a later annotation wins where tracks overlap, as with counts."""
+        """(rows, values) of a polygon frame for `polygons.fill_rows_host` / `ops.fill_polygons`: the `ring_rows` of every annotation;
+        `values` holds every row's annotation (0-based), so a later annotation wins where tracks overlap, as with counts."""
         t = self._unmixed(self._frame(t))
         rows, owner = [], []
         for a, polys in enumerate(self._polys):
             rings = polys.get(t)
             if rings is None:
                 continue
-            for row in ([[r] for r in rings] if self.fill == 'union' else [rings]):
+            for row in ring_rows(rings, self.fill):
                 rows.append(row)
                 owner.append(a)
         return rows, owner
@@ -502,7 +551,6 @@ class TrackReader:
         values='label': the annotations' labels; 'dense': 1..n in file order; or a list of one value in 0..255 per annotation.  A
         frame without any entry is all zero, not present.  Frames of polygon-only entries are filled by `ops.fill_polygons`."""
         import torch
-        from . import ops
         if isinstance(values, str):
             if values not in ('label', 'dense'):
                 raise ValueError(f"values must be 'label', 'dense' or a list of one value per track, got {values!r}")
@@ -545,6 +593,11 @@ class TrackReader:
         forms = [is_compressed(segs[t]) for segs in self._segs if t in segs]
         return bool(forms) and all(forms)
 
+    def all_compressed(self):
+        """True when the file has an entry with counts and all of them are strings: what is rewritten from it keeps that form."""
+        forms = [is_compressed(c) for segs in self._segs for c in segs.values()]
+        return bool(forms) and all(forms)
+
     def _decode_lists(self, frames, table, out):
         from . import ops
         records = [self.record(t) for t in frames]
@@ -565,17 +618,10 @@ class TrackReader:
         return ops.rle_decode(record, self.height, self.width, n_rows, capacity, values=table, out=out)
 
     def _fill_polygons(self, frames, per_track, out):
-        """One `ops.fill_polygons` for the frames: every annotation owns a fixed run of rows - one under 'evenodd', under 'union' as
-        many as its longest ring list among these frames -, so one values table serves all of them; the host packs per vertex."""
+        """One `ops.fill_polygons` for the frames, every annotation owning a fixed run of rows (`pack_rows`); the host packs per vertex."""
         from . import ops
-        union = self.fill == 'union'
-        per = [[[] if polys.get(t) is None else [[r] for r in polys[t]] if union else [polys[t]] for t in frames] for polys in self._polys]
-        width = [max(len(rows) for rows in of_track) for of_track in per]
-        if not any(width):
-            width[0] = 1
-        batch = [[row for of_track, n in zip(per, width) for row in of_track[j] + [[]] * (n - len(of_track[j]))] for j in range(len(frames))]
-        values = [v for v, n in zip(per_track, width) for _ in range(n)]
-        return ops.fill_polygons(batch, self.height, self.width, values=values, out=out)
+        rows, values = pack_rows([[polys.get(t) for t in frames] for polys in self._polys], per_track, self.fill)
+        return ops.fill_polygons(rows, self.height, self.width, values=values, out=out)
 
 
 # what `ops.rle_decompress` says about a row (include/xmem_hip.h, xmem_rle_decompress)
@@ -583,11 +629,18 @@ STRING_STATUS = {1: 'the compressed counts are malformed', 2: 'the counts do not
                  3: 'the events of the frame do not fit the capacity'}
 
 
+def _load_doc(tracks):
+    """A tracks file, or a parsed document, -> a document that is the caller's to change."""
+    if isinstance(tracks, dict):
+        return json.loads(json.dumps(tracks))                        # a deep copy that keeps the order of the keys
+    return read_json(tracks)
+
+
 def recode_tracks(doc, counts):
     """A parsed tracks document with every entry's counts in the form `counts` ('list' | 'compressed'), by the host definitions, per
     count; everything else - and an entry that already has the form - is kept as it is."""
     check_count_form(counts)
-    doc = json.loads(json.dumps(doc))                                # a deep copy that keeps the order of the keys
+    doc = _load_doc(doc)
     for ann in doc.get('annotations', []):
         for seg in ann.get('segmentations', []):
             if seg is None or 'counts' not in seg:                   # a polygon-only entry has nothing to recode
@@ -625,77 +678,56 @@ def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
     return written
 
 
+def _rewrite_masks(reader, labels, values, op, batch):
+    """The pass behind the tools that change a file's masks -> document.  Per batch: `reader.masks_device` with the dense `values`
+    (row v of the record is `labels[v - 1]`) -> `op`, label maps to label maps on the device -> `ops.rle_encode`; no mask plane
+    reaches the host.  The counts are lists, or compressed strings when every entry of the input is one."""
+    from . import ops
+    names, writer = reader.frame_names(), TrackWriter(reader.height, reader.width)
+    k, step = len(labels), max(1, int(batch))
+    for frames in batches(range(len(reader) if k else 0), step):
+        masks, present = reader.masks_device(frames, values=values, batch=step)
+        meta, events = ops.rle_encode(op(masks), k)
+        for j, t in enumerate(frames):                               # without meta the frame has no mask
+            writer.add_frame(names[t], meta[j] if present[j] else None, events[j], labels=labels)
+    for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
+        writer.add_frame(names[t])
+    for lab in labels:                                               # a track without any entry still has its (empty) row
+        writer.open_track(lab)
+    doc = writer.to_dict()
+    return recode_tracks(doc, 'compressed') if reader.all_compressed() else doc
+
+
 def clean_tracks(tracks, spec, batch=32):
-    """A tracks file (or parsed document) with `ops.clean_masks` applied to every frame -> (document, totals of the four counters).
-    Per batch: `TrackReader.masks_device` (dense ids, one per track) -> `ops.clean_masks` -> `ops.rle_encode`; no mask plane reaches
-    the host, and boxes and areas are the encoder's, of the cleaned masks.  `spec`: what `mask_cleanup.parse_cleanup` returns.  The
-    counts are lists, or compressed strings when every entry of the input is one."""
+    """A tracks file (or parsed document) with `ops.clean_masks` applied to every frame -> (document, totals of the four counters),
+    by `_rewrite_masks` with dense ids in file order: boxes and areas are the encoder's, of the cleaned masks.  `spec`: what
+    `mask_cleanup.parse_cleanup` returns."""
     import torch
     from . import ops
     from .mask_cleanup import STATS
     reader = TrackReader(tracks)
-    if len(set(reader.labels)) != len(reader.labels):
-        raise ValueError('clean_tracks: two tracks share a label')
-    names = reader.file_names if len(reader.file_names) == len(reader) else [str(t) for t in range(len(reader))]
-    writer = TrackWriter(reader.height, reader.width)
-    k, step = len(reader.labels), max(1, int(batch))
-    totals = torch.zeros(len(STATS), dtype=torch.int64)
-    for i in range(0, len(reader) if k else 0, step):
-        frames = list(range(i, min(i + step, len(reader))))
-        dense, present = reader.masks_device(frames, values='dense', batch=step)
+    reader.require_unique_labels('clean_tracks')
+    counters = []                                                    # per batch, on the device: read when its record has arrived
+
+    def clean(dense):
         cleaned, stats = ops.clean_masks(dense, **spec)
-        meta, events = ops.rle_encode(cleaned, k)                    # waits for the record: the counters have arrived with it
-        totals += stats.sum(0, dtype=torch.int64).cpu()
-        for j, t in enumerate(frames):
-            if present[j]:
-                writer.add_frame(names[t], meta[j], events[j], labels=reader.labels)
-            else:
-                writer.add_frame(names[t])
-    for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
-        writer.add_frame(names[t])
-    for lab in reader.labels:                                        # a track without any entry still has its (empty) row
-        writer._tracks.setdefault(lab, {})
-    doc = writer.to_dict()
-    forms = [is_compressed(c) for segs in reader._segs for c in segs.values()]
-    if forms and all(forms):
-        doc = recode_tracks(doc, 'compressed')
+        counters.append(stats)
+        return cleaned
+    doc = _rewrite_masks(reader, reader.labels, 'dense', clean, batch)
+    totals = sum((stats.sum(0, dtype=torch.int64).cpu() for stats in counters), torch.zeros(len(STATS), dtype=torch.int64))
     return doc, dict(zip(STATS, (int(v) for v in totals.tolist())))
 
 
 def grow_tracks(tracks, r, batch=32):
     """A tracks file (or parsed document) with `ops.grow_masks` applied to every frame -> document: r > 0 grows every object by r
-    pixels into the background, r < 0 shrinks it (`matte.grow_host` has the definition).  Per batch: `TrackReader.masks_device` ->
-    `ops.grow_masks` -> `ops.rle_encode`; no mask plane reaches the host, and counts, boxes and areas are the encoder's, of the grown
-    masks.  The masks are decoded with dense ids in ascending order of the labels, so that a tie between two objects goes to the
-    smaller LABEL as the definition says; the tracks come out in that order.  The counts are lists, or compressed strings when
-    every entry of the input is one."""
+    pixels into the background, r < 0 shrinks it (`matte.grow_host` has the definition), by `_rewrite_masks`: counts, boxes and
+    areas are the encoder's, of the grown masks.  The masks are decoded with dense ids in ascending order of the labels, so that a
+    tie between two objects goes to the smaller LABEL as the definition says; the tracks come out in that order."""
     from . import ops
     reader = TrackReader(tracks)
-    if len(set(reader.labels)) != len(reader.labels):
-        raise ValueError('grow_tracks: two tracks share a label')
-    names = reader.file_names if len(reader.file_names) == len(reader) else [str(t) for t in range(len(reader))]
-    writer = TrackWriter(reader.height, reader.width)
+    reader.require_unique_labels('grow_tracks')
     labels = sorted(reader.labels)
-    dense = [labels.index(lab) + 1 for lab in reader.labels]
-    k, step = len(labels), max(1, int(batch))
-    for i in range(0, len(reader) if k else 0, step):
-        frames = list(range(i, min(i + step, len(reader))))
-        masks, present = reader.masks_device(frames, values=dense, batch=step)
-        meta, events = ops.rle_encode(ops.grow_masks(masks, r), k)
-        for j, t in enumerate(frames):
-            if present[j]:
-                writer.add_frame(names[t], meta[j], events[j], labels=labels)
-            else:
-                writer.add_frame(names[t])
-    for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
-        writer.add_frame(names[t])
-    for lab in labels:                                               # a track without any entry still has its (empty) row
-        writer._tracks.setdefault(lab, {})
-    doc = writer.to_dict()
-    forms = [is_compressed(c) for segs in reader._segs for c in segs.values()]
-    if forms and all(forms):
-        doc = recode_tracks(doc, 'compressed')
-    return doc
+    return _rewrite_masks(reader, labels, [labels.index(lab) + 1 for lab in reader.labels], lambda masks: ops.grow_masks(masks, r), batch)
 
 
 def polygon_tracks(tracks, spec=True, batch=32):
@@ -709,17 +741,11 @@ def polygon_tracks(tracks, spec=True, batch=32):
     spec = poly.parse_polygons(spec)
     if spec is None:
         raise ValueError('polygon_tracks: the option is off')
-    reader = TrackReader(tracks)
-    if isinstance(tracks, dict):
-        doc = json.loads(json.dumps(tracks))                         # a deep copy that keeps the order of the keys
-    else:
-        with open(tracks) as f:
-            doc = json.load(f)
-    if len(set(reader.labels)) != len(reader.labels):
-        raise ValueError('polygon_tracks: two tracks share a label')
+    doc = _load_doc(tracks)
+    reader = TrackReader(doc)
+    reader.require_unique_labels('polygon_tracks')
     k, step = len(reader.labels), max(1, int(batch))
-    for i in range(0, len(reader) if k else 0, step):
-        frames = list(range(i, min(i + step, len(reader))))
+    for frames in batches(range(len(reader) if k else 0), step):
         dense, _ = reader.masks_device(frames, values='dense', batch=step)
         meta, words = ops.mask_polygons(dense, k)
         for j, t in enumerate(frames):
@@ -729,13 +755,6 @@ def polygon_tracks(tracks, spec=True, batch=32):
                     seg['polygons'] = rings
     doc['videos'][0]['polygons'] = {'tolerance': spec['tolerance'], 'fill': 'evenodd'}
     return doc
-
-
-def _load_doc(tracks):
-    if isinstance(tracks, dict):
-        return json.loads(json.dumps(tracks))                        # a deep copy that keeps the order of the keys
-    with open(tracks) as f:
-        return json.load(f)
 
 
 def verify_polygons(tracks, batch=32):
@@ -752,19 +771,15 @@ def verify_polygons(tracks, batch=32):
     anns, k, step = doc['annotations'], len(reader.labels), max(1, int(batch))
     if k > 254:
         raise ValueError(f'verify_polygons: {k} tracks, at most 254 fit a launch')
-    union = reader.fill == 'union'
     both = [[t for t, seg in enumerate(ann['segmentations']) if seg is not None and 'counts' in seg and 'polygons' in seg] for ann in anns]
     todo = sorted({t for ts in both for t in ts})
     ious = [[] for _ in anns]
     bad_frames = set()
-    for i in range(0, len(todo), step):
-        frames = todo[i:i + step]
+    for frames in batches(todo, step):
         want, _ = reader.masks_device(frames, values='dense', batch=step)
-        per = [[[] if t not in both[a] else [[r] for r in ann['segmentations'][t]['polygons']] if union else [ann['segmentations'][t]['polygons']]
-                for t in frames] for a, ann in enumerate(anns)]
-        width = [max(1, max(len(rows) for rows in of_track)) for of_track in per]
-        rows = [[row for of_track, n in zip(per, width) for row in of_track[j] + [[]] * (n - len(of_track[j]))] for j in range(len(frames))]
-        got = ops.fill_polygons(rows, reader.height, reader.width, values=[a + 1 for a, n in enumerate(width) for _ in range(n)])
+        rows, values = pack_rows([[ann['segmentations'][t]['polygons'] if t in both[a] else None for t in frames] for a, ann in enumerate(anns)],
+                                 range(1, k + 1), reader.fill, least=1)
+        got = ops.fill_polygons(rows, reader.height, reader.width, values=values)
         counts = ops.jf_counts(want, got, 0)[:, 1:k + 1, :3].cpu().numpy().astype(np.int64)      # gt_area, pred_area, inter
         for j, t in enumerate(frames):
             for a in range(k):
@@ -789,16 +804,13 @@ def counts_from_polygons(tracks, batch=32):
     from . import ops
     doc = _load_doc(tracks)
     reader = TrackReader(doc)
-    if len(set(reader.labels)) != len(reader.labels):
-        raise ValueError('counts_from_polygons: two tracks share a label')
+    reader.require_unique_labels('counts_from_polygons')
     h, w, k, step = reader.height, reader.width, len(reader.labels), max(1, int(batch))
-    todo = [t for t in range(len(reader)) if reader.has_polygons(t)]
     for ann in doc['annotations']:
         for key in ('bboxes', 'areas'):
             if ann.get(key) is None:
                 ann[key] = [None] * len(reader)
-    for i in range(0, len(todo), step):
-        frames = todo[i:i + step]
+    for frames in batches([t for t in range(len(reader)) if reader.has_polygons(t)], step):
         dense, _ = reader.masks_device(frames, values='dense', batch=step)
         meta, events = ops.rle_encode(dense, k)
         for j, t in enumerate(frames):
@@ -806,10 +818,9 @@ def counts_from_polygons(tracks, batch=32):
                 seg = ann['segmentations'][t]
                 if seg is None:
                     continue
-                x0, y0, x1, y1 = (int(v) for v in row[2:6])
                 ann['segmentations'][t] = dict({'size': [h, w], 'counts': counts_from_events(ev, h, w)},
                                                **{key: v for key, v in seg.items() if key not in ('size', 'counts')})
-                ann['bboxes'][t] = [x0, y0, x1 - x0 + 1, y1 - y0 + 1] if int(row[1]) else [0, 0, 0, 0]
+                ann['bboxes'][t] = box_xywh(row) if int(row[1]) else [0, 0, 0, 0]
                 ann['areas'][t] = int(row[1])
     return doc
 
@@ -878,23 +889,16 @@ def main(argv=None):
     if args.from_labelme is not None:
         from .polygons import from_labelme
         doc = from_labelme(args.from_labelme)
-        if os.path.dirname(args.out):
-            os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        text = json.dumps(doc, separators=(',', ':'))
-        with open(args.out, 'w') as f:
-            f.write(text)
+        text = write_json(doc, args.out)
         print(json.dumps({'frames': doc['videos'][0]['length'], 'tracks': len(doc['annotations']), 'bytes': len(text), 'out': args.out}))
         return 0
     if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons or args.grow is not None:
-        report = {}
+        doc, report = _load_doc(args.tracks), {}
         if args.from_polygons:                                       # first: what follows reads counts
-            doc = counts_from_polygons(args.tracks)
+            doc = counts_from_polygons(doc)
             report['from_polygons'] = True
         if args.clean is not None:
-            doc, report['clean'] = clean_tracks(doc if args.from_polygons else args.tracks, args.clean)
-        elif not args.from_polygons:
-            with open(args.tracks) as f:
-                doc = json.load(f)
+            doc, report['clean'] = clean_tracks(doc, args.clean)
         if args.grow is not None:                                    # of the cleaned masks, when both are asked for
             doc = grow_tracks(doc, args.grow)
             report['grow'] = args.grow
@@ -904,12 +908,7 @@ def main(argv=None):
         if args.recode is not None:
             doc = recode_tracks(doc, args.recode)
             report['recode'] = args.recode
-        if os.path.dirname(args.out):
-            os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        text = json.dumps(doc, separators=(',', ':'))
-        with open(args.out, 'w') as f:
-            f.write(text)
-        print(json.dumps(dict(report, bytes=len(text), out=args.out)))
+        print(json.dumps(dict(report, bytes=len(write_json(doc, args.out)), out=args.out)))
         return 0
     written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty)
     print(json.dumps({'frames': len(written), 'out': args.out}))
