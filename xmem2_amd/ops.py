@@ -2086,3 +2086,55 @@ def grow_masks(masks, r, out=None):
     ws = workspace(lib.xmem_mask_grow_workspace_bytes(N, H, W), masks.device, 'matte')
     check(lib.xmem_mask_grow(ptr(masks), N, H, W, r2, int(shrink), ptr(out), ptr(ws), ws.numel(), stream_ptr()))
     return out
+
+
+# ---- temporal majority vote (csrc/temporal.hip, include/xmem_hip_temporal.h): integer, bit-reproducible ---------------------------
+
+def temporal_mode_ring(ring, T, t0, n, radius, flags, out=None, changed=None):
+    """`temporal.mode_host` of the frames t0 .. t0 + n - 1 of a video of T frames whose frame t lives in slot t % ring.shape[0] of
+    `ring`, uint8 [slots,H,W] on the device; `flags` uint8 [T] on that device (1 present, 2 locked: `temporal.frame_flags`).
+    -> (`out` uint8 [n,H,W] - a tensor of the caller's that does not overlap `ring`, or a new one -, `changed` int32 [n], likewise,
+    overwritten).  The ring must hold the frames max(0, t0 - radius) .. min(T - 1, t0 + n - 1 + radius) at once.  One launch on the
+    current stream, no synchronisation."""
+    from . import _lib_temporal
+    ring = _req_u8(ring, 'temporal_mode_ring', frames='slots')
+    if ring.dim() != 3 or ring.numel() == 0:
+        raise RuntimeError(f'temporal_mode_ring: expected a ring [slots,H,W], got {tuple(ring.shape)}')
+    slots, H, W = ring.shape
+    T = _int_arg('temporal_mode_ring', 'T', T, 1, 65535)
+    n = _int_arg('temporal_mode_ring', 'n', n, 1, T)
+    t0 = _int_arg('temporal_mode_ring', 't0', t0, 0, T - n)
+    radius = _int_arg('temporal_mode_ring', 'radius', radius, 1, _lib_temporal.MAX_R)
+    held = min(T - 1, t0 + n - 1 + radius) - max(0, t0 - radius) + 1
+    if slots < held:
+        raise ValueError(f'temporal_mode_ring: a ring of {slots} slots cannot hold the {held} frames that frames {t0}..{t0 + n - 1} read')
+    if not torch.is_tensor(flags) or flags.dtype != torch.uint8 or tuple(flags.shape) != (T,) or flags.device != ring.device \
+            or not flags.is_contiguous():
+        raise RuntimeError(f'temporal_mode_ring: flags must be a contiguous uint8 tensor [{T}] on the ring\'s device')
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=ring.device)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or out.device != ring.device \
+            or not out.is_contiguous():
+        raise RuntimeError(f'temporal_mode_ring: out must be a contiguous uint8 CUDA (HIP) tensor of shape {(n, H, W)} on the ring\'s device')
+    if changed is None:
+        changed = torch.empty(n, dtype=torch.int32, device=ring.device)
+    elif not torch.is_tensor(changed) or changed.dtype != torch.int32 or tuple(changed.shape) != (n,) or changed.device != ring.device \
+            or not changed.is_contiguous():
+        raise RuntimeError(f'temporal_mode_ring: changed must be a contiguous int32 tensor [{n}] on the ring\'s device')
+    check(_lib_temporal.load().xmem_temporal_mode(ptr(ring), slots, H, W, T, t0, n, radius, ptr(flags), ptr(out), ptr(changed),
+                                                  stream_ptr()))
+    return out, changed
+
+
+def temporal_mode(masks, radius, present=None, locked=None, out=None):
+    """`temporal.mode_host(masks, radius, present, locked)` on the device: `masks` uint8 [T,H,W], `present` and `locked` bool [T]
+    (sequences or arrays on the host; default all present, none locked) -> (`out` uint8 [T,H,W], a tensor of the caller's that does
+    not overlap `masks`, or a new one; `changed` int32 [T]).  One launch on the current stream, no synchronisation (the T flag bytes
+    are uploaded from pageable memory, as any small argument is)."""
+    from .temporal import frame_flags
+    masks = _req_u8(masks, 'temporal_mode', frames='T')
+    if masks.dim() != 3 or masks.numel() == 0:
+        raise RuntimeError(f'temporal_mode: expected masks [T,H,W], got {tuple(masks.shape)}')
+    T = masks.shape[0]
+    flags = torch.from_numpy(frame_flags(T, present, locked)).to(masks.device)
+    return temporal_mode_ring(masks, T, 0, T, radius, flags, out=_out_like(out, masks, 'temporal_mode'))

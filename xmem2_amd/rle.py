@@ -678,16 +678,25 @@ def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
     return written
 
 
-def _rewrite_masks(reader, labels, values, op, batch):
+def _rewrite_masks(reader, labels, values, op, batch, halo=0):
     """The pass behind the tools that change a file's masks -> document.  Per batch: `reader.masks_device` with the dense `values`
     (row v of the record is `labels[v - 1]`) -> `op`, label maps to label maps on the device -> `ops.rle_encode`; no mask plane
-    reaches the host.  The counts are lists, or compressed strings when every entry of the input is one."""
+    reaches the host.  The counts are lists, or compressed strings when every entry of the input is one.
+    `halo` > 0, for an `op` that looks along time: a batch is decoded with up to `halo` frames of the FILE on either side (fewer at
+    the ends of the video) and `op(masks, present, at, n)` returns the new maps of the n frames from index `at` of what it was given."""
     from . import ops
     names, writer = reader.frame_names(), TrackWriter(reader.height, reader.width)
     k, step = len(labels), max(1, int(batch))
     for frames in batches(range(len(reader) if k else 0), step):
-        masks, present = reader.masks_device(frames, values=values, batch=step)
-        meta, events = ops.rle_encode(op(masks), k)
+        if halo:
+            span = list(range(max(0, frames[0] - halo), min(len(reader), frames[-1] + 1 + halo)))
+            masks, around = reader.masks_device(span, values=values, batch=len(span))
+            at = frames[0] - span[0]
+            new, present = op(masks, around, at, len(frames)), around[at:at + len(frames)]
+        else:
+            masks, present = reader.masks_device(frames, values=values, batch=step)
+            new = op(masks)
+        meta, events = ops.rle_encode(new, k)
         for j, t in enumerate(frames):                               # without meta the frame has no mask
             writer.add_frame(names[t], meta[j] if present[j] else None, events[j], labels=labels)
     for t in range(len(writer.file_names), len(reader)):             # a file without tracks: its frames, nothing else
@@ -728,6 +737,38 @@ def grow_tracks(tracks, r, batch=32):
     reader.require_unique_labels('grow_tracks')
     labels = sorted(reader.labels)
     return _rewrite_masks(reader, labels, [labels.index(lab) + 1 for lab in reader.labels], lambda masks: ops.grow_masks(masks, r), batch)
+
+
+def smooth_tracks(tracks, radius, locked=(), batch=32):
+    """A tracks file (or parsed document) with every mask replaced by the majority vote over the frames within `radius` of it
+    (`temporal.mode_host` has the definition) -> (document, pixels changed per frame), by `_rewrite_masks` with dense ids in file
+    order and a halo of `radius` frames round every batch, so that a batch boundary does not show.  `locked`: frame indices that
+    vote but stay as they are (the annotated ones); a frame without a mask neither votes nor changes."""
+    import torch
+    from . import ops
+    from .temporal import MAX_R, frame_flags
+    reader = TrackReader(tracks)
+    reader.require_unique_labels('smooth_tracks')
+    locked = sorted({int(t) for t in locked})
+    if locked and not 0 <= locked[0] <= locked[-1] < len(reader):
+        raise ValueError(f'smooth_tracks: locked frames {locked} outside 0..{len(reader) - 1}')
+    radius = ops._int_arg('smooth_tracks', 'radius', radius, 1, MAX_R)
+    is_locked = np.zeros(len(reader), bool)
+    is_locked[locked] = True
+    counters, first = [], []                                         # per batch, on the device: read when its record has arrived
+
+    def vote(masks, present, at, n):
+        start = sum(m for _, m in first)                             # the frame the batch starts at: batches come in order
+        first.append((start, n))
+        flags = torch.from_numpy(frame_flags(len(present), present, is_locked[start - at:start - at + len(present)])).to(masks.device)
+        out, changed = ops.temporal_mode_ring(masks, len(present), at, n, radius, flags)
+        counters.append(changed)
+        return out
+    doc = _rewrite_masks(reader, reader.labels, 'dense', vote, batch, halo=radius)
+    changed = [0] * len(reader)
+    for (start, n), c in zip(first, counters):
+        changed[start:start + n] = [int(v) for v in c.cpu().tolist()]
+    return doc, changed
 
 
 def polygon_tracks(tracks, spec=True, batch=32):
@@ -855,6 +896,11 @@ def parse_args(argv=None):
     ap.add_argument('--polygons', nargs='?', const=0.0, default=None, type=float, metavar='TOL',
                     help='write no PNGs: rewrite the file with the polygon outlines of every entry added (key "polygons"), traced on '
                          'the device (needs the GPU); TOL > 0 simplifies every ring (Ramer-Douglas-Peucker, lossy)')
+    ap.add_argument('--smooth', default=None, type=int, metavar='R',
+                    help='write no PNGs: rewrite the file with every mask replaced by the majority vote over the frames within R of it '
+                         '(1 <= R <= 7; needs the GPU); a step of its own, not to be combined with the others')
+    ap.add_argument('--lock', default=None, metavar='FRAMES',
+                    help='with --smooth: frame indices, e.g. 0,17,40, that vote but are written as they are (the annotated frames)')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
     args = ap.parse_args(argv)
@@ -869,6 +915,20 @@ def parse_args(argv=None):
     if args.from_labelme is not None and (args.verify_polygons or args.from_polygons or args.clean or args.recode or args.polygons is not None
                                           or args.grow is not None):
         ap.error('--from-labelme writes the polygon-only file and nothing else: run the other steps on that file')
+    if args.smooth is not None:
+        from .temporal import MAX_R
+        if not 1 <= args.smooth <= MAX_R:
+            ap.error(f'--smooth: 1 <= R <= {MAX_R} is needed')
+        if (args.verify_polygons or args.from_polygons or args.from_labelme is not None or args.clean or args.recode
+                or args.polygons is not None or args.grow is not None):
+            ap.error('--smooth is a step of its own: run --clean, --grow, --polygons, --recode and the polygon steps on the file it writes')
+    if args.lock is not None:
+        if args.smooth is None:
+            ap.error('--lock goes with --smooth')
+        try:
+            args.lock = [int(v) for v in args.lock.split(',') if v.strip()]
+        except ValueError:
+            ap.error('--lock: frame indices separated by commas are needed, e.g. 0,17,40')
     if args.clean is not None:
         from .mask_cleanup import parse_cleanup
         try:
@@ -891,6 +951,11 @@ def main(argv=None):
         doc = from_labelme(args.from_labelme)
         text = write_json(doc, args.out)
         print(json.dumps({'frames': doc['videos'][0]['length'], 'tracks': len(doc['annotations']), 'bytes': len(text), 'out': args.out}))
+        return 0
+    if args.smooth is not None:
+        doc, changed = smooth_tracks(args.tracks, args.smooth, locked=args.lock or ())
+        report = {'smooth': args.smooth, 'pixels_changed': sum(changed), 'frames_changed': sum(1 for c in changed if c)}
+        print(json.dumps(dict(report, bytes=len(write_json(doc, args.out)), out=args.out)))
         return 0
     if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons or args.grow is not None:
         doc, report = _load_doc(args.tracks), {}

@@ -436,6 +436,35 @@ def _parse_mattes(config):
     return parse_mattes(config['mattes'])
 
 
+def _parse_smooth(config):
+    """config['temporal_smooth'] as `temporal.parse_smooth` returns it; None without the key - nothing is imported for it then"""
+    if config.get('temporal_smooth') is None:
+        return None
+    from .temporal import parse_smooth
+    return parse_smooth(config['temporal_smooth'])
+
+
+def _with_smoothing(spec, outputs, vid_length, device):
+    """config['temporal_smooth']: `outputs` behind a delay line that hands every frame on as the majority vote over its neighbours in
+    time; `outputs` itself without the option - nothing is imported, allocated or launched for it then.  The vote comes after
+    `_clean_output` and before everything `_FrameOutputs` does; the probabilities that go back into the memory are not touched, so
+    propagation is the same with and without the option."""
+    if spec is None:
+        return outputs
+    from .temporal import DelayLine
+    return DelayLine(outputs, spec, vid_length, device)
+
+
+def _with_smooth_report(df, outputs, say=False):
+    """config['temporal_smooth']: the radius and the video's changed pixels and frames in `df.attrs['temporal_smooth']` (one transfer,
+    after the loop)"""
+    if hasattr(outputs, 'report'):
+        df.attrs['temporal_smooth'] = outputs.report()
+        if say:
+            print('TEMPORAL SMOOTHING: ' + ', '.join(f'{k.replace("_", " ")} {v}' for k, v in df.attrs['temporal_smooth'].items()))
+    return df
+
+
 class _MatteLoop:
     """config['mattes'] inside a frame loop: one `ops.mask_mattes` launch sequence per frame on the compute stream, right behind the
     clean-up, on the index mask the loop hands on (cleaned, at the original resolution).  The planes - uint8 [T, K, H, W], one per table
@@ -685,6 +714,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
     cleanup = parse_cleanup(config.get('mask_cleanup'))              # opt-in (default: absent): despeckle / fill holes / keep largest
     mattes = _parse_mattes(config)                                   # opt-in (default: absent): feathered mattes / trimaps per label
+    smooth = _parse_smooth(config)                                   # opt-in (default: absent): a majority vote over time
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
@@ -746,6 +776,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
+    outputs = _with_smoothing(smooth, outputs, vid_length, device)
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -778,7 +809,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps)
+    return _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
 
 
 def _with_cleanup(df, totals, say=False):
@@ -916,6 +947,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     passes = parse_ensemble(config.get('ensemble'), config['size'])
     cleanup = parse_cleanup(config.get('mask_cleanup'))
     mattes = _parse_mattes(config)
+    smooth = _parse_smooth(config)
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
@@ -983,6 +1015,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
+    outputs = _with_smoothing(smooth, outputs, vid_length, device)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):
@@ -1033,7 +1066,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps)
+    return _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),

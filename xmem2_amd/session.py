@@ -452,6 +452,31 @@ class VideoSession:
             for i in range(0, len(self), step):
                 self.masks[i:i + step].copy_(ops.grow_masks(self.masks[i:i + step], r))
 
+    def smooth(self, radius, batch=32):
+        """`ops.temporal_mode` on the masks as they stand, in place of what they held: every frame becomes the majority vote over the
+        frames within `radius` of it (1..7; `temporal.mode_host` has the definition).  The references vote but stay as they are, a
+        frame without a mask neither votes nor changes.  The vote runs `batch` frames per launch and every batch reads unsmoothed
+        frames: a batch is written back only when no later one reads it, so the result does not depend on `batch`.  Returns the
+        number of pixels changed per frame.  The session does not read config['temporal_smooth'] - `propagate` visits frames in
+        either direction and in parts, so there is no one delay line to hold: this method is its surface."""
+        from .temporal import frame_flags
+        T, step = len(self), max(1, int(batch))
+        locked = [t in set(self.references) for t in range(T)]
+        flags = torch.from_numpy(frame_flags(T, self._present, locked)).to(self.device)
+        changed = torch.empty(T, dtype=torch.int32, device=self.device)
+        waiting = []                                                     # (first frame, smoothed batch) a later batch still reads under
+        with torch.cuda.device(self.device):
+            for i in range(0, T, step):
+                n = min(step, T - i)
+                out, _ = ops.temporal_mode_ring(self.masks, T, i, n, radius, flags, changed=changed[i:i + n])
+                waiting.append((i, out))
+                while waiting and waiting[0][0] + waiting[0][1].shape[0] <= i + n - radius:
+                    at, done = waiting.pop(0)
+                    self.masks[at:at + done.shape[0]].copy_(done)
+            for at, done in waiting:
+                self.masks[at:at + done.shape[0]].copy_(done)
+        return [int(v) for v in changed.cpu().tolist()]
+
     # ---- candidates ----------------------------------------------------------------------------------------------------
     def mask_table(self, mask_form='objects'):
         """float32[256] on the host: the selector's mask value of a DENSE id.  'objects': any object 1.0 (the GUI's masks);
