@@ -240,10 +240,11 @@ def plane_job(names, labels, planes, stem):
     return job
 
 
-def write_mattes(masks_of, n_frames, stems, labels, out_dir, spec, batch=32):
+def write_mattes(masks_of, n_frames, stems, labels, out_dir, spec, batch=32, png_on_device=False):
     """`ops.mask_mattes` over `n_frames` frames in launches of at most `batch`, written under `out_dir`.  masks_of(frames) ->
     (uint8 device tensor [len(frames), H, W] of dense ids 1..len(labels), present bool per frame); a frame that is not present gets
-    no file.  Returns the number of files."""
+    no file.  `png_on_device`: the planes of a launch are encoded as 'grey' PNGs on the device in one `ops.png_encode` call and the
+    files' bytes reach the host, not the planes.  Returns the number of files."""
     import torch
     from . import ops
     from .rle import batches
@@ -258,17 +259,27 @@ def write_mattes(masks_of, n_frames, stems, labels, out_dir, spec, batch=32):
                 continue
             if tables_dev is None:
                 tables_dev = torch.from_numpy(tables).to(dense.device)
-            planes = ops.mask_mattes(dense, k, tables_dev, R).cpu().numpy()         # [T, N, K, H, W]
+            planes = ops.mask_mattes(dense, k, tables_dev, R)                       # [T, N, K, H, W]
+            if png_on_device:
+                from .png import bytes_job, plane_files
+                files = ops.png_encode(planes.reshape((-1,) + tuple(planes.shape[-2:])), 'grey')
+                n = len(frames)
+            else:
+                planes = planes.cpu().numpy()
             for j, t in enumerate(frames):
                 if present[j]:
-                    saver.submit(plane_job(names, labels, planes[:, j], stems[t]))
+                    if png_on_device:
+                        mine = [files[(i * n + j) * k + c] for i in range(len(names)) for c in range(k)]
+                        saver.submit(bytes_job(plane_files(names, labels, mine, stems[t])))
+                    else:
+                        saver.submit(plane_job(names, labels, planes[:, j], stems[t]))
                     written += len(names) * k
     finally:
         saver.close()
     return written
 
 
-def matte_tracks(tracks, out_dir, spec, batch=32):
+def matte_tracks(tracks, out_dir, spec, batch=32, png_on_device=False):
     """The planes of every entry of a tracks file, decoded on the device (`TrackReader.masks_device`): <label> is the track's label."""
     from .rle import TrackReader
     reader = TrackReader(tracks)
@@ -277,7 +288,7 @@ def matte_tracks(tracks, out_dir, spec, batch=32):
 
     def masks_of(frames):
         return reader.masks_device(frames, values='dense', batch=max(1, int(batch)))
-    return write_mattes(masks_of, len(reader), stems, list(reader.labels), out_dir, spec, batch)
+    return write_mattes(masks_of, len(reader), stems, list(reader.labels), out_dir, spec, batch, png_on_device)
 
 
 def _colour_keys(rgb):
@@ -285,7 +296,7 @@ def _colour_keys(rgb):
     return rgb[..., 0] << 16 | rgb[..., 1] << 8 | rgb[..., 2]
 
 
-def matte_pngs(mask_dir, out_dir, spec, batch=32, palette_from=None):
+def matte_pngs(mask_dir, out_dir, spec, batch=32, palette_from=None, png_on_device=False):
     """The planes of a directory of mask PNGs; <label> runs over the labels that occur in any of them, in ascending order.  Index
     PNGs (mode P or L, as `python -m xmem2_amd.rle --out DIR` writes them): the pixel values are the labels.  Colour PNGs (mode RGB,
     as run_on_video writes them): `palette_from` names a palette PNG - an annotation - and a colour is the first index that has it;
@@ -323,7 +334,7 @@ def matte_pngs(mask_dir, out_dir, spec, batch=32, palette_from=None):
 
     def masks_of(frames):
         return torch.from_numpy(np.stack([lut[masks[t]] for t in frames])).to(device), [True] * len(frames)
-    return write_mattes(masks_of, len(files), [os.path.splitext(f)[0] for f in files], labels, out_dir, spec, batch)
+    return write_mattes(masks_of, len(files), [os.path.splitext(f)[0] for f in files], labels, out_dir, spec, batch, png_on_device)
 
 
 def parse_args(argv=None):
@@ -341,6 +352,7 @@ def parse_args(argv=None):
     ap.add_argument('--offset', type=float, default=0.0, metavar='O', help='moves the edge outwards (> 0, spread) or inwards (< 0, choke)')
     ap.add_argument('--falloff', default='linear', choices=FALLOFFS)
     ap.add_argument('--trimap', type=float, default=None, metavar='T', help='also write trimaps with an unknown band of T pixels either side')
+    ap.add_argument('--png-on-device', action='store_true', help='build the PNG files on the device: their bytes reach the host, not the planes')
     args = ap.parse_args(argv)
     if (args.tracks is None) == (args.masks is None):
         ap.error('exactly one of --tracks and --masks is needed')
@@ -360,9 +372,9 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     if args.tracks is not None:
-        written = matte_tracks(args.tracks, args.out, args.spec)
+        written = matte_tracks(args.tracks, args.out, args.spec, png_on_device=args.png_on_device)
     else:
-        written = matte_pngs(args.masks, args.out, args.spec, palette_from=args.palette_from)
+        written = matte_pngs(args.masks, args.out, args.spec, palette_from=args.palette_from, png_on_device=args.png_on_device)
     print(json.dumps({'files': written, 'out': args.out}))
     return 0
 

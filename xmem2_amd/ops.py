@@ -2138,3 +2138,66 @@ def temporal_mode(masks, radius, present=None, locked=None, out=None):
     T = masks.shape[0]
     flags = torch.from_numpy(frame_flags(T, present, locked)).to(masks.device)
     return temporal_mode_ring(masks, T, 0, T, radius, flags, out=_out_like(out, masks, 'temporal_mode'))
+
+
+# ---- PNG files built on the device (csrc/png.hip, include/xmem_hip_png.h): integer, bit-reproducible ------------------------------
+
+PNG_STATS = {'launches': 0, 'retries': 0}      # calls of xmem_png_encode / frames encoded again because their file did not fit
+
+
+def _png_table(t, shape, device, what):
+    """a table of png_encode on the device: a uint8 tensor or array of `shape`, or None"""
+    if t is None:
+        return None
+    if not torch.is_tensor(t):
+        import numpy as np
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if t.dtype != torch.uint8 or tuple(t.shape) != shape:
+        raise ValueError(f'png_encode: {what} must be uint8 {list(shape)}')
+    return t.to(device).contiguous()
+
+
+def png_encode(planes, mode, table=None, palette=None, capacity=None, wait=True):
+    """`png.encode_host(plane, mode, table, palette)` of uint8 planes [H,W] or [N,H,W] on the device, byte for byte.  `mode`: 'grey'
+    (`table`: an optional uint8 [256] byte map), 'palette' (`table`: the byte map, `palette`: uint8 [256, 3]) or 'rgb' (`table`: uint8
+    [256, 3]); tables are tensors on the planes' device, or host arrays that are uploaded.  `capacity`: bytes per file there is room
+    for (default `png.default_capacity`).  wait=False: one launch sequence on the current stream and no synchronisation; returns the
+    uint8 device tensor `png.split_record(., N, capacity)` takes apart, whose meta holds every file's true length.  wait=True: returns
+    a list of N `bytes` on the HOST; a frame whose file did not fit is encoded again at its true length - nothing is ever cut off."""
+    from . import _lib_png, png
+    if mode not in png.MODES:
+        raise ValueError(f'png_encode: mode = {mode!r}: expected one of {sorted(png.MODES)}')
+    planes = _req_u8(planes, 'png_encode', frames='N')
+    N, H, W = _map_dims(planes, 'png_encode')
+    _frames_fit(N, 'png_encode')
+    if H > png.MAX_SIDE or W > png.MAX_SIDE:
+        raise ValueError(f'png_encode: planes of {H} x {W}: at most {png.MAX_SIDE} on a side')
+    channels = png.MODES[mode][1]
+    if table is None and mode != 'grey':
+        raise ValueError(f'png_encode: mode {mode!r} needs a table')
+    if (palette is not None) != (mode == 'palette'):
+        raise ValueError("png_encode: mode 'palette', and no other, takes a palette")
+    table = _png_table(table, (256,) if channels == 1 else (256, 3), planes.device, f'the table of mode {mode!r}')
+    palette = _png_table(palette, (256, 3), planes.device, 'the palette')
+    capacity = png.default_capacity(H, W, mode) if capacity is None else _int_arg('png_encode', 'capacity', capacity, 1, _lib_png.MAX_CAPACITY)
+    lib = _lib_png.load()
+    rec = torch.empty(png.record_bytes(N, capacity), dtype=torch.uint8, device=planes.device)
+    ws = workspace(lib.xmem_png_workspace_bytes(N, H, W, channels), planes.device, 'png')
+    PNG_STATS['launches'] += 1
+    check(lib.xmem_png_encode(ptr(planes), N, H, W, _lib_png.COLOR_TYPES[mode], ptr(table), ptr(palette), capacity, ptr(rec),
+                              C.c_void_p(rec.data_ptr() + 4 * png.META * N), ptr(ws), ws.numel(), stream_ptr()))
+    if not wait:
+        return rec
+    meta, data = png.split_record(rec.cpu().numpy(), N, capacity)
+    files = []
+    for n in range(N):
+        length = int(meta[n, 0])
+        if length > capacity:                                        # the length is the true one: once more, with room for all of it
+            PNG_STATS['retries'] += 1
+            again = png_encode(planes[n] if planes.dim() == 3 else planes, mode, table, palette, capacity=length)[0]
+            if len(again) != length:
+                raise RuntimeError('png_encode: a frame encoded again gave another length')
+            files.append(again)
+        else:
+            files.append(data[n, :length].tobytes())
+    return files

@@ -653,10 +653,40 @@ def recode_tracks(doc, counts):
     return doc
 
 
-def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True):
+def _tracks_to_pngs_on_device(tracks, out_dir, palette_from, empty_frames, batch=32):
+    """`tracks_to_pngs` with the masks decoded and the PNGs built on the device (`TrackReader.masks_device`, `ops.png_encode`): no mask
+    plane reaches the host.  Mode L, or mode P with all 256 entries of the palette, the ones the palette PNG lacks being zeros."""
+    import torch
+    from . import ops
+    reader = TrackReader(tracks)
+    mode, table, palette = 'grey', None, None
+    if palette_from is not None:
+        from PIL import Image
+        raw = Image.open(palette_from).convert('P').getpalette() or []
+        pal = np.zeros(768, np.uint8)
+        pal[:min(len(raw), 768)] = raw[:768]
+        device = torch.device('cuda', torch.cuda.current_device())
+        mode, table, palette = 'palette', torch.arange(256, device=device).to(torch.uint8), torch.from_numpy(pal.reshape(256, 3)).to(device)
+    os.makedirs(out_dir, exist_ok=True)
+    names, written = reader.frame_names(), []
+    for frames in batches(range(len(reader)), batch):
+        dev, present = reader.masks_device(frames, values='label', batch=max(1, int(batch)))
+        for t, ok, data in zip(frames, present, ops.png_encode(dev, mode, table, palette)):
+            if not ok and not empty_frames:
+                continue
+            path = os.path.join(out_dir, os.path.splitext(names[t])[0] + '.png')
+            with open(path, 'wb') as fh:
+                fh.write(data)
+            written.append(path)
+    return written
+
+
+def tracks_to_pngs(tracks, out_dir, palette_from=None, empty_frames=True, png_on_device=False):
     """Write every frame of tracks.json as an index PNG `<out_dir>/<frame>.png` whose pixel values are the tracks' labels (mode P with
     the palette of the PNG `palette_from`, else mode L).  A frame without any entry is written all zero (`empty_frames`) or left out.
-    Returns the written paths."""
+    `png_on_device`: decode and encode on the device; the files open to the same mode, size and pixels.  Returns the written paths."""
+    if png_on_device:
+        return _tracks_to_pngs_on_device(tracks, out_dir, palette_from, empty_frames)
     from PIL import Image
     video, masks = read_tracks(tracks)
     palette = None
@@ -903,6 +933,7 @@ def parse_args(argv=None):
                     help='with --smooth: frame indices, e.g. 0,17,40, that vote but are written as they are (the annotated frames)')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
+    ap.add_argument('--png-on-device', action='store_true', help='with --out DIR: decode the masks and build the PNG files on the device')
     args = ap.parse_args(argv)
     if args.polygons is not None and not (0 <= args.polygons < float('inf')):
         ap.error('--polygons: the tolerance must be a finite number >= 0')
@@ -975,7 +1006,7 @@ def main(argv=None):
             report['recode'] = args.recode
         print(json.dumps(dict(report, bytes=len(write_json(doc, args.out)), out=args.out)))
         return 0
-    written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty)
+    written = tracks_to_pngs(args.tracks, args.out, args.palette_from, empty_frames=not args.skip_empty, png_on_device=args.png_on_device)
     print(json.dumps({'frames': len(written), 'out': args.out}))
     return 0
 

@@ -191,12 +191,16 @@ class _AsyncSaver:
                 for img, sub, name in job():
                     d = os.path.join(self.root, sub)
                     os.makedirs(d, exist_ok=True)
+                    if isinstance(img, bytes):                       # a finished file (config['png_on_device'])
+                        with open(os.path.join(d, name), 'wb') as fh:
+                            fh.write(img)
+                        continue
                     img.save(os.path.join(d, name), **({'compress_level': 1} if name.endswith('.png') else {}))
             except Exception as e:                                   # surfaced by close()
                 self.err = e
 
     def submit(self, job):
-        """job() -> iterable of (PIL image, sub-directory, file name); runs on a writer thread."""
+        """job() -> iterable of (PIL image or the bytes of a finished file, sub-directory, file name); runs on a writer thread."""
         self.q.put(job)
 
     def close(self):
@@ -472,11 +476,14 @@ class _MatteLoop:
     (their own AsyncMaskFetcher) and written by `_AsyncSaver` threads as <masks_out_path>/mattes/<label>/<frame>.png and, with a
     trimap, <masks_out_path>/trimaps/<label>/<frame>.png, 8-bit mode L, <label> the annotation's label as in tracks.json.  Masks,
     tracks and what goes back into the memory are not touched.  `saver`: the loop's, or None - then the planes get writers of
-    their own, closed with the loop."""
+    their own, closed with the loop.  `png_on_device` (config['png_on_device']): the T x K planes of a frame are encoded as 'grey' PNGs in
+    one `ops.png_encode` call right behind the look-up and the files' bytes travel, not the planes; a frame with a file that did not
+    fit is encoded again when its record arrives, and the frames after it get twice that room."""
 
-    def __init__(self, spec, saver, masks_out_path, vid_name=''):
+    def __init__(self, spec, saver, masks_out_path, vid_name='', png_on_device=False):
         from .matte import tables_of
         self.names, self._tables, self.R = tables_of(spec)
+        self.png_on_device, self.capacity = bool(png_on_device), None
         self.own_saver = _AsyncSaver(masks_out_path, vid_name) if saver is None else None
         self.saver = self.own_saver if saver is None else saver
         self.tables = None                                           # on the device, from the first frame on
@@ -488,7 +495,14 @@ class _MatteLoop:
             return []
         if self.tables is None:
             self.tables = torch.from_numpy(self._tables).to(mask_dev.device)
-        return self.fetcher.submit((tag, k), ops.mask_mattes(mask_dev, k, self.tables, self.R))
+        planes = ops.mask_mattes(mask_dev, k, self.tables, self.R)
+        if not self.png_on_device:
+            return self.fetcher.submit((tag, k), planes)
+        from .png import default_capacity
+        if self.capacity is None:
+            self.capacity = default_capacity(*planes.shape[-2:], 'grey')
+        planes = planes.reshape((-1,) + tuple(planes.shape[-2:]))
+        return self.fetcher.submit((tag, k, planes, self.capacity), ops.png_encode(planes, 'grey', capacity=self.capacity, wait=False))
 
     def drain(self):
         return self.fetcher.drain()
@@ -496,12 +510,81 @@ class _MatteLoop:
     def finish(self, item, mapper):
         from .matte import plane_job
         from .rle import inverse_labels
+        if self.png_on_device:
+            from .png import bytes_job, files_of_record, plane_files
+            ((sample, _), k, planes_dev, capacity), buf = item
+
+            def again(n, length):
+                ops.PNG_STATS['retries'] += 1
+                return ops.png_encode(planes_dev[n], 'grey', capacity=length)[0]
+
+            def grow(length):
+                self.capacity = max(self.capacity, 2 * length)
+            files = files_of_record(buf, planes_dev.shape[0], capacity, again, grow)
+            self.saver.submit(bytes_job(plane_files(self.names, inverse_labels(mapper, k), files, sample.frame[:-4])))
+            return
         ((sample, _), k), planes = item
         self.saver.submit(plane_job(self.names, inverse_labels(mapper, k), planes, sample.frame[:-4]))
 
     def close(self):
         if self.own_saver is not None:
             self.own_saver.close()                                   # re-raises a writer's error
+
+
+def _parse_png(config):
+    """config['png_on_device'] as `png.parse_option` returns it; None without the key - nothing is imported for it then"""
+    if config.get('png_on_device') is None:
+        return None
+    from .png import parse_option
+    return parse_option(config['png_on_device'])
+
+
+class _PngLoop:
+    """config['png_on_device'] inside a frame loop: one `ops.png_encode` launch sequence per frame on the compute stream, on the index
+    mask the loop hands on (behind the clean-up and the delay line), the record - meta and `capacity` bytes - delivered through pinned
+    memory one frame behind like the mask (its own AsyncMaskFetcher, fed before the mask's: when a frame's mask has arrived, so has its
+    file).  mode 'rgb': the colours `map_the_colors_back` gives the labels as of that frame, so masks/<frame>.png opens to what the
+    host path writes; 'palette': the index PNG with the annotation's palette.  The tables are made per label map and stay on the
+    device.  A frame whose file did not fit is encoded again at its true length when its record arrives, and the frames after it get
+    twice that room.  `mask_dev` must stay untouched until then."""
+
+    def __init__(self, spec, reader):
+        self.mode, self.reader = spec['mode'], reader
+        self.capacity = None                                         # made for the first frame's size
+        self._tables = {}                                            # label map -> (table, palette) on the device
+        self.fetcher = AsyncMaskFetcher()
+
+    def _device_tables(self, mapper, device):
+        from .png import label_map, mask_tables
+        key = label_map(mapper).tobytes()
+        if key not in self._tables:
+            self._tables[key] = tuple(None if t is None else torch.from_numpy(t).to(device) for t in mask_tables(self.reader, mapper, self.mode))
+        return self._tables[key]
+
+    def submit(self, tag, mask_dev, mapper):
+        """-> the (tag, record) pairs that have arrived"""
+        if self.capacity is None:
+            from .png import default_capacity
+            self.capacity = default_capacity(*mask_dev.shape, self.mode)
+        table, palette = self._device_tables(mapper, mask_dev.device)
+        rec = ops.png_encode(mask_dev, self.mode, table, palette, capacity=self.capacity, wait=False)
+        return self.fetcher.submit((tag, mask_dev, table, palette, self.capacity), rec)
+
+    def drain(self):
+        return self.fetcher.drain()
+
+    def finish(self, item):
+        """-> (the frame's name, the bytes of its file)"""
+        from .png import files_of_record
+        (tag, mask_dev, table, palette, capacity), buf = item
+
+        def again(n, length):
+            ops.PNG_STATS['retries'] += 1
+            return ops.png_encode(mask_dev, self.mode, table, palette, capacity=length)[0]
+
+        def grow(length):
+            self.capacity = max(self.capacity, 2 * length)           # the frames to come get room for a video as ragged as this
+        return tag[0].frame, files_of_record(buf, 1, capacity, again, grow)[0]
 
 
 def _working_u8(src_u8, target_hw, device, flip=False):
@@ -594,13 +677,19 @@ def _stats_row(frame, had_mask, compute_iou, out_mask=None, gt=None):
     return stat
 
 
-def _saver_job(reader, ids, frame, overlay_image=None):
+def _saver_job(reader, ids, frame, overlay_image=None, png=None):
     """The _AsyncSaver job that colour-maps the index mask `ids` and yields <frame>.png and, when `overlay_image() -> PIL image` is
-    given, the overlay <frame>.jpg on it."""
+    given, the overlay <frame>.jpg on it.  `png`: the bytes of <frame>.png, built on the device; the colours are then made for the
+    overlay alone, and without an overlay `ids` is not looked at."""
     def job():
         from PIL import Image
+        if png is not None:
+            yield png, 'masks', frame[:-4] + '.png'
+            if overlay_image is None:
+                return
         out_img = reader.map_the_colors_back(Image.fromarray(ids))
-        yield out_img, 'masks', frame[:-4] + '.png'
+        if png is None:
+            yield out_img, 'masks', frame[:-4] + '.png'
         if overlay_image is not None:
             yield _overlay(overlay_image(), out_img), 'overlay', frame[:-4] + '.jpg'
     return job
@@ -614,20 +703,23 @@ class _FrameOutputs:
     its record arrives, gets a copy."""
 
     def __init__(self, reader, mapper, fetcher, saver=None, tracks=None, scorer=None, compute_iou=False, save_overlay=True,
-                 masks_out_path=None, reused_output=False, mattes=None):
+                 masks_out_path=None, reused_output=False, mattes=None, pngs=None):
         self.reader, self.mapper, self.fetcher, self.saver, self.tracks, self.scorer = reader, mapper, fetcher, saver, tracks, scorer
         self.mattes = mattes                                         # config['mattes']: a _MatteLoop, None without the option
+        self.pngs = pngs if saver is not None else None              # config['png_on_device']: a _PngLoop, None without the option
         self.compute_iou, self.save_overlay, self.masks_out_path, self.reused_output = compute_iou, save_overlay, masks_out_path, reused_output
         # the H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou
         self.need_mask = tracks is None or saver is not None or compute_iou
+        if self.pngs is not None:                                    # the files come from the device: only the overlays and compute_iou read it
+            self.need_mask = save_overlay or compute_iou
         self.stats = []
         self._arrived = ((), ())
         self._matted = ()
+        self._encoded = ()
 
-    @staticmethod
-    def _tags(tdone):
-        """tracks only: the frames whose record arrived stand in for the masks that were never copied"""
-        return [(it[0][0], None) for it in tdone]
+    def _tags(self, tdone):
+        """no mask travels: the frames whose track record or PNG record arrived stand in for the masks that were never copied"""
+        return [(it[0][0], None) for it in (tdone if self.tracks is not None else self._encoded)]
 
     def submit(self, ti, sample, had_mask, out_dev):
         if self.scorer is not None and sample.mask is not None:
@@ -637,12 +729,16 @@ class _FrameOutputs:
             if self.tracks is not None else ()
         if self.mattes is not None:                                  # fed before the mask: when a frame's mask has arrived, so have its planes
             self._matted = self.mattes.submit(tag, out_dev, len(self.mapper.labels))
+        if self.pngs is not None:                                    # likewise; a frame may be encoded again when its record arrives
+            self._encoded = self.pngs.submit(tag, out_dev.clone() if self.reused_output else out_dev, self.mapper)
         self._arrived = tdone, (self.fetcher.submit(tag, out_dev) if self.need_mask else self._tags(tdone))
 
     def drain(self):
         tdone = self.tracks.drain() if self.tracks is not None else ()
         if self.mattes is not None:
             self._matted = self.mattes.drain()
+        if self.pngs is not None:
+            self._encoded = self.pngs.drain()
         self._arrived = tdone, (self.fetcher.drain() if self.need_mask else self._tags(tdone))
 
     def deliver(self, last=False):
@@ -653,9 +749,15 @@ class _FrameOutputs:
         for item in self._matted:
             self.mattes.finish(item, self.mapper)
         self._matted = ()
+        files = dict(self.pngs.finish(item) for item in self._encoded) if self.pngs is not None else None      # by frame name
+        self._encoded = ()
         for (sample, had_mask), out_mask in done:
             self.stats.append(_stats_row(sample.frame, had_mask, self.compute_iou, out_mask, sample.mask))
-            if self.saver is not None:
+            if files is not None:
+                overlay = self.save_overlay and out_mask is not None
+                self.saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(out_mask) if overlay else None, sample.frame,
+                                             (lambda s=sample: s.raw_image_pil) if overlay else None, png=files.pop(sample.frame)))
+            elif self.saver is not None:
                 ids = self.mapper.remap_index_mask(out_mask)         # label LUT as of this frame (cheap); the rest is off-thread
                 self.saver.submit(_saver_job(self.reader, ids, sample.frame,
                                              (lambda s=sample: s.raw_image_pil) if self.save_overlay else None))
@@ -714,6 +816,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
     cleanup = parse_cleanup(config.get('mask_cleanup'))              # opt-in (default: absent): despeckle / fill holes / keep largest
     mattes = _parse_mattes(config)                                   # opt-in (default: absent): feathered mattes / trimaps per label
+    png_spec = _parse_png(config)                                   # opt-in (default: absent): the PNG files are built on the device
     smooth = _parse_smooth(config)                                   # opt-in (default: absent): a majority vote over time
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
@@ -775,7 +878,8 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
-        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
+        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
+        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader))
     outputs = _with_smoothing(smooth, outputs, vid_length, device)
 
     def hint(samples):
@@ -947,6 +1051,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     passes = parse_ensemble(config.get('ensemble'), config['size'])
     cleanup = parse_cleanup(config.get('mask_cleanup'))
     mattes = _parse_mattes(config)
+    png_spec = _parse_png(config)
     smooth = _parse_smooth(config)
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
@@ -1014,7 +1119,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
-        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name))
+        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
+        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader))
     outputs = _with_smoothing(smooth, outputs, vid_length, device)
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 

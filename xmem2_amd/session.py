@@ -512,11 +512,28 @@ class VideoSession:
     def _host_masks(self):
         return self.masks.cpu().numpy()
 
-    def save(self, masks_out_path, save_overlay=True):
-        """Exactly the files run_on_video writes: <out>/masks/<frame>.png (+ overlay/<frame>.jpg) for every frame that has a mask."""
+    def save(self, masks_out_path, save_overlay=True, png_on_device=None, batch=32):
+        """Exactly the files run_on_video writes: <out>/masks/<frame>.png (+ overlay/<frame>.jpg) for every frame that has a mask.
+        `png_on_device` (config['png_on_device']: None, True or {'mode': 'rgb' | 'palette'}): the PNGs are built on the device from the
+        resident `masks` in calls of `batch` frames (`ops.png_encode`) and their bytes reach the host; the masks travel only for the
+        overlays."""
         from PIL import Image
         from .run_on_video import _AsyncSaver, _saver_job
-        host = self._host_masks()
+        spec = None
+        if png_on_device is not None:
+            from .png import mask_tables, parse_option
+            spec = parse_option(png_on_device)
+        host = self._host_masks() if spec is None or save_overlay else None
+        files = {}
+        if spec is not None:
+            table, palette = (None if t is None else torch.from_numpy(t).to(self.device) for t in mask_tables(self.reader, self.mapper, spec['mode']))
+            present = [t for t, p in enumerate(self._present) if p]
+            with torch.cuda.device(self.device):
+                for i in range(0, len(present), max(1, int(batch))):
+                    chunk = present[i:i + max(1, int(batch))]
+                    contiguous = chunk == list(range(chunk[0], chunk[-1] + 1))
+                    dev = self.masks[chunk[0]:chunk[-1] + 1] if contiguous else self.masks[torch.tensor(chunk, device=self.device)]
+                    files.update(zip(chunk, ops.png_encode(dev, spec['mode'], table, palette)))
         saver = _AsyncSaver(str(masks_out_path), '')
         try:
             for t, fr in enumerate(self.frames):
@@ -524,7 +541,8 @@ class VideoSession:
                     continue
                 def reopen(name=fr.frame):                               # the decoded frames were not kept: on the writer thread
                     return Image.open(os.path.join(self.reader.image_dir, name)).convert('RGB')
-                saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(host[t]), fr.frame, reopen if save_overlay else None))
+                saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(host[t]) if host is not None else None, fr.frame,
+                                        reopen if save_overlay else None, png=files.get(t)))
         finally:
             saver.close()
 
@@ -691,6 +709,8 @@ def parse_args(argv=None):
                     help='the counts in tracks.json: uncompressed lists, or the compressed COCO strings built on the device')
     ap.add_argument('--tracks-polygons', nargs='?', const=0.0, default=None, type=float, metavar='TOL',
                     help='with --tracks: add the polygon outlines of every entry, traced on the device; TOL > 0 simplifies the rings (lossy)')
+    ap.add_argument('--png-on-device', nargs='?', const='rgb', default=None, choices=('rgb', 'palette'), metavar='MODE',
+                    help="build the mask PNGs on the device (config['png_on_device']); MODE rgb (default): today's colours, palette: index PNGs")
     ap.add_argument('--feature-cache-gb', type=float, default=0.0,
                     help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
@@ -719,7 +739,7 @@ def main(argv=None):
             chosen = s.candidates(k=args.k, alpha=args.alpha, min_mask_presence_percent=args.min_mask_presence_percent,
                                   mask_form=args.mask_form) if len(s.references) < len(s) else []
         print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
-    s.save(args.out, save_overlay=args.overlay)
+    s.save(args.out, save_overlay=args.overlay, png_on_device=None if args.png_on_device is None else {'mode': args.png_on_device})
     if args.tracks:
         s.save_tracks(args.out, counts=args.tracks_counts,
                       polygons=None if args.tracks_polygons is None else {'tolerance': args.tracks_polygons})
