@@ -2201,3 +2201,43 @@ def png_encode(planes, mode, table=None, palette=None, capacity=None, wait=True)
         else:
             files.append(data[n, :length].tobytes())
     return files
+
+
+# ---- confidence and uncertainty maps (csrc/confidence.hip, include/xmem_hip_confidence.h): integer sums, bit-reproducible ----------
+
+def _confidence_out(t, shape, dtype, device, fn, what):
+    """an output of confidence_stats: the caller's contiguous tensor of that shape, dtype and device, or a new one"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        raise RuntimeError(f'{fn}: {what} must be a contiguous {dtype} CUDA (HIP) tensor of shape {tuple(shape)} on the scores\' device')
+    return t
+
+
+def confidence_stats(prob, tau=64, passes=None, want_mask=True, want_plane=False, record=None, mask=None, plane=None):
+    """`confidence.stats_host(prob, tau, passes)` on the device, byte for byte: `prob` [C,H,W], float32 with passes=None (the tensor
+    `argmax_u8` sees), or the ensemble's uint16 sums of `passes` bytes.  -> (mask uint8 [H,W] == `argmax_u8(prob)`, or None without
+    want_mask; plane uint8 [H,W] = 255 - q, or None without want_plane; record int64 [C,4]: area, margin_sum, low, contested per
+    class).  `record`, `mask`, `plane`: tensors of the caller's to write into (a given `mask` or `plane` is wanted).  One memset and
+    one launch on the current stream, no synchronisation."""
+    from . import _lib_confidence
+    fn = 'confidence_stats'
+    want = torch.float32 if passes is None else torch.uint16
+    if not torch.is_tensor(prob) or not prob.is_cuda or prob.dtype != want or prob.dim() != 3 or prob.numel() == 0:
+        raise RuntimeError(f'{fn}: expected {want} CUDA (HIP) scores [C,H,W]' + (' with passes' if passes is not None else '')
+                           + ' - xmem2_amd has no CPU path')
+    prob = prob.contiguous()
+    Cc, H, W = prob.shape
+    if Cc > _lib_confidence.MAX_C:
+        raise ValueError(f'{fn}: {Cc} classes, at most {_lib_confidence.MAX_C} (a label fits a byte)')
+    tau = _int_arg(fn, 'tau', tau, 0, _lib_confidence.MAX_TAU)
+    record = _confidence_out(record, (Cc, _lib_confidence.RECORD), torch.int64, prob.device, fn, 'record')
+    mask = _confidence_out(mask, (H, W), torch.uint8, prob.device, fn, 'mask') if (want_mask or mask is not None) else None
+    plane = _confidence_out(plane, (H, W), torch.uint8, prob.device, fn, 'plane') if (want_plane or plane is not None) else None
+    lib = _lib_confidence.load()
+    if passes is None:
+        check(lib.xmem_confidence_f32(ptr(prob), Cc, H, W, tau, ptr(mask), ptr(plane), ptr(record), stream_ptr()))
+    else:
+        passes = _int_arg(fn, 'passes', passes, 1, _lib_confidence.MAX_PASSES)
+        check(lib.xmem_confidence_u16(ptr(prob), passes, Cc, H, W, tau, ptr(mask), ptr(plane), ptr(record), stream_ptr()))
+    return mask, plane, record

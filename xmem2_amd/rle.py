@@ -268,6 +268,7 @@ class TrackWriter:
         self._tracks = collections.OrderedDict()                     # label in the annotation PNGs -> {frame index: (counts, bbox, area)}
         self.polygons = parse_polygons(polygons)
         self._rings = {}                                             # (label, frame index) -> the entry's rings as flat integer lists
+        self._confidence = None                                      # config['confidence']: label -> (track score, per-frame confidence)
 
     def open_track(self, label):
         """The entries {frame index: (counts, bbox, area)} of the track with this label, opened - so far without any - when the label
@@ -308,6 +309,12 @@ class TrackWriter:
                 counts = counts_from_events(ev, self.height, self.width) if strings is None else str(ev)
                 track[t] = (counts, box_xywh(row), area)
 
+    def set_confidence(self, entries):
+        """config['confidence'] (xmem2_amd/confidence.py): `entries` maps a track's label to (its score, its confidence in every
+        frame).  Every annotation then gains "score" and every non-null segmentation "confidence"; NaN - no pixel to judge by - is
+        written as null, and so is everything of a label without an entry.  Without this call the file is what it was."""
+        self._confidence = {int(lab): (float(score), [float(v) for v in per_frame]) for lab, (score, per_frame) in entries.items()}
+
     def add_mask(self, file_name, mask, k=None, labels=None, counts='list'):
         """A frame from a host index array (dense ids 1..k, default its largest id), encoded on the host; None: a frame without mask.
         counts='compressed' writes the string form (`compress_counts`)."""
@@ -340,6 +347,13 @@ class TrackWriter:
             anns.append({'id': n, 'video_id': 1, 'category_id': 1, 'label': lab, 'segmentations': seg,
                          'bboxes': [track[t][1] if t in track else None for t in range(T)],
                          'areas': [track[t][2] if t in track else None for t in range(T)]})
+            if self._confidence is not None:
+                def number(v):
+                    return None if v != v else v                     # NaN is no JSON
+                score, per_frame = self._confidence.get(lab, (float('nan'), []))
+                anns[-1]['score'] = number(score)
+                for t in track:
+                    seg[t]['confidence'] = number(per_frame[t]) if t < len(per_frame) else None
         video = {'id': 1, 'height': self.height, 'width': self.width, 'length': T, 'file_names': list(self.file_names)}
         if self.polygons is not None:                                # simplified rings are lossy: the file says how it was written
             video['polygons'] = {'tolerance': self.polygons['tolerance'], 'fill': 'evenodd'}

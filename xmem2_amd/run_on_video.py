@@ -298,10 +298,14 @@ class AsyncMaskFetcher:
         return out
 
 
-def _post_process_gpu(sample, prob):
-    """run_on_video.py:165-170 on the device: resize to the original shape if needed, argmax over classes."""
+def _post_process_gpu(sample, prob, confidence=None, ti=None, given=False):
+    """run_on_video.py:165-170 on the device: resize to the original shape if needed, argmax over classes.  `confidence`
+    (config['confidence']: a `confidence.FrameConfidence`): its kernel takes the place of the argmax, yields the same mask and keeps
+    frame ti's record."""
     if sample.need_resize and tuple(prob.shape[-2:]) != tuple(sample.shape):
         prob = ops.resize_bilinear(prob, sample.shape)
+    if confidence is not None:
+        return confidence.mask(ti, prob, sample.frame, given)
     return ops.argmax_u8(prob)
 
 
@@ -446,6 +450,40 @@ def _parse_smooth(config):
         return None
     from .temporal import parse_smooth
     return parse_smooth(config['temporal_smooth'])
+
+
+def _parse_confidence(config):
+    """config['confidence'] as `confidence.parse_confidence` returns it; None without the key - nothing is imported for it then"""
+    if config.get('confidence') is None:
+        return None
+    from .confidence import parse_confidence
+    return parse_confidence(config['confidence'])
+
+
+def _frame_confidence(spec, vid_length, device, saver, config, vid_name, png_on_device):
+    """config['confidence']: the loop's `confidence.FrameConfidence`; None without the option - nothing is imported, allocated or
+    launched for it then"""
+    if spec is None:
+        return None
+    from .confidence import FrameConfidence
+    return FrameConfidence(spec, vid_length, device, saver, config['masks_out_path'], vid_name, png_on_device)
+
+
+def _with_confidence(confidence, outputs):
+    """`outputs` with the loop's FrameConfidence drained and closed beside it; `outputs` itself without the option"""
+    if confidence is None:
+        return outputs
+    from .confidence import LoopOutputs
+    return LoopOutputs(outputs, confidence)
+
+
+def _with_confidence_report(df, confidence, mapper):
+    """config['confidence']: the frame confidence per row in `df['confidence']` and the table in `df.attrs['confidence']` (one
+    transfer, after the loop)"""
+    if confidence is not None:
+        df['confidence'] = confidence.frame_confidence()[:len(df)]
+        df.attrs['confidence'] = confidence.report(mapper)
+    return df
 
 
 def _with_smoothing(spec, outputs, vid_length, device):
@@ -703,8 +741,9 @@ class _FrameOutputs:
     its record arrives, gets a copy."""
 
     def __init__(self, reader, mapper, fetcher, saver=None, tracks=None, scorer=None, compute_iou=False, save_overlay=True,
-                 masks_out_path=None, reused_output=False, mattes=None, pngs=None):
+                 masks_out_path=None, reused_output=False, mattes=None, pngs=None, confidence=None):
         self.reader, self.mapper, self.fetcher, self.saver, self.tracks, self.scorer = reader, mapper, fetcher, saver, tracks, scorer
+        self.confidence = confidence                                 # config['confidence']: the loop's FrameConfidence, for the tracks' scores
         self.mattes = mattes                                         # config['mattes']: a _MatteLoop, None without the option
         self.pngs = pngs if saver is not None else None              # config['png_on_device']: a _PngLoop, None without the option
         self.compute_iou, self.save_overlay, self.masks_out_path, self.reused_output = compute_iou, save_overlay, masks_out_path, reused_output
@@ -762,6 +801,8 @@ class _FrameOutputs:
                 self.saver.submit(_saver_job(self.reader, ids, sample.frame,
                                              (lambda s=sample: s.raw_image_pil) if self.save_overlay else None))
         if last and self.tracks is not None:
+            if self.confidence is not None:                          # the table's one transfer, after the loop
+                self.tracks.writer.set_confidence(self.confidence.track_entries(self.mapper))
             self.tracks.write(self.masks_out_path)
 
     def close(self):
@@ -818,6 +859,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     mattes = _parse_mattes(config)                                   # opt-in (default: absent): feathered mattes / trimaps per label
     png_spec = _parse_png(config)                                   # opt-in (default: absent): the PNG files are built on the device
     smooth = _parse_smooth(config)                                   # opt-in (default: absent): a majority vote over time
+    conf_spec = _parse_confidence(config)                            # opt-in (default: absent): per-object confidence, uncertainty maps
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
 
@@ -873,14 +915,15 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     cleaned = _cleanup_totals(cleanup, device)
     # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).
     saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
+    conf = _frame_confidence(conf_spec, vid_length, device, saver, config, vid_reader.vid_name, png_spec is not None)
     outputs = _FrameOutputs(
         vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
-        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader))
-    outputs = _with_smoothing(smooth, outputs, vid_length, device)
+        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
+    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device))
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -901,7 +944,8 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         skip_add = (ti == 0) if original_memory_mechanism else (msk is not None)
         prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
                               manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
-        return msk is not None, _clean_output(cleanup, _post_process_gpu(sample, prob), cleaned)
+        raw = _post_process_gpu(sample, prob) if conf is None else _post_process_gpu(sample, prob, conf, ti, msk is not None)
+        return msk is not None, _clean_output(cleanup, raw, cleaned)
 
     key_batch = max(1, int(config.get('key_batch', 4)))                # frames per batched key-encoder hint
     decoder = FramePrefetcher(vid_reader, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
@@ -913,7 +957,8 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
+    df = _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
+    return _with_confidence_report(df, conf, mapper)
 
 
 def _with_cleanup(df, totals, say=False):
@@ -1053,6 +1098,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     mattes = _parse_mattes(config)
     png_spec = _parse_png(config)
     smooth = _parse_smooth(config)
+    conf_spec = _parse_confidence(config)
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
@@ -1114,14 +1160,15 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
     scorer = InLoopScorer(vid_length, device) if compute_jf else None
     cleaned = _cleanup_totals(cleanup, device)
     saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
+    conf = _frame_confidence(conf_spec, vid_length, device, saver, config, vid_reader.vid_name, png_spec is not None)
     outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again - unless cleaned
         vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
         tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
         scorer=scorer,
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
-        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader))
-    outputs = _with_smoothing(smooth, outputs, vid_length, device)
+        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
+    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device))
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):
@@ -1159,7 +1206,9 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             if shp not in bufs:
                 bufs[shp] = (torch.empty(shp, dtype=torch.uint16, device=device), torch.empty((H, W), dtype=torch.uint8, device=device))
             acc, merged = bufs[shp]
-            ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 else None)
+            ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 and conf is None else None)
+        if conf is not None:                                         # the same first-index argmax of the sum, and the frame's record
+            conf.mask(ti, acc, sample.frame, given, passes=P, out=merged)
         return given, _clean_output(cleanup, merged, cleaned)        # cleaned: into a tensor of its own, `merged` is rewritten next frame
 
     key_batch = max(1, int(config.get('key_batch', 4)))
@@ -1172,7 +1221,8 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    return _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
+    df = _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
+    return _with_confidence_report(df, conf, mapper)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),

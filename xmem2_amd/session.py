@@ -240,6 +240,12 @@ class VideoSession:
         self._refs = {}                                                  # frame index -> the annotation's raw H x W index array
         budget = int(config.get('session_feature_cache_bytes', 0))      # opt-in: the key pass of every frame kept on the device
         self._fcache = FeatureCache(n, budget, self.device) if budget > 0 else None
+        self._confidence = None                                          # opt-in (config['confidence']): a record per propagated frame
+        if config.get('confidence') is not None:
+            from .confidence import FrameConfidence, parse_confidence
+            spec = parse_confidence(config['confidence'])
+            planes = torch.zeros((n,) + tuple(self.shape), dtype=torch.uint8, device=self.device) if spec['maps'] else None
+            self._confidence = FrameConfidence(spec, n, self.device, planes=planes)     # 'maps': the planes stay here until `save`
         torch.cuda.synchronize()                                         # the frames are complete for every stream from here on
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
@@ -391,6 +397,7 @@ class VideoSession:
 
         fcache = getattr(self, '_fcache', None)
         cleanup, cleaned = getattr(self, 'cleanup', None), getattr(self, '_cleaned', None)
+        conf = getattr(self, '_confidence', None)
 
         def prefetch(batch):
             # resident frames were complete long ago (synchronised at construction): the pass may start under the current frame
@@ -417,7 +424,8 @@ class VideoSession:
             self.key[t].view(gh, gw, -1).copy_(key[0].permute(1, 2, 0))
             self.shrinkage[t].view(gh, gw).copy_(shr[0, 0])
             self.selection[t].view(gh, gw, -1).copy_(sel[0].permute(1, 2, 0))
-            self.masks[t].copy_(_clean_output(cleanup, _post_process_gpu(fr, prob), cleaned))
+            raw = _post_process_gpu(fr, prob) if conf is None else _post_process_gpu(fr, prob, conf, t, msk is not None)
+            self.masks[t].copy_(_clean_output(cleanup, raw, cleaned))
             self._present[t] = True
         return order
 
@@ -476,6 +484,36 @@ class VideoSession:
             for at, done in waiting:
                 self.masks[at:at + done.shape[0]].copy_(done)
         return [int(v) for v in changed.cpu().tolist()]
+
+    # ---- confidence ----------------------------------------------------------------------------------------------------
+    def _require_confidence(self, what):
+        conf = getattr(self, '_confidence', None)
+        if conf is None:
+            raise RuntimeError(f"{what} needs overwrite_config={{'confidence': ...}} (xmem2_amd/confidence.py)")
+        return conf
+
+    def confidence(self):
+        """The records of the frames propagated so far (config['confidence']), one row per frame in frame order: {'threshold',
+        'labels' (0, the background, then the annotation's labels), 'frames' (their indices), 'confidence' (float64, the frame
+        confidence), 'area', 'margin_sum', 'low', 'contested' (int64 [rows, len(labels)])}.  A later visit of a frame overwrites its
+        row.  One transfer of the device table."""
+        conf = self._require_confidence('confidence()')
+        rows = [t for t, v in enumerate(conf.visited) if v]
+        out = conf.report(self.mapper)
+        for name in out:
+            if name not in ('threshold', 'labels'):
+                out[name] = out[name][rows]
+        out['frames'], out['confidence'] = rows, conf.frame_confidence()[rows]
+        return out
+
+    def review_queue(self, k=5, min_gap=0):
+        """The `k` frames whose least sure object is the least sure (`confidence.review_queue` on the table): references and frames
+        without a record are never proposed, NaN sorts last, ties go to the lower index, a frame within `min_gap` of one already
+        chosen is passed over."""
+        from .confidence import review_queue
+        conf = self._require_confidence('review_queue()')
+        skip = set(self._refs) | {t for t, v in enumerate(conf.visited) if not v} | {t for t, p in enumerate(self._present) if not p}
+        return review_queue(conf.frame_confidence(), skip, k, min_gap)
 
     # ---- candidates ----------------------------------------------------------------------------------------------------
     def mask_table(self, mask_form='objects'):
@@ -543,6 +581,13 @@ class VideoSession:
                     return Image.open(os.path.join(self.reader.image_dir, name)).convert('RGB')
                 saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(host[t]) if host is not None else None, fr.frame,
                                         reopen if save_overlay else None, png=files.get(t)))
+            conf = getattr(self, '_confidence', None)
+            if conf is not None and conf.planes is not None:             # config['confidence'] with 'maps': uncertainty/<frame>.png
+                from .confidence import plane_job
+                planes = conf.planes.cpu().numpy()
+                for t, fr in enumerate(self.frames):
+                    if conf.visited[t]:
+                        saver.submit(plane_job(planes[t], fr.frame[:-4]))
         finally:
             saver.close()
 
@@ -586,6 +631,8 @@ class VideoSession:
         for t, fr in enumerate(self.frames):
             meta, events, strings = encoded.get(t, (None, None, None))
             writer.add_frame(fr.frame, meta, events, labels=labels, strings=strings, polygons=rings.get(t))
+        if getattr(self, '_confidence', None) is not None:               # config['confidence']: "score" and "confidence"
+            writer.set_confidence(self._confidence.track_entries(self.mapper))
         return writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
 
     def save_mattes(self, masks_out_path, batch=32, **spec):
@@ -711,6 +758,9 @@ def parse_args(argv=None):
                     help='with --tracks: add the polygon outlines of every entry, traced on the device; TOL > 0 simplifies the rings (lossy)')
     ap.add_argument('--png-on-device', nargs='?', const='rgb', default=None, choices=('rgb', 'palette'), metavar='MODE',
                     help="build the mask PNGs on the device (config['png_on_device']); MODE rgb (default): today's colours, palette: index PNGs")
+    ap.add_argument('--review-by', default='dissimilarity', choices=('dissimilarity', 'confidence'),
+                    help="where the next frames to annotate come from: the selector's key dissimilarity (`candidates`), or the frames whose "
+                         "least sure object is the least sure (`review_queue`, which turns config['confidence'] on)")
     ap.add_argument('--feature-cache-gb', type=float, default=0.0,
                     help="device memory for the key encoder's per-frame outputs (config['session_feature_cache_bytes']); 0: off")
     args = ap.parse_args(argv)
@@ -726,6 +776,8 @@ def main(argv=None):
     config = json.loads(args.config) if args.config else {}
     if args.feature_cache_gb > 0:
         config['session_feature_cache_bytes'] = int(args.feature_cache_gb * (1 << 30))
+    if args.review_by == 'confidence' and config.get('confidence') is None:
+        config['confidence'] = True
     s = VideoSession(args.images, args.masks, overwrite_config=config or None)
     for t in sorted(int(x) for x in args.first.split(',') if x != ''):
         s.save_reference(t)
@@ -735,9 +787,14 @@ def main(argv=None):
             if s.frames[t].mask is not None:
                 s.save_reference(t)
         s.full_propagation()
-        with contextlib.redirect_stdout(sys.stderr):                     # the selector's progress line: stdout carries the JSON only
-            chosen = s.candidates(k=args.k, alpha=args.alpha, min_mask_presence_percent=args.min_mask_presence_percent,
-                                  mask_form=args.mask_form) if len(s.references) < len(s) else []
+        if len(s.references) >= len(s):
+            chosen = []
+        elif args.review_by == 'confidence':
+            chosen = s.review_queue(k=args.k)
+        else:
+            with contextlib.redirect_stdout(sys.stderr):                 # the selector's progress line: stdout carries the JSON only
+                chosen = s.candidates(k=args.k, alpha=args.alpha, min_mask_presence_percent=args.min_mask_presence_percent,
+                                      mask_form=args.mask_form)
         print(json.dumps(dict(round=r, references=s.references, chosen=chosen)), flush=True)
     s.save(args.out, save_overlay=args.overlay, png_on_device=None if args.png_on_device is None else {'mode': args.png_on_device})
     if args.tracks:
