@@ -14,7 +14,7 @@ import re
 
 SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t, 'uint64_t': C.c_uint64,
            'int32_t': C.c_int32, 'uint8_t': C.c_uint8}
-POINTEES = set(SCALARS) | {'void', 'char', 'uint16_t', 'uint32_t'}      # what a plain c_void_p may point to
+POINTEES = set(SCALARS) | {'void', 'char', 'int8_t', 'uint16_t', 'uint32_t'}     # what a plain c_void_p may point to
 FIELD_NAMES = {'in': 'inp'}                                             # Python keywords
 _ENUM = r'(?:typedef\s+)?enum\s*\{([^{}]*)\}\s*\w*\s*;'
 _STRUCT = r'typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;'

@@ -9,9 +9,9 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
-SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip', 'components.hip', 'polygons.hip', 'polygons_fill.hip', 'matte.hip', 'temporal.hip', 'png.hip', 'confidence.hip']
+SOURCES = ['conv.hip', 'conv_mfma.hip', 'conv_winograd.hip', 'gemm_stream.hip', 'pointwise_pair.hip', 'elementwise.hip', 'affinity.hip', 'affinity_filter.hip', 'consolidate.hip', 'selector.hip', 'augment.hip', 'metrics.hip', 'click.hip', 'brs.hip', 'edt.hip', 'resize_u8.hip', 'copy_segments.hip', 'rle.hip', 'store_compact.hip', 'components.hip', 'polygons.hip', 'polygons_fill.hip', 'matte.hip', 'temporal.hip', 'png.hip', 'motion.hip', 'confidence.hip']
 HEADERS = ['common.hpp', 'host_math.hpp', 'affinity_common.hpp', 'conv_plan.hpp', 'conv_mfma.hpp', 'conv_winograd.hpp', 'gemm_stream.hpp',
-           'pointwise_pair.hpp']
+           'pointwise_pair.hpp', 'vote_bytes.hpp']
 LIB = os.path.join(CSRC, 'libxmem_hip.so')
 ARCH = 'gfx950'
 EXTRA_FLAGS = {'augment.hip': ['-ffp-contract=off']}      # per-source flags: the augmentation kernel rounds where the host libraries round
@@ -33,6 +33,8 @@ TEMPORAL_HEADERS = [os.path.join(INCLUDE, f) for f in ('xmem_hip_temporal.h',)]
 PNG_HEADERS = [os.path.join(INCLUDE, f) for f in ('xmem_hip_png.h',)]
 # the eighth header (confidence and uncertainty maps), for the same reason
 CONFIDENCE_HEADERS = [os.path.join(INCLUDE, f) for f in ('xmem_hip_confidence.h',)]
+# the ninth header (luma, block motion, the motion-compensated vote), for the same reason
+MOTION_HEADERS = [os.path.join(INCLUDE, f) for f in ('xmem_hip_motion.h',)]
 DEVICE_FLAGS = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 _NOISE = "'-packed-fp32-ops' is not a recognized feature for this target (ignoring feature)"
 
@@ -49,7 +51,7 @@ def needs_build():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    deps += [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS] + LATER_HEADERS + MATTE_HEADERS + TEMPORAL_HEADERS + PNG_HEADERS + CONFIDENCE_HEADERS
+    deps += [os.path.join(INCLUDE, f) for f in PUBLIC_HEADERS] + LATER_HEADERS + MATTE_HEADERS + TEMPORAL_HEADERS + PNG_HEADERS + CONFIDENCE_HEADERS + MOTION_HEADERS
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -63,7 +65,7 @@ def source_digest():
     for f in PUBLIC_HEADERS:
         with open(os.path.join(INCLUDE, f), 'rb') as fh:
             h.update(fh.read())
-    for path in LATER_HEADERS + MATTE_HEADERS + TEMPORAL_HEADERS + PNG_HEADERS + CONFIDENCE_HEADERS:
+    for path in LATER_HEADERS + MATTE_HEADERS + TEMPORAL_HEADERS + PNG_HEADERS + CONFIDENCE_HEADERS + MOTION_HEADERS:
         with open(path, 'rb') as fh:
             h.update(fh.read())
     h.update(' '.join(DEVICE_FLAGS).encode())

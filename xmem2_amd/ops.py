@@ -2140,6 +2140,117 @@ def temporal_mode(masks, radius, present=None, locked=None, out=None):
     return temporal_mode_ring(masks, T, 0, T, radius, flags, out=_out_like(out, masks, 'temporal_mode'))
 
 
+# ---- block motion and the motion-compensated vote (csrc/motion.hip, include/xmem_hip_motion.h): integer, bit-reproducible ----------
+
+def _given(fn, name, t, dtype, shape, device):
+    """`t` for an output of `fn`: the caller's contiguous tensor of that dtype and shape on `device`, or a new one"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        raise RuntimeError(f'{fn}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on the input\'s device')
+    return t
+
+
+def _ring_args(fn, ring, T, t0, n, radius, flags):
+    """the arguments every call on a ring [slots,H,W] shares, checked as `temporal_mode_ring` checks them -> (ring, T, t0, n, radius)"""
+    from . import _lib_temporal
+    ring = _req_u8(ring, fn, frames='slots')
+    if ring.dim() != 3 or ring.numel() == 0:
+        raise RuntimeError(f'{fn}: expected a ring [slots,H,W], got {tuple(ring.shape)}')
+    T = _int_arg(fn, 'T', T, 1, 65535)
+    n = _int_arg(fn, 'n', n, 1, T)
+    t0 = _int_arg(fn, 't0', t0, 0, T - n)
+    radius = _int_arg(fn, 'radius', radius, 1, _lib_temporal.MAX_R)
+    held = min(T - 1, t0 + n - 1 + radius) - max(0, t0 - radius) + 1
+    if ring.shape[0] < held:
+        raise ValueError(f'{fn}: a ring of {ring.shape[0]} slots cannot hold the {held} frames that frames {t0}..{t0 + n - 1} read')
+    if not torch.is_tensor(flags) or flags.dtype != torch.uint8 or tuple(flags.shape) != (T,) or flags.device != ring.device \
+            or not flags.is_contiguous():
+        raise RuntimeError(f'{fn}: flags must be a contiguous uint8 tensor [{T}] on the ring\'s device')
+    return ring, T, t0, n, radius
+
+
+def luma_u8(rgb, out=None):
+    """`motion.luma_host` on the device: uint8 [H,W,3] or [N,H,W,3] -> uint8 [H,W] or [N,H,W].  One launch, no synchronisation."""
+    from . import _lib_motion
+    if not torch.is_tensor(rgb) or not rgb.is_cuda or rgb.dtype != torch.uint8 or rgb.dim() not in (3, 4) or rgb.shape[-1] != 3 or rgb.numel() == 0:
+        raise RuntimeError('luma_u8: expected a uint8 CUDA (HIP) tensor [H,W,3] or [N,H,W,3] - xmem2_amd has no CPU path')
+    rgb = rgb.contiguous()
+    out = _given('luma_u8', 'out', out, torch.uint8, rgb.shape[:-1], rgb.device)
+    N, H, W = (1,) + tuple(rgb.shape[:2]) if rgb.dim() == 3 else tuple(rgb.shape[:3])
+    check(_lib_motion.load().xmem_luma_u8(ptr(rgb), N, H, W, ptr(out), stream_ptr()))
+    return out
+
+
+def block_motion(cur, ref, search=16, bias=1, vec=None, sad=None):
+    """`motion.block_motion_host(cur, ref, search, bias)` on the device: uint8 [H,W] or N independent pairs [N,H,W] -> (vec int8
+    [(N,)By,Bx,2] as (dy, dx), sad int32 [(N,)By,Bx]).  One launch, no synchronisation."""
+    from . import _lib_motion
+    cur = _req_u8(cur, 'block_motion', frames='N')
+    ref = _req_u8(ref, 'block_motion', shape=cur.shape)
+    if ref.device != cur.device:
+        raise RuntimeError('block_motion: cur and ref must be on one device')
+    N, H, W = _map_dims(cur, 'block_motion')
+    search = _int_arg('block_motion', 'search', search, 1, _lib_motion.MAX_SEARCH)
+    bias = _int_arg('block_motion', 'bias', bias, 0, 255)
+    lead = tuple(cur.shape[:-2]) + (-(-H // _lib_motion.BLOCK), -(-W // _lib_motion.BLOCK))
+    vec = _given('block_motion', 'vec', vec, torch.int8, lead + (2,), cur.device)
+    sad = _given('block_motion', 'sad', sad, torch.int32, lead, cur.device)
+    check(_lib_motion.load().xmem_block_motion(ptr(cur), ptr(ref), N, H, W, search, bias, ptr(vec), ptr(sad), stream_ptr()))
+    return vec, sad
+
+
+def motion_window(luma, T, t0, n, radius, flags, search=16, bias=1, vec=None, sad=None):
+    """The block motion of the frames t0 .. t0 + n - 1 of a video of T frames towards each of their 2 `radius` neighbours, frame t
+    in slot t % luma.shape[0] of `luma`, uint8 [slots,H,W]; `flags` as `temporal_mode_ring` takes them -> (vec int8
+    [n,2 radius,By,Bx,2], sad int32 [n,2 radius,By,Bx]); entry e is the offset e - radius for e < radius, e - radius + 1 after it.
+    sad = -1 and vec = 0 where the neighbour is outside the video or not present and where the frame itself is absent or locked.
+    One launch, no synchronisation."""
+    from . import _lib_motion
+    luma, T, t0, n, radius = _ring_args('motion_window', luma, T, t0, n, radius, flags)
+    slots, H, W = luma.shape
+    search = _int_arg('motion_window', 'search', search, 1, _lib_motion.MAX_SEARCH)
+    bias = _int_arg('motion_window', 'bias', bias, 0, 255)
+    lead = (n, 2 * radius, -(-H // _lib_motion.BLOCK), -(-W // _lib_motion.BLOCK))
+    vec = _given('motion_window', 'vec', vec, torch.int8, lead + (2,), luma.device)
+    sad = _given('motion_window', 'sad', sad, torch.int32, lead, luma.device)
+    check(_lib_motion.load().xmem_motion_window(ptr(luma), slots, H, W, T, t0, n, radius, ptr(flags), search, bias, ptr(vec), ptr(sad),
+                                                stream_ptr()))
+    return vec, sad
+
+
+def temporal_mode_mc_ring(ring, luma, T, t0, n, radius, flags, search=16, bias=1, max_sad=24, out=None, changed=None, vec=None, sad=None):
+    """`temporal.mode_mc_host` of the frames t0 .. t0 + n - 1 of a video of T frames: `ring` (masks) and `luma`, both uint8
+    [slots,H,W] with frame t in slot t % slots, `flags` uint8 [T]; everything else as `temporal_mode_ring` -> (out uint8 [n,H,W],
+    changed int32 [n]).  `motion_window` (into `vec` and `sad`, the caller's or new ones) and the vote: two launches and a memset node
+    on the current stream, no synchronisation."""
+    from . import _lib_motion
+    ring, T, t0, n, radius = _ring_args('temporal_mode_mc_ring', ring, T, t0, n, radius, flags)
+    luma = _req_u8(luma, 'temporal_mode_mc_ring', shape=ring.shape)
+    if luma.device != ring.device:
+        raise RuntimeError('temporal_mode_mc_ring: the masks and the lumas must be on one device')
+    max_sad = _int_arg('temporal_mode_mc_ring', 'max_sad', max_sad, 0, 255)
+    slots, H, W = ring.shape
+    out = _given('temporal_mode_mc_ring', 'out', out, torch.uint8, (n, H, W), ring.device)
+    changed = _given('temporal_mode_mc_ring', 'changed', changed, torch.int32, (n,), ring.device)
+    vec, sad = motion_window(luma, T, t0, n, radius, flags, search, bias, vec, sad)
+    check(_lib_motion.load().xmem_temporal_mode_mc(ptr(ring), slots, H, W, T, t0, n, radius, ptr(flags), ptr(vec), ptr(sad), max_sad,
+                                                   ptr(out), ptr(changed), stream_ptr()))
+    return out, changed
+
+
+def temporal_mode_mc(masks, luma, radius, search=16, bias=1, max_sad=24, present=None, locked=None, out=None):
+    """`temporal.mode_mc_host(masks, luma, radius, search, bias, max_sad, present, locked)` on the device: masks and luma uint8
+    [T,H,W] -> (out uint8 [T,H,W], changed int32 [T])."""
+    from .temporal import frame_flags
+    masks = _req_u8(masks, 'temporal_mode_mc', frames='T')
+    if masks.dim() != 3 or masks.numel() == 0:
+        raise RuntimeError(f'temporal_mode_mc: expected masks [T,H,W], got {tuple(masks.shape)}')
+    T = masks.shape[0]
+    flags = torch.from_numpy(frame_flags(T, present, locked)).to(masks.device)
+    return temporal_mode_mc_ring(masks, luma, T, 0, T, radius, flags, search, bias, max_sad, out=_out_like(out, masks, 'temporal_mode_mc'))
+
+
 # ---- PNG files built on the device (csrc/png.hip, include/xmem_hip_png.h): integer, bit-reproducible ------------------------------
 
 PNG_STATS = {'launches': 0, 'retries': 0}      # calls of xmem_png_encode / frames encoded again because their file did not fit

@@ -783,15 +783,48 @@ def grow_tracks(tracks, r, batch=32):
     return _rewrite_masks(reader, labels, [labels.index(lab) + 1 for lab in reader.labels], lambda masks: ops.grow_masks(masks, r), batch)
 
 
-def smooth_tracks(tracks, radius, locked=(), batch=32):
+FRAME_SUFFIXES = ('.jpg', '.jpeg', '.png', '.bmp', '.tif', '.tiff', '.webp')
+
+
+def frame_lumas(frames_dir, height, width, count):
+    """`lumas(lo, hi)` -> uint8 [hi - lo, height, width]: `motion.luma_host` of the frames lo .. hi - 1 of a directory of images
+    (FRAME_SUFFIXES; other files are ignored), in the order of their names, decoded with Pillow.  ValueError unless the directory
+    holds exactly `count` frames, and for a frame of another size."""
+    from PIL import Image
+    from .motion import luma_host
+    names = sorted(f for f in os.listdir(frames_dir) if f.lower().endswith(FRAME_SUFFIXES) and not f.startswith('.'))
+    if len(names) != count:
+        raise ValueError(f'{frames_dir}: {len(names)} frames, the tracks have {count}')
+
+    def lumas(lo, hi):
+        out = np.empty((hi - lo, height, width), np.uint8)
+        for t in range(lo, hi):
+            rgb = np.asarray(Image.open(os.path.join(frames_dir, names[t])).convert('RGB'), dtype=np.uint8)
+            if rgb.shape[:2] != (height, width):
+                raise ValueError(f'{names[t]} is {rgb.shape[:2]}, the tracks are {(height, width)}: the motion search runs at the masks\' size')
+            out[t - lo] = luma_host(rgb)
+        return out
+    return lumas
+
+
+def smooth_tracks(tracks, radius, locked=(), batch=32, motion=None, lumas=None):
     """A tracks file (or parsed document) with every mask replaced by the majority vote over the frames within `radius` of it
     (`temporal.mode_host` has the definition) -> (document, pixels changed per frame), by `_rewrite_masks` with dense ids in file
     order and a halo of `radius` frames round every batch, so that a batch boundary does not show.  `locked`: frame indices that
-    vote but stay as they are (the annotated ones); a frame without a mask neither votes nor changes."""
+    vote but stay as they are (the annotated ones); a frame without a mask neither votes nor changes.
+    `motion` (True or {'search', 'bias', 'max_sad'}): the motion-compensated vote, `temporal.mode_mc_host`, on the lumas
+    `lumas(lo, hi)` -> uint8 [hi - lo, H, W] hands over (`frame_lumas` of a directory of frames, or that directory's path)."""
     import torch
     from . import ops
     from .temporal import MAX_R, frame_flags
     reader = TrackReader(tracks)
+    if motion is not None:
+        from .motion import parse_motion
+        motion = parse_motion(motion, 'smooth_tracks: motion')
+        if lumas is None:
+            raise ValueError('smooth_tracks: motion needs the frames (lumas)')
+        if isinstance(lumas, (str, os.PathLike)):
+            lumas = frame_lumas(lumas, reader.height, reader.width, len(reader))
     reader.require_unique_labels('smooth_tracks')
     locked = sorted({int(t) for t in locked})
     if locked and not 0 <= locked[0] <= locked[-1] < len(reader):
@@ -805,7 +838,11 @@ def smooth_tracks(tracks, radius, locked=(), batch=32):
         start = sum(m for _, m in first)                             # the frame the batch starts at: batches come in order
         first.append((start, n))
         flags = torch.from_numpy(frame_flags(len(present), present, is_locked[start - at:start - at + len(present)])).to(masks.device)
-        out, changed = ops.temporal_mode_ring(masks, len(present), at, n, radius, flags)
+        if motion is None:
+            out, changed = ops.temporal_mode_ring(masks, len(present), at, n, radius, flags)
+        else:
+            luma = torch.from_numpy(lumas(start - at, start - at + len(present))).to(masks.device)
+            out, changed = ops.temporal_mode_mc_ring(masks, luma, len(present), at, n, radius, flags, **motion)
         counters.append(changed)
         return out
     doc = _rewrite_masks(reader, reader.labels, 'dense', vote, batch, halo=radius)
@@ -945,6 +982,10 @@ def parse_args(argv=None):
                          '(1 <= R <= 7; needs the GPU); a step of its own, not to be combined with the others')
     ap.add_argument('--lock', default=None, metavar='FRAMES',
                     help='with --smooth: frame indices, e.g. 0,17,40, that vote but are written as they are (the annotated frames)')
+    ap.add_argument('--motion', default=None, metavar='FRAMES_DIR',
+                    help='with --smooth: the motion-compensated vote; the directory of the video\'s frames, in frame order by name and of '
+                         'the tracks\' size')
+    ap.add_argument('--motion-search', default=None, type=int, metavar='S', help='with --motion: the search range in pixels (1..32, default 16)')
     ap.add_argument('--palette-from', default=None, help='a palette PNG (an annotation) whose palette the written PNGs take')
     ap.add_argument('--skip-empty', action='store_true', help='write no file for a frame without any track entry')
     ap.add_argument('--png-on-device', action='store_true', help='with --out DIR: decode the masks and build the PNG files on the device')
@@ -967,6 +1008,14 @@ def parse_args(argv=None):
         if (args.verify_polygons or args.from_polygons or args.from_labelme is not None or args.clean or args.recode
                 or args.polygons is not None or args.grow is not None):
             ap.error('--smooth is a step of its own: run --clean, --grow, --polygons, --recode and the polygon steps on the file it writes')
+    if args.motion is not None and args.smooth is None:
+        ap.error('--motion goes with --smooth')
+    if args.motion_search is not None:
+        from .motion import MAX_SEARCH
+        if args.motion is None:
+            ap.error('--motion-search goes with --motion')
+        if not 1 <= args.motion_search <= MAX_SEARCH:
+            ap.error(f'--motion-search: 1 <= S <= {MAX_SEARCH} is needed')
     if args.lock is not None:
         if args.smooth is None:
             ap.error('--lock goes with --smooth')
@@ -998,8 +1047,13 @@ def main(argv=None):
         print(json.dumps({'frames': doc['videos'][0]['length'], 'tracks': len(doc['annotations']), 'bytes': len(text), 'out': args.out}))
         return 0
     if args.smooth is not None:
-        doc, changed = smooth_tracks(args.tracks, args.smooth, locked=args.lock or ())
+        motion = None if args.motion is None else ({} if args.motion_search is None else {'search': args.motion_search})
+        doc, changed = smooth_tracks(args.tracks, args.smooth, locked=args.lock or (), **({} if motion is None else
+                                                                                       {'motion': motion, 'lumas': args.motion}))
         report = {'smooth': args.smooth, 'pixels_changed': sum(changed), 'frames_changed': sum(1 for c in changed if c)}
+        if motion is not None:
+            from .motion import parse_motion
+            report['motion'] = parse_motion(motion, '--motion')
         print(json.dumps(dict(report, bytes=len(write_json(doc, args.out)), out=args.out)))
         return 0
     if args.recode is not None or args.clean is not None or args.polygons is not None or args.from_polygons or args.grow is not None:

@@ -486,15 +486,40 @@ def _with_confidence_report(df, confidence, mapper):
     return df
 
 
-def _with_smoothing(spec, outputs, vid_length, device):
+def _motion_frames(spec, dev_resize, source_frame):
+    """config['temporal_smooth']['motion']: `frame_of(sample)`, the sample's frame at the MASK's size - the source size - for the
+    motion search; None without the key.  With `resize_on_device` the source-size frame travels anyway (`src_u8`); else
+    `source_frame` is the loop's way to a frame it works on at the source size, unmirrored, or None if it has no such pass - an
+    error, before the loop starts."""
+    if spec is None or spec.get('motion') is None:
+        return None
+    if dev_resize:
+        return lambda sample: sample.src_u8
+    if source_frame is None:
+        raise ValueError("config['temporal_smooth']['motion'] needs frames of the masks' size, and this run resizes them on the host: "
+                         "set config['resize_on_device'] = True, or run at the source size (config['size'] = -1)")
+    return source_frame
+
+
+def _source_pass(passes):
+    """the index of the first of the ensemble's (working size, flip) passes that works at the source size, unmirrored; None if none"""
+    return next((p for p, (size, flip) in enumerate(passes) if size < 0 and not flip), None)
+
+
+def _pass_frame(p):
+    """`sample -> the frame of its pass p` (an ensemble sample's `rgb_u8` is a list); None for p None"""
+    return None if p is None else (lambda sample: sample.rgb_u8[p])
+
+
+def _with_smoothing(spec, outputs, vid_length, device, frame_of=None):
     """config['temporal_smooth']: `outputs` behind a delay line that hands every frame on as the majority vote over its neighbours in
     time; `outputs` itself without the option - nothing is imported, allocated or launched for it then.  The vote comes after
     `_clean_output` and before everything `_FrameOutputs` does; the probabilities that go back into the memory are not touched, so
-    propagation is the same with and without the option."""
+    propagation is the same with and without the option.  `frame_of`: `_motion_frames`' answer, for the compensated vote."""
     if spec is None:
         return outputs
     from .temporal import DelayLine
-    return DelayLine(outputs, spec, vid_length, device)
+    return DelayLine(outputs, spec, vid_length, device, frame_of=frame_of)
 
 
 def _with_smooth_report(df, outputs, say=False):
@@ -862,6 +887,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     conf_spec = _parse_confidence(config)                            # opt-in (default: absent): per-object confidence, uncertainty maps
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
+    motion_frames = _motion_frames(smooth, vid_reader.resize_on_device, (lambda sample: sample.rgb_u8) if vid_reader.size < 0 else None)
 
     to_permanent = [0] if original_memory_mechanism else sorted(frames_with_masks)
     loaded, preload_time = False, 0.0
@@ -923,7 +949,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
         pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
-    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device))
+    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device, motion_frames))
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -1115,6 +1141,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True, resize_on_device=dev_resize)
     vid_reader = readers[passes[0][0]]
     vid_length = len(vid_reader)
+    motion_frames = _motion_frames(smooth, dev_resize, _pass_frame(_source_pass(passes)))
     _set_long_term_count_usage(config, vid_length)                   # once for all passes
     mappers = [MaskMapper() for _ in passes]
     cores = [InferenceCore(network, config=config) for _ in passes]
@@ -1168,7 +1195,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
         mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
         pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
-    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device))
+    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device, motion_frames))
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):

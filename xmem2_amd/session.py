@@ -460,15 +460,30 @@ class VideoSession:
             for i in range(0, len(self), step):
                 self.masks[i:i + step].copy_(ops.grow_masks(self.masks[i:i + step], r))
 
-    def smooth(self, radius, batch=32):
+    def smooth(self, radius, batch=32, motion=None):
         """`ops.temporal_mode` on the masks as they stand, in place of what they held: every frame becomes the majority vote over the
         frames within `radius` of it (1..7; `temporal.mode_host` has the definition).  The references vote but stay as they are, a
         frame without a mask neither votes nor changes.  The vote runs `batch` frames per launch and every batch reads unsmoothed
         frames: a batch is written back only when no later one reads it, so the result does not depend on `batch`.  Returns the
         number of pixels changed per frame.  The session does not read config['temporal_smooth'] - `propagate` visits frames in
-        either direction and in parts, so there is no one delay line to hold: this method is its surface."""
+        either direction and in parts, so there is no one delay line to hold: this method is its surface.
+        `motion` (True, or {'search', 'bias', 'max_sad'}: `motion.parse_motion`): the motion-compensated vote,
+        `temporal.mode_mc_host` of the masks and the lumas of the resident frames (`ops.temporal_mode_mc_ring`), for which the
+        working size must be the masks' size - ValueError otherwise."""
         from .temporal import frame_flags
         T, step = len(self), max(1, int(batch))
+        vote = lambda i, n, **kw: ops.temporal_mode_ring(self.masks, T, i, n, radius, flags, **kw)
+        if motion is not None:
+            from .motion import parse_motion
+            spec = parse_motion(motion, 'VideoSession.smooth: motion')
+            if tuple(self.frame_u8(0).shape[:2]) != tuple(self.shape):
+                raise ValueError(f'VideoSession.smooth: motion needs frames of the masks\' size; the session works at '
+                                 f'{tuple(self.frame_u8(0).shape[:2])}, the masks are {tuple(self.shape)}')
+            lumas = torch.empty_like(self.masks)
+            with torch.cuda.device(self.device):
+                for t in range(T):
+                    ops.luma_u8(self.frame_u8(t).to(self.device, non_blocking=True), out=lumas[t])
+            vote = lambda i, n, **kw: ops.temporal_mode_mc_ring(self.masks, lumas, T, i, n, radius, flags, **spec, **kw)
         locked = [t in set(self.references) for t in range(T)]
         flags = torch.from_numpy(frame_flags(T, self._present, locked)).to(self.device)
         changed = torch.empty(T, dtype=torch.int32, device=self.device)
@@ -476,7 +491,7 @@ class VideoSession:
         with torch.cuda.device(self.device):
             for i in range(0, T, step):
                 n = min(step, T - i)
-                out, _ = ops.temporal_mode_ring(self.masks, T, i, n, radius, flags, changed=changed[i:i + n])
+                out, _ = vote(i, n, changed=changed[i:i + n])
                 waiting.append((i, out))
                 while waiting and waiting[0][0] + waiting[0][1].shape[0] <= i + n - radius:
                     at, done = waiting.pop(0)
