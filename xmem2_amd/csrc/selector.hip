@@ -27,7 +27,15 @@ __device__ __forceinline__ void selector_prepare_pixel(const float* __restrict__
     for (int c = lane; c < Ck; c += 64) {
         const float k = key[(size_t)p * Ck + c];
         float ck = k;
-        if (has_mask) ck = __fadd_rn(__fmul_rn(__fmul_rn(k, m), alpha), __fmul_rn(k, one_minus_alpha));
+        if (has_mask) {
+            // three rounded products and one rounded sum, as the reference's tensor expression: the _rn intrinsics are plain
+            // operators that the compiler contracts into an FMA after inlining, so contraction is switched off here instead
+#pragma clang fp contract(off)
+            const float km = k * m;
+            const float kma = km * alpha;
+            const float kb = k * one_minus_alpha;
+            ck = kma + kb;
+        }
         const float e = sel[(size_t)p * Ck + c];
         Mexp[(size_t)p * 2 * Ck + c] = ck * ck;
         Mexp[(size_t)p * 2 * Ck + Ck + c] = ck;
