@@ -322,10 +322,10 @@ def test_run_on_video_with_polygons_on_the_chair_clip(checkpoint, net, tmp_path,
 
 def test_a_frame_whose_corners_do_not_fit_is_traced_again_in_the_loop(monkeypatch):
     from xmem2_amd import ops, polygons, rle
-    from xmem2_amd.run_on_video import _TrackLoop
+    from xmem2_amd.frame_outputs import Tag, _TrackLoop
 
     class Mapper:
-        remappings = {}
+        remappings, labels = {}, [1]
     yy, xx = np.mgrid[:33, :65]
     board = ((yy + xx) % 2 == 0).astype(np.uint8)                     # 4292 corners, the default room is 2048
     quiet = np.zeros((33, 65), np.uint8)
@@ -334,12 +334,12 @@ def test_a_frame_whose_corners_do_not_fit_is_traced_again_in_the_loop(monkeypatc
     retries = ops.POLY_STATS['retries']
     arrived = []
     for t, m in enumerate((quiet, board, quiet)):
-        arrived += loop.submit(t, torch.from_numpy(m).cuda(), 1)
+        arrived += loop.submit(Tag(f'{t}.png'), torch.from_numpy(m).cuda(), Mapper)
     arrived += loop.drain()
-    assert loop.poly_capacity == 2048
+    assert loop.corners.size == 2048
     for item in arrived:
-        loop.finish(item, f'{item[0][0]}.png', Mapper)
-    assert ops.POLY_STATS['retries'] == retries + 1 and loop.poly_capacity == 2 * 4292
+        loop.finish(item, Mapper)
+    assert ops.POLY_STATS['retries'] == retries + 1 and loop.corners.size == 2 * 4292
     doc = loop.writer.to_dict()
     for t, m in enumerate((quiet, board, quiet)):
         seg = doc['annotations'][0]['segmentations'][t]

@@ -444,7 +444,7 @@ def test_track_loop_redoes_a_frame_whose_events_or_characters_did_not_fit():
     """Both overflow kinds of the frame loop, without a network: the loop's own submit / finish on a noisy frame."""
     from xmem2_amd import ops, rle
     from xmem2_amd.mask_mapper import MaskMapper
-    from xmem2_amd.run_on_video import _TrackLoop
+    from xmem2_amd.frame_outputs import Tag, _TrackLoop
     H, W, K = 33, 16, 3
     noisy = np.random.default_rng(12).integers(0, 4, size=(H, W)).astype(np.uint8)
     quiet = _from_runs((H, W), [(1, 3, 9), (2, 20, 40), (3, 50, 60)])
@@ -457,11 +457,11 @@ def test_track_loop_redoes_a_frame_whose_events_or_characters_did_not_fit():
         for t, m in enumerate((quiet, noisy, quiet)):
             dev = torch.from_numpy(m).cuda()
             if t > 0:                                                 # the noisy frame alone gets the small room
-                loop.capacity, loop.char_capacity = (capacity, ccap) if t == 1 else (4096, 4096)
-            arrived += loop.submit((f'{t}.png',), dev, K)
+                loop.events.size, loop.chars.size = (capacity, ccap) if t == 1 else (4096, 4096)
+            arrived += loop.submit(Tag(f'{t}.png'), dev, mapper)
         arrived += loop.drain()
         for item in arrived:
-            loop.finish(item, item[0][0][0], mapper)
+            loop.finish(item, mapper)
         assert (ops.RLE_STATS['retries'] - before[0], ops.RLE_STRING_STATS['retries'] - before[1]) == ((1, 0) if capacity == 16 else (0, 1))
         want = rle.TrackWriter(H, W)
         for t, m in enumerate((quiet, noisy, quiet)):

@@ -24,6 +24,8 @@ where `FrameConfidence` takes the place of the `ops.argmax_u8` call.
 """
 import numpy as np
 
+from .frame_outputs import Tag, _PlaneChannel
+
 KEY = 'confidence'
 MAX_C = 255
 MAX_TAU = 256
@@ -180,26 +182,18 @@ class FrameConfidence:
     a wider one on the device.  Nothing reaches the host before `host_table`, one transfer after the loop.  A later visit of a frame
     overwrites its row (`VideoSession.propagate`).
 
-    `maps`: the plane of every frame is delivered one frame behind through pinned memory (its own AsyncMaskFetcher) and written by
-    `_AsyncSaver` threads as <masks_out_path>/uncertainty/<frame>.png, keyed by the frame it belongs to and not by what the temporal
-    delay line hands on.  `png_on_device`: the file is built by `ops.png_encode` in grey mode and its bytes travel; a frame whose file
-    did not fit is encoded again when its record arrives, and the frames after it get twice that room.  `saver`: the loop's, or None -
-    then the planes get writers of their own, closed with the loop.  `planes`: a uint8 [T,H,W] device tensor that receives the planes
-    in place of any of that (the session's arena)."""
+    `maps`: the plane of every frame goes through a `frame_outputs._PlaneChannel` of its own - one frame behind, raw or with
+    `png_on_device` as the bytes of a file built on the device, to the loop's `saver` or to writers of its own - and becomes
+    <masks_out_path>/uncertainty/<frame>.png, keyed by the frame it belongs to and not by what the temporal delay line hands on.
+    `planes`: a uint8 [T,H,W] device tensor that receives the planes in place of any of that (the session's arena)."""
 
     def __init__(self, spec, vid_length, device, saver=None, masks_out_path=None, vid_name='', png_on_device=False, planes=None):
         self.tau, self.maps, self.T, self.device = spec['threshold'], bool(spec['maps']), int(vid_length), device
         self.table = None
         self.visited, self.given = [False] * self.T, [False] * self.T
         self.planes = planes
-        self.png_on_device, self.capacity = bool(png_on_device), None
-        self.own_saver = self.saver = self.fetcher = None
+        self.channel = _PlaneChannel(saver, masks_out_path, vid_name, png_on_device) if self.maps and planes is None else None
         self._host = None
-        if self.maps and planes is None:
-            from .run_on_video import AsyncMaskFetcher, _AsyncSaver
-            self.own_saver = _AsyncSaver(masks_out_path, vid_name) if saver is None else None
-            self.saver = self.own_saver if saver is None else saver
-            self.fetcher = AsyncMaskFetcher()
 
     def _row(self, ti, C):
         import torch
@@ -219,45 +213,22 @@ class FrameConfidence:
         mask, plane, _ = ops.confidence_stats(scores, self.tau, passes, want_mask=True, want_plane=want_plane,
                                               record=self._row(ti, scores.shape[0]), mask=out, plane=plane_out)
         self.visited[ti], self.given[ti], self._host = True, bool(given), None
-        if self.fetcher is not None:
-            self._deliver(self._submit(name, plane))
+        if self.channel is not None:
+            self._write(self.channel.send(Tag(name, had_mask=bool(given)), plane))
         return mask
 
-    def _submit(self, name, plane):
-        if not self.png_on_device:
-            return self.fetcher.submit((name,), plane)
-        from . import ops
-        from .png import default_capacity
-        if self.capacity is None:
-            self.capacity = default_capacity(*plane.shape, 'grey')
-        return self.fetcher.submit((name, plane, self.capacity), ops.png_encode(plane, 'grey', capacity=self.capacity, wait=False))
-
-    def _deliver(self, arrived):
-        for tag, buf in arrived:
-            stem = tag[0][:-4]
-            if not self.png_on_device:
-                self.saver.submit(plane_job(buf, stem))
-                continue
-            from . import ops
-            from .png import bytes_job, files_of_record
-            _, plane_dev, capacity = tag
-
-            def again(n, length, plane_dev=plane_dev):
-                ops.PNG_STATS['retries'] += 1
-                return ops.png_encode(plane_dev, 'grey', capacity=length)[0]
-
-            def grow(length):
-                self.capacity = max(self.capacity, 2 * length)
-            self.saver.submit(bytes_job([(files_of_record(buf, 1, capacity, again, grow)[0], MAPS_DIR, stem + '.png')]))
+    def _write(self, arrived):
+        for item in arrived:
+            self.channel.write(item, [(MAPS_DIR, item[0].frame[:-4] + '.png')])
 
     def drain(self):
         """the planes still on their way, after the last frame"""
-        if self.fetcher is not None:
-            self._deliver(self.fetcher.drain())
+        if self.channel is not None:
+            self._write(self.channel.drain())
 
     def close(self):
-        if self.own_saver is not None:
-            self.own_saver.close()                                       # re-raises a writer's error
+        if self.channel is not None:
+            self.channel.close()                                         # re-raises an error of writers of its own
 
     def host_table(self):
         """int64 [T, C, 4] on the host: one transfer, kept until the next frame is visited"""
@@ -286,25 +257,3 @@ class FrameConfidence:
         scores = track_scores(t[:, :, 0], t[:, :, 1], self.given)
         per_frame = object_confidence(t[:, :, 0], t[:, :, 1])
         return {lab: (scores[c], per_frame[:, c]) for c, lab in enumerate(self.labels(mapper)) if c > 0}
-
-
-class LoopOutputs:
-    """`_FrameOutputs`' interface (submit, drain, deliver, close, stats, and `report` where the inner one has it) round the real one
-    and the loop's `FrameConfidence`: the planes still on their way are drained with the loop, and the writers they may own are closed
-    with it."""
-
-    def __init__(self, inner, confidence):
-        self.inner, self.confidence = inner, confidence
-
-    def __getattr__(self, name):                                         # stats, report, submit, deliver
-        return getattr(self.inner, name)
-
-    def drain(self):
-        self.inner.drain()
-        self.confidence.drain()
-
-    def close(self):
-        try:
-            self.confidence.close()
-        finally:
-            self.inner.close()

@@ -248,7 +248,7 @@ def write_mattes(masks_of, n_frames, stems, labels, out_dir, spec, batch=32, png
     import torch
     from . import ops
     from .rle import batches
-    from .run_on_video import _AsyncSaver
+    from .frame_outputs import _AsyncSaver
     names, tables, R = tables_of(spec)
     k, written = len(labels), 0
     saver, tables_dev = _AsyncSaver(str(out_dir), ''), None

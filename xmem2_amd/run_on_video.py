@@ -12,14 +12,12 @@ What is reproduced from the reference: config merge and the derived ``enable_lon
 (:115-123) and the output layout ``<out>/masks/<frame>.png`` (+ ``overlay/<frame>.jpg``).
 Not reproduced: mp4 extraction (needs cv2).  `augment_images_with_masks` uses xmem2_amd/augmentations.py (unpinned restatement).
 
-There is one frame loop, `_run_frame_loop`: `hinted` decides which frames are hinted when, `_FrameOutputs` is the whole output side
-(scorer, tracks, mask copy one frame behind, stats rows, saver jobs).  `run_on_video` and `run_on_video_ensemble` are a preload and
-three callbacks each (hint / prepare / frame); `VideoSession` shares `hinted`, `_stats_row` and `_saver_job`.
+There is one frame loop, `_run_frame_loop`: `hinted` decides which frames are hinted when, and the whole output side (scorer, side
+channels, mask copy one frame behind, stats rows, saver jobs, the returned DataFrame) is frame_outputs.py.  `run_on_video` and
+`run_on_video_ensemble` are a preload and three callbacks each (hint / prepare / frame); `VideoSession` shares `hinted`.
 """
 import collections
 import os
-import queue
-import threading
 from dataclasses import dataclass
 from time import perf_counter
 from typing import Iterable, Optional
@@ -30,12 +28,12 @@ import torch
 
 from . import ops
 from .configuration import VIDEO_INFERENCE_CONFIG
+# the output side; the names other code takes from this module stay importable from it
+from .frame_outputs import (AsyncMaskFetcher, _AsyncSaver, _clean_output, _FrameOutputs, _TrackLoop,  # noqa: F401
+                            loop_outputs, loop_report, parse_outputs)
 from .inference_core import InferenceCore
-from .mask_cleanup import parse_cleanup
 from .mask_mapper import MaskMapper
-from .metrics import InLoopScorer
 from .network import XMem
-from .tensor_util import compute_array_iou
 
 IM_MEAN = np.array([0.485, 0.456, 0.406], np.float32)     # dataset/range_transform.py:5-8
 IM_STD = np.array([0.229, 0.224, 0.225], np.float32)
@@ -170,48 +168,6 @@ class VideoReader:
         return pred_mask.quantize(palette=self.reference_mask, dither=Image.Dither.NONE).convert('RGB')
 
 
-class _AsyncSaver:
-    """Background threads that colour-map and write masks / overlays (the reference uses two writer processes,
-    util/image_saver.py:240-345).  PIL releases the GIL inside quantize / PNG / JPEG encoding, so threads scale."""
-
-    def __init__(self, out_dir, vid_name, max_queue=200, workers=4):
-        self.root = os.path.join(out_dir, vid_name)
-        self.q = queue.Queue(max_queue)
-        self.err = None
-        self.threads = [threading.Thread(target=self._run, daemon=True) for _ in range(max(1, workers))]
-        for t in self.threads:
-            t.start()
-
-    def _run(self):
-        while True:
-            job = self.q.get()
-            if job is None:
-                return
-            try:
-                for img, sub, name in job():
-                    d = os.path.join(self.root, sub)
-                    os.makedirs(d, exist_ok=True)
-                    if isinstance(img, bytes):                       # a finished file (config['png_on_device'])
-                        with open(os.path.join(d, name), 'wb') as fh:
-                            fh.write(img)
-                        continue
-                    img.save(os.path.join(d, name), **({'compress_level': 1} if name.endswith('.png') else {}))
-            except Exception as e:                                   # surfaced by close()
-                self.err = e
-
-    def submit(self, job):
-        """job() -> iterable of (PIL image or the bytes of a finished file, sub-directory, file name); runs on a writer thread."""
-        self.q.put(job)
-
-    def close(self):
-        for _ in self.threads:
-            self.q.put(None)
-        for t in self.threads:
-            t.join()
-        if self.err is not None:
-            raise self.err
-
-
 class FramePrefetcher:
     """Decode ahead on worker threads (the reference's DataLoader worker, inference/run_on_video.py:80-92): frames are
     requested in order and arrive as Samples whose uint8 frame is already in pinned host memory."""
@@ -250,54 +206,6 @@ class FramePrefetcher:
         self.pool.shutdown(wait=False, cancel_futures=True)
 
 
-def _overlay(img, mask_rgb, alpha=0.5):
-    from PIL import Image
-    m = np.asarray(mask_rgb.resize(img.size, Image.NEAREST) if mask_rgb.size != img.size else mask_rgb)
-    fg = m.sum(-1) > 0
-    a = np.full(m.shape[:2], 255, np.uint8)
-    a[fg] = int(alpha * 255)
-    return Image.composite(img, Image.fromarray(m), Image.fromarray(a, mode='L'))
-
-
-class AsyncMaskFetcher:
-    """Device->host delivery of the uint8 index masks one frame behind the GPU: the copy of frame t goes to pinned
-    memory on the compute stream and is waited for only after frame t+1 has been enqueued, so the GPU never idles
-    on the host round trip (the reference blocks on `.cpu()` every frame, run_on_video.py:170-172)."""
-
-    def __init__(self, depth=3):
-        self.depth = depth
-        self.slots = [None] * depth
-        self.pending = []          # (tag, host tensor, event)
-        self._n = 0
-
-    def submit(self, tag, mask_gpu):
-        i = self._n % self.depth
-        self._n += 1
-        buf = self.slots[i]
-        if buf is None or buf.shape != mask_gpu.shape:
-            buf = torch.empty(mask_gpu.shape, dtype=torch.uint8, pin_memory=True)
-            self.slots[i] = buf
-        buf.copy_(mask_gpu, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.pending.append((tag, buf, ev))
-        ready = []
-        while len(self.pending) >= self.depth:      # keep at most depth-1 frames in flight
-            ready.append(self._pop())
-        return ready
-
-    def _pop(self):
-        tag, buf, ev = self.pending.pop(0)
-        ev.synchronize()
-        return tag, buf.numpy().copy()
-
-    def drain(self):
-        out = []
-        while self.pending:
-            out.append(self._pop())
-        return out
-
-
 def _post_process_gpu(sample, prob, confidence=None, ti=None, given=False):
     """run_on_video.py:165-170 on the device: resize to the original shape if needed, argmax over classes.  `confidence`
     (config['confidence']: a `confidence.FrameConfidence`): its kernel takes the place of the argmax, yields the same mask and keeps
@@ -307,183 +215,6 @@ def _post_process_gpu(sample, prob, confidence=None, ti=None, given=False):
     if confidence is not None:
         return confidence.mask(ti, prob, sample.frame, given)
     return ops.argmax_u8(prob)
-
-
-def _clean_output(spec, out_dev, totals=None):
-    """config['mask_cleanup'] (as `mask_cleanup.parse_cleanup` returns it) on the index mask a frame loop is about to hand on: `out_dev`
-    itself without the option - nothing is loaded or launched for it - else the cleaned mask in a tensor of its own, its four
-    counters added to `totals` on the device.  The probabilities that go back into the memory are not this function's business:
-    propagation is the same with and without the option, only what is written differs."""
-    if spec is None:
-        return out_dev
-    out, stats = ops.clean_masks(out_dev, **spec)
-    if totals is not None:
-        totals.add_(stats)
-    return out
-
-
-def _cleanup_totals(spec, device):
-    """the per-video sum of xmem_mask_clean's counters, kept on the device and fetched once after the loop (None without the option)"""
-    return None if spec is None else torch.zeros(4, dtype=torch.int64, device=device)
-
-
-def _cleanup_report(totals):
-    from .mask_cleanup import STATS
-    return dict(zip(STATS, (int(v) for v in totals.cpu().tolist())))
-
-
-class _TrackLoop:
-    """config['save_tracks'] inside a frame loop: one `ops.rle_encode` launch sequence per frame on the compute stream, the record
-    delivered through pinned memory one frame behind like the mask (its own AsyncMaskFetcher, fed right before the mask's: when the
-    mask of a frame has arrived, so has its record), the counts made on the host per event, the file written at the end.  A frame
-    whose events did not fit is encoded again when its record arrives, and the capacity of the frames after it grows to twice its size.
-    counts='compressed' (config['tracks_counts']): `ops.rle_compress` runs right behind the encoder on the same stream and what
-    travels is meta + string lengths + characters, not the events; a frame whose events or characters did not fit is done again at
-    its exact size when its record arrives.
-    polygons (config['tracks_polygons']): `ops.mask_polygons` runs right behind the encoder (and the compressor) on the same stream,
-    its record travels at the end of the same buffer, and a frame whose corners did not fit is traced again when it arrives, the
-    capacity of the frames after it growing to twice its size.  Without the option nothing is loaded or launched for it."""
-
-    def __init__(self, counts='list', polygons=None):
-        from .polygons import parse_polygons
-        from .rle import check_count_form
-        self.counts = check_count_form(counts)
-        self.polygons = parse_polygons(polygons)
-        # made for the first frame's size (that of the written PNGs)
-        self.writer = self.capacity = self.char_capacity = self.poly_capacity = None
-        self.fetcher = AsyncMaskFetcher()
-
-    def submit(self, tag, mask_dev, k):
-        """-> the (tag, record) pairs that have arrived.  `mask_dev` must stay untouched until its record was delivered: it is
-        encoded again should its events not fit."""
-        if self.writer is None:
-            from .rle import TrackWriter, default_capacity, default_char_capacity
-            self.writer, self.capacity = TrackWriter(*mask_dev.shape, polygons=self.polygons), default_capacity(*mask_dev.shape)
-            self.char_capacity = default_char_capacity(*mask_dev.shape)
-            if self.polygons is not None:
-                from .polygons import default_capacity as default_corners
-                self.poly_capacity = default_corners(*mask_dev.shape)
-        rec = ops.rle_encode(mask_dev, k, self.capacity, wait=False)
-        if self.counts == 'compressed':
-            from .rle import META
-            srec = ops.rle_compress(rec, *mask_dev.shape, k, self.capacity, self.char_capacity, wait=False)
-            parts, sizes = [rec[:k * META].view(torch.uint8), srec], (self.capacity, self.char_capacity)
-        else:
-            parts, sizes = [rec.view(torch.uint8)], (self.capacity,)
-        if self.polygons is not None:                                # the last 4 (2 k + poly_capacity) bytes of what travels
-            parts.append(ops.mask_polygons(mask_dev, k, self.poly_capacity, wait=False).view(torch.uint8))
-        return self.fetcher.submit((tag, mask_dev, k) + sizes + (self.poly_capacity,),
-                                   torch.cat(parts) if len(parts) > 1 else parts[0])
-
-    def drain(self):
-        return self.fetcher.drain()
-
-    def finish(self, item, name, mapper):
-        from .rle import inverse_labels, split_record
-        (_, mask_dev, k, *_sizes, poly_capacity), buf = item
-        rings = None
-        if poly_capacity is not None:
-            from .polygons import META as POLY_META
-            n = 4 * (k * POLY_META + poly_capacity)
-            rings, buf = self._finish_polygons(mask_dev, k, poly_capacity, buf[len(buf) - n:]), buf[:len(buf) - n]
-        if self.counts == 'compressed':
-            return self._finish_compressed((item[0][:-1], buf), name, mapper, rings)
-        capacity = _sizes[0]
-        meta, events = split_record(buf, 1, k, capacity)
-        meta, events = meta[0], events[0]
-        total = int(meta[:, 0].sum())
-        if total > capacity:                                         # the exact size is known now: once more, nothing is cut off
-            ops.RLE_STATS['retries'] += 1
-            meta_all, ev_all = ops.rle_encode(mask_dev, k, capacity=total)
-            meta, events = meta_all[0], ev_all[0]
-            self.capacity = max(self.capacity, 2 * total)            # and the frames to come get room for a video as ragged as this
-        self.writer.add_frame(name, meta, events, inverse_labels(mapper, k), polygons=rings)
-
-    def _finish_polygons(self, mask_dev, k, capacity, buf):
-        """-> (meta [k, 2], the frame's corner words) of the record that arrived; the frame is traced again when they did not fit"""
-        from .polygons import split_record
-        meta, corners = split_record(buf.view(np.int32), 1, k, capacity)
-        meta, total = meta[0], int(meta[0, :, 0].sum())
-        if total <= capacity:
-            return meta, corners[0, :total]
-        ops.POLY_STATS['retries'] += 1                               # the exact size is known now: once more, nothing is cut off
-        meta_all, words_all = ops.mask_polygons(mask_dev, k, capacity=total)
-        if (meta_all[0] != meta).any():
-            raise RuntimeError('tracks_polygons: a frame traced again gave other counts')
-        self.poly_capacity = max(self.poly_capacity, 2 * total)      # and the frames to come get room for a video as ragged as this
-        return meta_all[0], words_all[0]
-
-    def _finish_compressed(self, item, name, mapper, rings=None):
-        from .rle import META, inverse_labels, label_strings, split_string_record
-        (_, mask_dev, k, capacity, char_capacity), buf = item
-        meta = buf[:4 * k * META].view(np.int32).reshape(k, META)
-        str_len, chars = split_string_record(buf[4 * k * META:], 1, k, char_capacity)
-        total, need = int(meta[:, 0].sum()), int(str_len[0].sum())   # need < 0: the events did not fit, no string was made
-        if total > capacity or need > char_capacity:                 # the exact sizes are known now: once more, nothing is cut off
-            if total > capacity:
-                ops.RLE_STATS['retries'] += 1
-                self.capacity = max(self.capacity, 2 * total)        # the frames to come get room for a video as ragged as this
-            else:
-                ops.RLE_STRING_STATS['retries'] += 1
-            rec = ops.rle_encode(mask_dev, k, max(total, 1), wait=False)
-            strings = ops.rle_compress(rec, *mask_dev.shape, k, max(total, 1), max(need, char_capacity))[0]
-            self.char_capacity = max(self.char_capacity, 2 * sum(len(v) for v in strings))
-        else:
-            strings = label_strings(str_len[0], chars[0])
-        self.writer.add_frame(name, meta, None, inverse_labels(mapper, k), strings=strings, polygons=rings)
-
-    def write(self, masks_out_path):
-        return self.writer.write(os.path.join(str(masks_out_path), 'tracks.json'))
-
-
-def _parse_mattes(config):
-    """config['mattes'] as `matte.parse_mattes` returns it; None without the key - nothing is imported for it then"""
-    if config.get('mattes') is None:
-        return None
-    from .matte import parse_mattes
-    return parse_mattes(config['mattes'])
-
-
-def _parse_smooth(config):
-    """config['temporal_smooth'] as `temporal.parse_smooth` returns it; None without the key - nothing is imported for it then"""
-    if config.get('temporal_smooth') is None:
-        return None
-    from .temporal import parse_smooth
-    return parse_smooth(config['temporal_smooth'])
-
-
-def _parse_confidence(config):
-    """config['confidence'] as `confidence.parse_confidence` returns it; None without the key - nothing is imported for it then"""
-    if config.get('confidence') is None:
-        return None
-    from .confidence import parse_confidence
-    return parse_confidence(config['confidence'])
-
-
-def _frame_confidence(spec, vid_length, device, saver, config, vid_name, png_on_device):
-    """config['confidence']: the loop's `confidence.FrameConfidence`; None without the option - nothing is imported, allocated or
-    launched for it then"""
-    if spec is None:
-        return None
-    from .confidence import FrameConfidence
-    return FrameConfidence(spec, vid_length, device, saver, config['masks_out_path'], vid_name, png_on_device)
-
-
-def _with_confidence(confidence, outputs):
-    """`outputs` with the loop's FrameConfidence drained and closed beside it; `outputs` itself without the option"""
-    if confidence is None:
-        return outputs
-    from .confidence import LoopOutputs
-    return LoopOutputs(outputs, confidence)
-
-
-def _with_confidence_report(df, confidence, mapper):
-    """config['confidence']: the frame confidence per row in `df['confidence']` and the table in `df.attrs['confidence']` (one
-    transfer, after the loop)"""
-    if confidence is not None:
-        df['confidence'] = confidence.frame_confidence()[:len(df)]
-        df.attrs['confidence'] = confidence.report(mapper)
-    return df
 
 
 def _motion_frames(spec, dev_resize, source_frame):
@@ -509,145 +240,6 @@ def _source_pass(passes):
 def _pass_frame(p):
     """`sample -> the frame of its pass p` (an ensemble sample's `rgb_u8` is a list); None for p None"""
     return None if p is None else (lambda sample: sample.rgb_u8[p])
-
-
-def _with_smoothing(spec, outputs, vid_length, device, frame_of=None):
-    """config['temporal_smooth']: `outputs` behind a delay line that hands every frame on as the majority vote over its neighbours in
-    time; `outputs` itself without the option - nothing is imported, allocated or launched for it then.  The vote comes after
-    `_clean_output` and before everything `_FrameOutputs` does; the probabilities that go back into the memory are not touched, so
-    propagation is the same with and without the option.  `frame_of`: `_motion_frames`' answer, for the compensated vote."""
-    if spec is None:
-        return outputs
-    from .temporal import DelayLine
-    return DelayLine(outputs, spec, vid_length, device, frame_of=frame_of)
-
-
-def _with_smooth_report(df, outputs, say=False):
-    """config['temporal_smooth']: the radius and the video's changed pixels and frames in `df.attrs['temporal_smooth']` (one transfer,
-    after the loop)"""
-    if hasattr(outputs, 'report'):
-        df.attrs['temporal_smooth'] = outputs.report()
-        if say:
-            print('TEMPORAL SMOOTHING: ' + ', '.join(f'{k.replace("_", " ")} {v}' for k, v in df.attrs['temporal_smooth'].items()))
-    return df
-
-
-class _MatteLoop:
-    """config['mattes'] inside a frame loop: one `ops.mask_mattes` launch sequence per frame on the compute stream, right behind the
-    clean-up, on the index mask the loop hands on (cleaned, at the original resolution).  The planes - uint8 [T, K, H, W], one per table
-    (matte, trimap) and label the mapper knows at that frame - are delivered through pinned memory one frame behind like the mask
-    (their own AsyncMaskFetcher) and written by `_AsyncSaver` threads as <masks_out_path>/mattes/<label>/<frame>.png and, with a
-    trimap, <masks_out_path>/trimaps/<label>/<frame>.png, 8-bit mode L, <label> the annotation's label as in tracks.json.  Masks,
-    tracks and what goes back into the memory are not touched.  `saver`: the loop's, or None - then the planes get writers of
-    their own, closed with the loop.  `png_on_device` (config['png_on_device']): the T x K planes of a frame are encoded as 'grey' PNGs in
-    one `ops.png_encode` call right behind the look-up and the files' bytes travel, not the planes; a frame with a file that did not
-    fit is encoded again when its record arrives, and the frames after it get twice that room."""
-
-    def __init__(self, spec, saver, masks_out_path, vid_name='', png_on_device=False):
-        from .matte import tables_of
-        self.names, self._tables, self.R = tables_of(spec)
-        self.png_on_device, self.capacity = bool(png_on_device), None
-        self.own_saver = _AsyncSaver(masks_out_path, vid_name) if saver is None else None
-        self.saver = self.own_saver if saver is None else saver
-        self.tables = None                                           # on the device, from the first frame on
-        self.fetcher = AsyncMaskFetcher()
-
-    def submit(self, tag, mask_dev, k):
-        """-> the (tag, planes) pairs that have arrived"""
-        if k == 0:
-            return []
-        if self.tables is None:
-            self.tables = torch.from_numpy(self._tables).to(mask_dev.device)
-        planes = ops.mask_mattes(mask_dev, k, self.tables, self.R)
-        if not self.png_on_device:
-            return self.fetcher.submit((tag, k), planes)
-        from .png import default_capacity
-        if self.capacity is None:
-            self.capacity = default_capacity(*planes.shape[-2:], 'grey')
-        planes = planes.reshape((-1,) + tuple(planes.shape[-2:]))
-        return self.fetcher.submit((tag, k, planes, self.capacity), ops.png_encode(planes, 'grey', capacity=self.capacity, wait=False))
-
-    def drain(self):
-        return self.fetcher.drain()
-
-    def finish(self, item, mapper):
-        from .matte import plane_job
-        from .rle import inverse_labels
-        if self.png_on_device:
-            from .png import bytes_job, files_of_record, plane_files
-            ((sample, _), k, planes_dev, capacity), buf = item
-
-            def again(n, length):
-                ops.PNG_STATS['retries'] += 1
-                return ops.png_encode(planes_dev[n], 'grey', capacity=length)[0]
-
-            def grow(length):
-                self.capacity = max(self.capacity, 2 * length)
-            files = files_of_record(buf, planes_dev.shape[0], capacity, again, grow)
-            self.saver.submit(bytes_job(plane_files(self.names, inverse_labels(mapper, k), files, sample.frame[:-4])))
-            return
-        ((sample, _), k), planes = item
-        self.saver.submit(plane_job(self.names, inverse_labels(mapper, k), planes, sample.frame[:-4]))
-
-    def close(self):
-        if self.own_saver is not None:
-            self.own_saver.close()                                   # re-raises a writer's error
-
-
-def _parse_png(config):
-    """config['png_on_device'] as `png.parse_option` returns it; None without the key - nothing is imported for it then"""
-    if config.get('png_on_device') is None:
-        return None
-    from .png import parse_option
-    return parse_option(config['png_on_device'])
-
-
-class _PngLoop:
-    """config['png_on_device'] inside a frame loop: one `ops.png_encode` launch sequence per frame on the compute stream, on the index
-    mask the loop hands on (behind the clean-up and the delay line), the record - meta and `capacity` bytes - delivered through pinned
-    memory one frame behind like the mask (its own AsyncMaskFetcher, fed before the mask's: when a frame's mask has arrived, so has its
-    file).  mode 'rgb': the colours `map_the_colors_back` gives the labels as of that frame, so masks/<frame>.png opens to what the
-    host path writes; 'palette': the index PNG with the annotation's palette.  The tables are made per label map and stay on the
-    device.  A frame whose file did not fit is encoded again at its true length when its record arrives, and the frames after it get
-    twice that room.  `mask_dev` must stay untouched until then."""
-
-    def __init__(self, spec, reader):
-        self.mode, self.reader = spec['mode'], reader
-        self.capacity = None                                         # made for the first frame's size
-        self._tables = {}                                            # label map -> (table, palette) on the device
-        self.fetcher = AsyncMaskFetcher()
-
-    def _device_tables(self, mapper, device):
-        from .png import label_map, mask_tables
-        key = label_map(mapper).tobytes()
-        if key not in self._tables:
-            self._tables[key] = tuple(None if t is None else torch.from_numpy(t).to(device) for t in mask_tables(self.reader, mapper, self.mode))
-        return self._tables[key]
-
-    def submit(self, tag, mask_dev, mapper):
-        """-> the (tag, record) pairs that have arrived"""
-        if self.capacity is None:
-            from .png import default_capacity
-            self.capacity = default_capacity(*mask_dev.shape, self.mode)
-        table, palette = self._device_tables(mapper, mask_dev.device)
-        rec = ops.png_encode(mask_dev, self.mode, table, palette, capacity=self.capacity, wait=False)
-        return self.fetcher.submit((tag, mask_dev, table, palette, self.capacity), rec)
-
-    def drain(self):
-        return self.fetcher.drain()
-
-    def finish(self, item):
-        """-> (the frame's name, the bytes of its file)"""
-        from .png import files_of_record
-        (tag, mask_dev, table, palette, capacity), buf = item
-
-        def again(n, length):
-            ops.PNG_STATS['retries'] += 1
-            return ops.png_encode(mask_dev, self.mode, table, palette, capacity=length)[0]
-
-        def grow(length):
-            self.capacity = max(self.capacity, 2 * length)           # the frames to come get room for a video as ragged as this
-        return tag[0].frame, files_of_record(buf, 1, capacity, again, grow)[0]
 
 
 def _working_u8(src_u8, target_hw, device, flip=False):
@@ -732,113 +324,6 @@ def hinted(order, key_batch, prefetch):
         yield pending.popleft()
 
 
-def _stats_row(frame, had_mask, compute_iou, out_mask=None, gt=None):
-    """One row of the returned DataFrame (run_on_video.py:115-123)."""
-    stat = {'frame': frame, 'mask_provided': had_mask}
-    if compute_iou:
-        stat['iou'] = float(compute_array_iou(out_mask, gt)) if (gt is not None and not had_mask) else -1
-    return stat
-
-
-def _saver_job(reader, ids, frame, overlay_image=None, png=None):
-    """The _AsyncSaver job that colour-maps the index mask `ids` and yields <frame>.png and, when `overlay_image() -> PIL image` is
-    given, the overlay <frame>.jpg on it.  `png`: the bytes of <frame>.png, built on the device; the colours are then made for the
-    overlay alone, and without an overlay `ids` is not looked at."""
-    def job():
-        from PIL import Image
-        if png is not None:
-            yield png, 'masks', frame[:-4] + '.png'
-            if overlay_image is None:
-                return
-        out_img = reader.map_the_colors_back(Image.fromarray(ids))
-        if png is None:
-            yield out_img, 'masks', frame[:-4] + '.png'
-        if overlay_image is not None:
-            yield _overlay(overlay_image(), out_img), 'overlay', frame[:-4] + '.jpg'
-    return job
-
-
-class _FrameOutputs:
-    """Everything a frame loop does with a frame's index mask once it is on the device: J&F scoring, the track record, the copy to the
-    host one frame behind, and - when a frame has arrived - its stats row and its saver job.  `submit` and `drain` enqueue and wait
-    (the caller times them); `deliver` is the host side of whatever arrived.  With tracks only, no mask travels: a frame is delivered
-    with its record.  `reused_output`: the caller rewrites `out_dev` next frame, so the track loop, which may encode a frame again when
-    its record arrives, gets a copy."""
-
-    def __init__(self, reader, mapper, fetcher, saver=None, tracks=None, scorer=None, compute_iou=False, save_overlay=True,
-                 masks_out_path=None, reused_output=False, mattes=None, pngs=None, confidence=None):
-        self.reader, self.mapper, self.fetcher, self.saver, self.tracks, self.scorer = reader, mapper, fetcher, saver, tracks, scorer
-        self.confidence = confidence                                 # config['confidence']: the loop's FrameConfidence, for the tracks' scores
-        self.mattes = mattes                                         # config['mattes']: a _MatteLoop, None without the option
-        self.pngs = pngs if saver is not None else None              # config['png_on_device']: a _PngLoop, None without the option
-        self.compute_iou, self.save_overlay, self.masks_out_path, self.reused_output = compute_iou, save_overlay, masks_out_path, reused_output
-        # the H x W mask itself travels only for who reads it on the host: the PNG writers and compute_iou
-        self.need_mask = tracks is None or saver is not None or compute_iou
-        if self.pngs is not None:                                    # the files come from the device: only the overlays and compute_iou read it
-            self.need_mask = save_overlay or compute_iou
-        self.stats = []
-        self._arrived = ((), ())
-        self._matted = ()
-        self._encoded = ()
-
-    def _tags(self, tdone):
-        """no mask travels: the frames whose track record or PNG record arrived stand in for the masks that were never copied"""
-        return [(it[0][0], None) for it in (tdone if self.tracks is not None else self._encoded)]
-
-    def submit(self, ti, sample, had_mask, out_dev):
-        if self.scorer is not None and sample.mask is not None:
-            self.scorer.add(ti, sample.mask, out_dev, self.mapper)
-        tag = (sample, had_mask)
-        tdone = self.tracks.submit(tag, out_dev.clone() if self.reused_output else out_dev, len(self.mapper.labels)) \
-            if self.tracks is not None else ()
-        if self.mattes is not None:                                  # fed before the mask: when a frame's mask has arrived, so have its planes
-            self._matted = self.mattes.submit(tag, out_dev, len(self.mapper.labels))
-        if self.pngs is not None:                                    # likewise; a frame may be encoded again when its record arrives
-            self._encoded = self.pngs.submit(tag, out_dev.clone() if self.reused_output else out_dev, self.mapper)
-        self._arrived = tdone, (self.fetcher.submit(tag, out_dev) if self.need_mask else self._tags(tdone))
-
-    def drain(self):
-        tdone = self.tracks.drain() if self.tracks is not None else ()
-        if self.mattes is not None:
-            self._matted = self.mattes.drain()
-        if self.pngs is not None:
-            self._encoded = self.pngs.drain()
-        self._arrived = tdone, (self.fetcher.drain() if self.need_mask else self._tags(tdone))
-
-    def deliver(self, last=False):
-        tdone, done = self._arrived
-        self._arrived = ((), ())
-        for item in tdone:
-            self.tracks.finish(item, item[0][0][0].frame, self.mapper)
-        for item in self._matted:
-            self.mattes.finish(item, self.mapper)
-        self._matted = ()
-        files = dict(self.pngs.finish(item) for item in self._encoded) if self.pngs is not None else None      # by frame name
-        self._encoded = ()
-        for (sample, had_mask), out_mask in done:
-            self.stats.append(_stats_row(sample.frame, had_mask, self.compute_iou, out_mask, sample.mask))
-            if files is not None:
-                overlay = self.save_overlay and out_mask is not None
-                self.saver.submit(_saver_job(self.reader, self.mapper.remap_index_mask(out_mask) if overlay else None, sample.frame,
-                                             (lambda s=sample: s.raw_image_pil) if overlay else None, png=files.pop(sample.frame)))
-            elif self.saver is not None:
-                ids = self.mapper.remap_index_mask(out_mask)         # label LUT as of this frame (cheap); the rest is off-thread
-                self.saver.submit(_saver_job(self.reader, ids, sample.frame,
-                                             (lambda s=sample: s.raw_image_pil) if self.save_overlay else None))
-        if last and self.tracks is not None:
-            if self.confidence is not None:                          # the table's one transfer, after the loop
-                self.tracks.writer.set_confidence(self.confidence.track_entries(self.mapper))
-            self.tracks.write(self.masks_out_path)
-
-    def close(self):
-        try:
-            if self.mattes is not None:
-                self.mattes.close()
-        finally:
-            if self.saver is not None:
-                self.saver.close()                                   # re-raises a writer's error
-
-
 def _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame):
     """The frame loop of run_on_video and of the ensemble.  Frames come from `decoder` (a FramePrefetcher: the DataLoader role, outside
     the timed region, run_on_video.py:80-113) and are hinted `key_batch` ahead: `hint(samples) -> one device input per sample`.
@@ -876,18 +361,13 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
                         augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
                         object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
                         compute_jf=False, network=None):
-    import pandas as pd
     device = _inference_device()
     frames_with_masks = set(frames_with_masks)
     config = _merged_config({} if overwrite_config is None else overwrite_config, masks_out_path)   # the caller's dict receives the path
-    cleanup = parse_cleanup(config.get('mask_cleanup'))              # opt-in (default: absent): despeckle / fill holes / keep largest
-    mattes = _parse_mattes(config)                                   # opt-in (default: absent): feathered mattes / trimaps per label
-    png_spec = _parse_png(config)                                   # opt-in (default: absent): the PNG files are built on the device
-    smooth = _parse_smooth(config)                                   # opt-in (default: absent): a majority vote over time
-    conf_spec = _parse_confidence(config)                            # opt-in (default: absent): per-object confidence, uncertainty maps
+    out_spec = parse_outputs(config)
     mapper, processor, vid_reader = _load_main_objects(imgs_in_path, masks_in_path, config, device, network=network)
     vid_length = len(vid_reader)
-    motion_frames = _motion_frames(smooth, vid_reader.resize_on_device, (lambda sample: sample.rgb_u8) if vid_reader.size < 0 else None)
+    motion_frames = _motion_frames(out_spec['smooth'], vid_reader.resize_on_device, (lambda sample: sample.rgb_u8) if vid_reader.size < 0 else None)
 
     to_permanent = [0] if original_memory_mechanism else sorted(frames_with_masks)
     loaded, preload_time = False, 0.0
@@ -937,19 +417,9 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
     if not loaded:
         raise ValueError('No valid masks provided!')
 
-    scorer = InLoopScorer(vid_length, device) if compute_jf else None
-    cleaned = _cleanup_totals(cleanup, device)
-    # Opt-in (config['save_tracks'] = True; default False): the device finds the run boundaries, the host receives those (rle.py).
-    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
-    conf = _frame_confidence(conf_spec, vid_length, device, saver, config, vid_reader.vid_name, png_spec is not None)
-    outputs = _FrameOutputs(
-        vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
-        tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
-        scorer=scorer,
-        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'],
-        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
-        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
-    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device, motion_frames))
+    side = loop_outputs(config, out_spec, vid_reader, mapper, device, vid_length, motion_frames=motion_frames, compute_iou=compute_iou,
+                        save_overlay=save_overlay, compute_jf=compute_jf, max_queue=image_saving_max_queue_size)
+    conf = side.conf
 
     def hint(samples):
         if samples[0].rgb_u8 is None:                                # resize_on_device: source frames; H2D + resize on the side stream too
@@ -971,11 +441,11 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         prob = processor.step(rgb, msk, labels, end=(ti == vid_length - 1),
                               manually_curated_masks=manually_curated_masks, do_not_add_mask_to_memory=skip_add)
         raw = _post_process_gpu(sample, prob) if conf is None else _post_process_gpu(sample, prob, conf, ti, msk is not None)
-        return msk is not None, _clean_output(cleanup, raw, cleaned)
+        return msk is not None, _clean_output(side.cleanup, raw, side.cleaned)
 
     key_batch = max(1, int(config.get('key_batch', 4)))                # frames per batched key-encoder hint
     decoder = FramePrefetcher(vid_reader, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
-    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame)
+    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, side.outputs, hint, prepare, frame)
     if print_fps:
         print(f'TOTAL PRELOADING TIME: {preload_time:.4f}s')
         print(f'TOTAL PROCESSING TIME: {total_time:.4f}s')
@@ -983,24 +453,7 @@ def _inference_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_ou
         print(f'TOTAL FPS (excluding image saving): {vid_length / (preload_time + total_time):.4f}')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    df = _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
-    return _with_confidence_report(df, conf, mapper)
-
-
-def _with_cleanup(df, totals, say=False):
-    """config['mask_cleanup']: the video's totals of the four counters in `df.attrs['cleanup']` (one transfer, after the loop)"""
-    if totals is not None:
-        df.attrs['cleanup'] = _cleanup_report(totals)
-        if say:
-            print('MASK CLEAN-UP: ' + ', '.join(f'{k.replace("_", " ")} {v}' for k, v in df.attrs['cleanup'].items()))
-    return df
-
-
-def _with_jf(df, scorer):
-    """compute_jf=True: the J and F columns (per-frame means over the sequence's ground-truth objects, NaN without a ground truth)."""
-    if scorer is not None:
-        df['J'], df['F'] = scorer.scores()
-    return df
+    return loop_report(side, say=print_fps)
 
 
 def run_on_video(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),
@@ -1117,14 +570,9 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
                        augment_images_with_masks=False, overwrite_config: dict = None, save_overlay=True,
                        object_color_if_single_object=(255, 255, 255), print_fps=False, image_saving_max_queue_size=200,
                        compute_jf=False, network=None):
-    import pandas as pd
     config = _merged_config(dict(overwrite_config or {}), masks_out_path)           # on a copy: the caller's dict stays as it is
     passes = parse_ensemble(config.get('ensemble'), config['size'])
-    cleanup = parse_cleanup(config.get('mask_cleanup'))
-    mattes = _parse_mattes(config)
-    png_spec = _parse_png(config)
-    smooth = _parse_smooth(config)
-    conf_spec = _parse_confidence(config)
+    out_spec = parse_outputs(config)
     if augment_images_with_masks:
         raise NotImplementedError('run_on_video_ensemble: augment_images_with_masks is not supported (the augmented preload is '
                                   'defined for one working size and orientation); run the passes without it')
@@ -1141,7 +589,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             readers[s] = VideoReader('', imgs_in_path, masks_in_path, size=s, use_all_masks=True, resize_on_device=dev_resize)
     vid_reader = readers[passes[0][0]]
     vid_length = len(vid_reader)
-    motion_frames = _motion_frames(smooth, dev_resize, _pass_frame(_source_pass(passes)))
+    motion_frames = _motion_frames(out_spec['smooth'], dev_resize, _pass_frame(_source_pass(passes)))
     _set_long_term_count_usage(config, vid_length)                   # once for all passes
     mappers = [MaskMapper() for _ in passes]
     cores = [InferenceCore(network, config=config) for _ in passes]
@@ -1184,18 +632,11 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         raise ValueError('No valid masks provided!')
 
     mapper = mappers[0]
-    scorer = InLoopScorer(vid_length, device) if compute_jf else None
-    cleaned = _cleanup_totals(cleanup, device)
-    saver = _AsyncSaver(config['masks_out_path'], vid_reader.vid_name, image_saving_max_queue_size) if config['save_masks'] else None
-    conf = _frame_confidence(conf_spec, vid_length, device, saver, config, vid_reader.vid_name, png_spec is not None)
-    outputs = _FrameOutputs(                                         # on the merged mask, a buffer the next frame writes again - unless cleaned
-        vid_reader, mapper, AsyncMaskFetcher(), saver=saver,
-        tracks=_TrackLoop(config.get('tracks_counts', 'list'), config.get('tracks_polygons')) if config.get('save_tracks', False) else None,
-        scorer=scorer,
-        compute_iou=compute_iou, save_overlay=save_overlay, masks_out_path=config['masks_out_path'], reused_output=cleanup is None,
-        mattes=None if mattes is None else _MatteLoop(mattes, saver, config['masks_out_path'], vid_reader.vid_name, png_spec is not None),
-        pngs=None if png_spec is None or saver is None else _PngLoop(png_spec, vid_reader), confidence=conf)
-    outputs = _with_confidence(conf, _with_smoothing(smooth, outputs, vid_length, device, motion_frames))
+    # on the merged mask, a buffer the next frame writes again - unless cleaned
+    side = loop_outputs(config, out_spec, vid_reader, mapper, device, vid_length, reused_output=out_spec['cleanup'] is None,
+                        motion_frames=motion_frames, compute_iou=compute_iou, save_overlay=save_overlay, compute_jf=compute_jf,
+                        max_queue=image_saving_max_queue_size)
+    conf = side.conf
     bufs = {}                                                        # (C, H, W) -> (uint16 score sum, uint8 merged mask)
 
     def hint(samples):
@@ -1236,11 +677,11 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
             ops.ensemble_accumulate(prob, (H, W), f, acc, first=(p == 0), out=merged if p == P - 1 and conf is None else None)
         if conf is not None:                                         # the same first-index argmax of the sum, and the frame's record
             conf.mask(ti, acc, sample.frame, given, passes=P, out=merged)
-        return given, _clean_output(cleanup, merged, cleaned)        # cleaned: into a tensor of its own, `merged` is rewritten next frame
+        return given, _clean_output(side.cleanup, merged, side.cleaned)       # cleaned: into a tensor of its own, `merged` is rewritten next frame
 
     key_batch = max(1, int(config.get('key_batch', 4)))
     decoder = EnsembleFramePrefetcher(readers, passes, depth=4 * key_batch, workers=int(config.get('decode_workers', 8)))
-    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, outputs, hint, prepare, frame)
+    total_time, loop_wall, total_wall = _run_frame_loop(vid_length, key_batch, decoder, side.outputs, hint, prepare, frame)
     if print_fps:
         print(f'ENSEMBLE PASSES: {P} (' + ', '.join(str(s) + (' flip' if f else '') for s, f in passes) + ')')
         print(f'TOTAL PRELOADING TIME: {preload_time:.4f}s')
@@ -1248,8 +689,7 @@ def _ensemble_on_video(frames_with_masks, imgs_in_path, masks_in_path, masks_out
         print(f'TOTAL PROCESSING FPS: {vid_length / total_time:.4f} (ensemble of {P} passes; {P * vid_length / total_time:.4f} passes/s)')
         print(f'WALL-CLOCK FPS of the frame loop incl. decode: {vid_length / loop_wall:.4f}; incl. writing every mask: '
               f'{vid_length / total_wall:.4f}')
-    df = _with_smooth_report(_with_cleanup(_with_jf(pd.DataFrame(outputs.stats), scorer), cleaned, print_fps), outputs, print_fps)
-    return _with_confidence_report(df, conf, mapper)
+    return loop_report(side, say=print_fps)
 
 
 def run_on_video_ensemble(imgs_in_path, masks_in_path, masks_out_path, frames_with_masks: Iterable[int] = (0,),

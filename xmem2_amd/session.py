@@ -173,7 +173,8 @@ class _Frame:
 
 class VideoSession:
     def __init__(self, imgs_in_path, masks_in_path=None, overwrite_config=None, network=None):
-        from .run_on_video import _cleanup_totals, _make_network, _set_long_term_count_usage, _working_u8
+        from .frame_outputs import _cleanup_totals
+        from .run_on_video import _make_network, _set_long_term_count_usage, _working_u8
         if not os.path.isdir(imgs_in_path):
             raise NotADirectoryError(f'imgs_in_path: {imgs_in_path!r} is not a directory of frames')
         if masks_in_path is not None and not os.path.isdir(masks_in_path) and not os.path.isfile(masks_in_path):
@@ -388,7 +389,8 @@ class VideoSession:
     def propagate(self, start=0, direction='forward', stop=None, manually_curated_masks=False):
         """gui.on_propagation: step over start..stop in `direction` on the memory as it stands; per visited frame the call
         run_on_video's frame loop makes.  Returns the visited frame indices."""
-        from .run_on_video import _clean_output, _post_process_gpu
+        from .frame_outputs import _clean_output
+        from .run_on_video import _post_process_gpu
         order = visit_order(len(self), start, direction, stop)
         if not self._refs:
             raise ValueError('No valid masks provided!')
@@ -440,7 +442,7 @@ class VideoSession:
         """`ops.clean_masks` on the masks as they stand, `batch` frames per call, in place of what they held; a frame without a mask
         is all zero and stays so.  Returns the totals {components_removed, pixels_removed, holes_filled, pixels_filled}."""
         from .mask_cleanup import parse_cleanup
-        from .run_on_video import _cleanup_report
+        from .frame_outputs import _cleanup_report
         spec = parse_cleanup({'min_area': min_area, 'max_hole': max_hole, 'keep_largest': keep_largest})
         totals = torch.zeros(4, dtype=torch.int64, device=self.device)
         step = max(1, int(batch))
@@ -571,7 +573,7 @@ class VideoSession:
         resident `masks` in calls of `batch` frames (`ops.png_encode`) and their bytes reach the host; the masks travel only for the
         overlays."""
         from PIL import Image
-        from .run_on_video import _AsyncSaver, _saver_job
+        from .frame_outputs import _AsyncSaver, _saver_job
         spec = None
         if png_on_device is not None:
             from .png import mask_tables, parse_option
@@ -712,7 +714,7 @@ class VideoSession:
         """The DataFrame run_on_video returns for the frames that have a mask (compute_iou / compute_jf as there)."""
         import pandas as pd
         from .metrics import InLoopScorer
-        from .run_on_video import _cleanup_report, _stats_row, _with_jf
+        from .frame_outputs import _cleanup_report, _stats_row, _with_jf
         host = self._host_masks() if compute_iou else None
         if compute_jf and not self.all_masks_present():
             raise RuntimeError('compute_jf scores the whole video: run propagation on all frames first')
